@@ -8,12 +8,19 @@ N GPUs (config 4 at N=8).  A "step" is one training iteration: T env steps
 of every env + learn() (value step, GAE, 4 policy epochs), i.e. N*T env-steps.
 
     python bench.py [--gpus N --steps K --warmup W] [--config 2|3|5]
+                    [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
         --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 Prints ONE JSON line (rank 0).  The timed region starts with all state
-resident in HBM; rank 0 additionally times the reference CPU path
-(oracle/_ref, single thread) on a bounded sample: `cpu_baseline`.
+resident in HBM.  A plain run sets up, warms up, times the K steps and
+prints the headline (value, ms_per_step, the rooflines that follow from the
+timed region alone).  --full adds what takes runs of its own: the phase
+breakdown (PHASE_ITERS more iterations with events on every launch), the
+numerical health check, the PMC traffic citation of this library build, and
+on rank 0 the reference CPU path (oracle/_ref, single thread) on a bounded
+sample: `cpu_baseline`.  --dump-outputs DIR writes what the last timed step
+left (parameters, trajectory buffers) as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -76,7 +83,48 @@ TRAIN_DTYPE = {
                            "split (dW2) MFMA, f32 accumulate",
     "bf16_split": "f32 via 3-part bf16 split MFMA, f32 accumulate",
 }
-PHASE_ITERS = 3  # the phase-breakdown pass after the timed region
+PHASE_ITERS = 3  # the phase-breakdown pass after the timed region (--full)
+DUMP_SEED = 20241008  # the env sample of --dump-outputs
+DUMP_ENVS = 1024      # envs of the state buffers it keeps
+
+
+def _save(directory, name, arr, rank, world):
+    a = np.asarray(arr)
+    a = a.astype(np.float64 if a.dtype.itemsize > 4 and a.dtype.kind in "iuf"
+                 else np.float32)
+    stem = name if world == 1 else "rank%d_%s" % (rank, name)
+    np.save(os.path.join(directory, stem + ".npy"), a)
+    return a.nbytes
+
+
+def dump_trainer_outputs(tr, directory, rank, world):
+    """--dump-outputs: what a caller holds after the last timed iteration --
+    both networks' parameters and the iteration's trajectory (actions, their
+    probabilities, done flags, state values, targets, advantages), float32.
+    The env states (int8 [T+1][N][B][D]) are kept for a fixed seeded sample
+    of DUMP_ENVS envs.  About 5 MB at config 3."""
+    from dependence_free_rl_amd import POLICY, VALUE, _lib
+    from dependence_free_rl_amd import trainer as t
+    os.makedirs(directory, exist_ok=True)
+    total = _save(directory, "policy_params", tr.params(POLICY), rank, world)
+    total += _save(directory, "value_params", tr.params(VALUE), rank, world)
+    for name, which in (("action", t.BUF_ACTION), ("p_old", t.BUF_POLD),
+                        ("done", t.BUF_DONE), ("v_state", t.BUF_V_STATE),
+                        ("targets", t.BUF_TARGETS), ("advantage", t.BUF_ADV),
+                        ("policy_grads", t.BUF_POLICY_GRADS)):
+        try:
+            a = tr.buffer(which)
+        except _lib.XhError:
+            continue  # this learner keeps no such buffer
+        total += _save(directory, name, a, rank, world)
+    envs = np.arange(tr.N)
+    if tr.N > DUMP_ENVS:
+        envs = np.sort(np.random.default_rng(DUMP_SEED).choice(
+            tr.N, DUMP_ENVS, replace=False))
+    total += _save(directory, "sample_envs", envs.astype(np.int32), rank, world)
+    total += _save(directory, "bins_sample", tr.buffer(t.BUF_BINS)[:, envs],
+                   rank, world)
+    assert total <= 64 << 20, total
 
 
 def kernel_roofline(k, flops_per_launch, avg_ms):
@@ -283,6 +331,10 @@ def env_only(args, cfg, ctx, rank, world, rdzv):
     dt = time.perf_counter() - t0
     if rdzv:
         dt = rdzv.allreduce_max(dt)
+    if args.dump_outputs:  # the last timed step's reward and done flags
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        _save(args.dump_outputs, "reward", env.get(_venv_reward()), rank, world)
+        _save(args.dump_outputs, "done", env.get(_venv_done()), rank, world)
     env.set_timing(True)
     for _ in range(args.steps):
         env.step(fetch=False)
@@ -502,7 +554,17 @@ def main():
     ap.add_argument("--rollout-steps", type=int, default=None,
                     help="T, env steps per env per iteration (default: the "
                          "config's; SURVEY 8(d)'s larger-T throughput point)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also run the phase "
+                         "breakdown, the health check, the PMC traffic "
+                         "citation and the CPU baseline (a plain run prints "
+                         "the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as "
+                         "DIR/<name>.npy (float32; the same arguments give "
+                         "the same inputs in every run)")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: skip the CPU baseline")
     ap.add_argument("--allow-kernel-override", action="store_true",
                     help="run even if XH_TRAIN_KERNEL / XH_ROLLOUT_KERNEL / XH_VALUE_KERNEL / "
                          "XH_W0_FUSE are "
@@ -519,6 +581,8 @@ def main():
                          "this batch size; default: lr_scale_rows)")
     argv = sys.argv[1:]
     args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps needs at least 1 timed step, --warmup at least 0")
     set_over = {k: os.environ[k] for k in KERNEL_OVERRIDES if k in os.environ}
     if set_over and not args.allow_kernel_override:
         print("bench.py: kernel-selection override(s) set %s; unset them or "
@@ -626,23 +690,29 @@ def main():
     if ALGO == "klppo":
         from dependence_free_rl_amd.trainer import BUF_DONE
         n_end = int(np.asarray(tr.buffer(BUF_DONE)).astype(np.int64).sum())
-    # the phase pass also records the last step's probabilities (diagnostics,
-    # off inside the timed region) for the health check after it
-    # the phase breakdown: PHASE_ITERS more iterations (every rank), every
-    # launch timed
-    tr.set_timing(True)
-    tr.set_record_last_step(True)
-    tr.iterate(1)  # (the events' own first use)
-    tr.reset_timing()
-    tr.iterate(PHASE_ITERS)
-    tr.synchronize()
-    ph = {k: tr.kernel_time(k)[0] / PHASE_ITERS
-          for k in ("rollout_step", "policy_train", "value", "reduce_sgd",
-                    "allreduce")}
-    tr.set_timing(False)
-    # numerical health (after the timed region): finite parameters and
-    # last-step probabilities, done rate and mean episode length
-    health = tr.health()
+    # the last timed iteration's results, before the phase pass overwrites them
+    if args.dump_outputs:
+        dump_trainer_outputs(tr, args.dump_outputs, rank, world)
+    ph = health = None
+    if args.full:
+        # the phase pass also records the last step's probabilities
+        # (diagnostics, off inside the timed region) for the health check
+        # after it
+        # the phase breakdown: PHASE_ITERS more iterations (every rank), every
+        # launch timed
+        tr.set_timing(True)
+        tr.set_record_last_step(True)
+        tr.iterate(1)  # (the events' own first use)
+        tr.reset_timing()
+        tr.iterate(PHASE_ITERS)
+        tr.synchronize()
+        ph = {k: tr.kernel_time(k)[0] / PHASE_ITERS
+              for k in ("rollout_step", "policy_train", "value", "reduce_sgd",
+                        "allreduce")}
+        tr.set_timing(False)
+        # numerical health (after the timed region): finite parameters and
+        # last-step probabilities, done rate and mean episode length
+        health = tr.health()
     env_steps = n * world * T * args.steps
     value = env_steps / dt
     # dominant kernel: policy_train (one PPO epoch over N*T env-steps);
@@ -666,10 +736,12 @@ def main():
     split = kt["math"] != "f32_mfma"
     # the split kernels have one shape each: their summaries are keyed by
     # name; the f32 kernels by their PShape<B, D, H1, H2> instantiation
-    lib_sha = library_sha256()
-    traffic, traffic_src, pmc = (
-        pmc_traffic(kt["kernel"], any_shape=True, lib_sha=lib_sha, envs=n) if split
-        else pmc_traffic(lib_sha=lib_sha, envs=n))
+    lib_sha = traffic = traffic_src = pmc = None
+    if args.full:
+        lib_sha = library_sha256()
+        traffic, traffic_src, pmc = (
+            pmc_traffic(kt["kernel"], any_shape=True, lib_sha=lib_sha, envs=n)
+            if split else pmc_traffic(lib_sha=lib_sha, envs=n))
     if args.rollout_steps and args.rollout_steps != cfg["T"]:
         # the PMC passes profile the config's own T: their bytes per launch
         # are not this launch's
@@ -739,11 +811,6 @@ def main():
                    "epochs": EPOCHS, "parallelism": "dp%d" % world,
                    "lr_scale_rows": not args.reference_lr},
         "roofline": dict(roofline, **{
-                     "traffic": traffic,
-                     "traffic_source": traffic_src,
-                     "library_sha256": lib_sha,
-                     "mfma_busy_frac": pmc and pmc.get("mfma_busy_frac"),
-                     "clock_ghz_profiled": pmc and pmc.get("clock_ghz"),
                      "algorithmic_bytes_per_launch": alg_bytes,
                      "avg_launch_ms": round(avg_ms, 4),
                      "flops_per_launch": flops_epoch,
@@ -757,20 +824,30 @@ def main():
                          "achieved": round(hbm_gbs, 2),
                          "peak": HBM_PEAK_GBS * world, "unit": "GB/s",
                          "frac": round(hbm_gbs / (HBM_PEAK_GBS * world), 6)},
-        "health": health,
         "kernels": kinfo,
         "runtime": runtime_info(),
-        "phase_ms_per_step": {
+        "full": args.full,
+    }
+    if args.full:
+        line["roofline"].update({
+            "traffic": traffic,
+            "traffic_source": traffic_src,
+            "library_sha256": lib_sha,
+            "mfma_busy_frac": pmc and pmc.get("mfma_busy_frac"),
+            "clock_ghz_profiled": pmc and pmc.get("clock_ghz")})
+        line["health"] = health
+        line["phase_ms_per_step"] = {
             "rollout": round(ph["rollout_step"], 3),
             "policy_train": round(ph["policy_train"], 3),
             "value": round(ph["value"], 3),
             "reduce_sgd": round(ph["reduce_sgd"], 3),
             "allreduce": round(ph["allreduce"], 3),
             "source": "%d iterations after the timed region, HIP events on "
-                      "every launch" % PHASE_ITERS},
-    }
+                      "every launch" % PHASE_ITERS}
+    if args.dump_outputs:
+        line["dump_outputs"] = args.dump_outputs
     # the CPU baseline is timed on rank 0 of the N=1 run only
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         line["cpu_baseline"] = cpu_baseline()
     if rank == 0:
         print(json.dumps(line), flush=True)

@@ -288,6 +288,66 @@ def test_bench_json_line(tmp_path):
     assert 0 < d["iteration_roofline"]["frac"] < 1
 
 
+def _bench(*extra):
+    import json
+    import os
+    import subprocess
+    import sys
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = subprocess.run(
+        [sys.executable, os.path.join(repo, "bench.py"), "--gpus", "1",
+         "--steps", "2", "--warmup", "1", "--envs", "256"] + list(extra),
+        capture_output=True, text=True, timeout=110, check=True, cwd=repo)
+    lines = [l for l in out.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1
+    return json.loads(lines[0])
+
+
+def test_bench_plain_run_is_lean_and_dumps_its_outputs(tmp_path):
+    """A plain run prints the headline without the passes of --full, and
+    --dump-outputs writes the last timed step's arrays as float32 .npy files,
+    identical from run to run (fixed seeds, deterministic kernels)."""
+    import os
+    runs = []
+    for k in range(2):
+        d = _bench("--dump-outputs", str(tmp_path / ("run%d" % k)))
+        for key in ("metric", "value", "unit", "higher_is_better", "dtype",
+                    "ms_per_step"):
+            assert key in d, key
+        for key in ("health", "phase_ms_per_step", "cpu_baseline"):
+            assert key not in d, key
+        assert d["full"] is False and "traffic" not in d["roofline"]
+        assert d["steps"] == 2 and d["ms_per_step"] > 0
+        files = sorted(os.listdir(tmp_path / ("run%d" % k)))
+        runs.append({f: np.load(tmp_path / ("run%d" % k) / f) for f in files})
+    a, b = runs
+    assert sorted(a) == sorted(b)
+    for name in ("policy_params.npy", "value_params.npy", "action.npy",
+                 "p_old.npy", "advantage.npy", "bins_sample.npy"):
+        assert name in a, sorted(a)
+    for name in a:
+        assert a[name].dtype in (np.float32, np.float64), name
+        assert np.isfinite(a[name]).all(), name
+        np.testing.assert_array_equal(a[name], b[name], err_msg=name)
+    assert a["action.npy"].shape == (4, 256)
+    assert a["bins_sample.npy"].shape == (5, 256, 64, 2)
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    # two updates moved the parameters away from their initial values
+    from dependence_free_rl_amd import init_policy
+    assert np.any(a["policy_params.npy"] != init_policy(2, 128, 128, seed=0))
+
+
+def test_bench_full_line():
+    """--full adds the passes after the timed region: the phase breakdown,
+    the health check and the PMC citation's library hash."""
+    d = _bench("--full", "--no-cpu-baseline")
+    assert d["full"] is True and d["health"]["finite"] is True
+    ph = d["phase_ms_per_step"]
+    assert ph["policy_train"] > 0 and ph["rollout"] > 0
+    assert len(d["roofline"]["library_sha256"]) == 64
+    assert "traffic" in d["roofline"] and "cpu_baseline" not in d
+
+
 def _c3_health_run(ctx, iters, **kw):
     from dependence_free_rl_amd import POLICY, VALUE, Trainer, init_policy, init_value
     from dependence_free_rl_amd.trainer import BUF_ADV

@@ -13,7 +13,7 @@ fi
 for rep in $(seq ${REPS:-3}); do
   for side in A B; do
     if [ $side = A ]; then e="$ENVA"; else e="$ENVB"; fi
-    env $e timeout -k 10 200 python bench.py --config ${CONFIG:-3} --steps 5 --warmup 2 --no-cpu-baseline $EXTRA \
+    env $e timeout -k 10 200 python bench.py --full --config ${CONFIG:-3} --steps 5 --warmup 2 --no-cpu-baseline $EXTRA \
       > gpurun_out/abe_$side.json 2> gpurun_out/abe_$side.err || { echo "$side failed"; tail -5 gpurun_out/abe_$side.err; exit 1; }
     python -c "
 import json

@@ -14,6 +14,6 @@ done
 [ $rc = 0 ] || exit $rc
 timeout -k 10 200 python -u bench.py --env-only --steps 50 --warmup 5 \
     > $O/profiles/${TAG}_bench_envonly.json 2> $O/envonly.err || { tail -5 $O/envonly.err; exit 1; }
-timeout -k 10 300 python -u bench.py --steps 10 --no-cpu-baseline \
+timeout -k 10 300 python -u bench.py --full --steps 10 --no-cpu-baseline \
     > $O/profiles/${TAG}_bench_config3.json 2> $O/b3.err || { tail -5 $O/b3.err; exit 1; }
 cut -c1-600 $O/profiles/${TAG}_bench_envonly.json $O/profiles/${TAG}_bench_config3.json

@@ -19,6 +19,7 @@ OBJS     := $(SRC)/policy_kernels.o $(SRC)/value_kernels.o \
             $(SRC)/policy_split8x_kernels.o $(SRC)/policy_split8x_kl_kernels.o \
             $(SRC)/policy_split4h_kernels.o $(SRC)/policy_split4h_kl_kernels.o \
             $(SRC)/loss_kernels.o $(SRC)/tensor_kernels.o \
+            $(SRC)/stats_kernels.o \
             $(SRC)/train_select.o $(SRC)/model_api.o $(SRC)/tensor_api.o \
             $(SRC)/xylo_hip.o
 # superseded train kernels (the config-3 / config-5

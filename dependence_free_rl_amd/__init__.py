@@ -3,6 +3,12 @@ path for vectorised bin packing (drop-in for beehover/dependence_free_rl's
 xylo::rl / xylo::policy_gradient hot path).  See DESIGN.md."""
 from ._lib import (XhError, device_count, lib,  # noqa: F401  (fails loudly
                    runtime_info)                 # if not built)
+from ._lib import (STAT_ADV_SQSUM, STAT_ADV_SUM, STAT_COUNT,  # noqa: F401
+                   STAT_EPISODES, STAT_EPLEN_SQSUM, STAT_EPLEN_SUM, STAT_ITER,
+                   STAT_KL_BETA, STAT_KL_MEAN, STAT_NEGLOGP_SUM,
+                   STAT_PGRAD_SQ_FIRST, STAT_PGRAD_SQ_LAST, STAT_REWARD_SUM,
+                   STAT_TARGET_SQSUM, STAT_TARGET_SUM, STAT_TRANSITIONS,
+                   STAT_VERR_SQSUM, STAT_VERR_SUM, STAT_VGRAD_SQ)
 from .trainer import (ALGOS, POLICY, VALUE, Context, Trainer,  # noqa: F401
                       heuristic_evaluate, init_full_policy, init_policy,
                       init_value,

@@ -22,6 +22,12 @@ OPTIMIZERS = {"sgd": 0, "momentum": 1, "adam": 2}
 (BUF_BINS, BUF_ITEMS, BUF_ACTION, BUF_POLD, BUF_DONE, BUF_RNG, BUF_V_STATE,
  BUF_V_TERM, BUF_TARGETS, BUF_ADV, BUF_VALUE_GRAD, BUF_POLICY_GRADS,
  BUF_LOGITS, BUF_PROBS, BUF_V_STATE0, BUF_QOLD, BUF_KL, BUF_LEN) = range(18)
+# one row of training statistics (the XH_STAT_* enum; xh_trainer_set_stats)
+(STAT_ITER, STAT_TRANSITIONS, STAT_EPISODES, STAT_EPLEN_SUM, STAT_EPLEN_SQSUM,
+ STAT_REWARD_SUM, STAT_NEGLOGP_SUM, STAT_VERR_SUM, STAT_VERR_SQSUM,
+ STAT_TARGET_SUM, STAT_TARGET_SQSUM, STAT_ADV_SUM, STAT_ADV_SQSUM,
+ STAT_PGRAD_SQ_FIRST, STAT_PGRAD_SQ_LAST, STAT_VGRAD_SQ, STAT_KL_BETA,
+ STAT_KL_MEAN, STAT_COUNT) = range(19)
 
 
 class XhError(RuntimeError):
@@ -127,6 +133,9 @@ def _load():
                                    C.c_float, C.c_float, vp, vp, vp, vp, sz]),
         "xh_trainer_forget": (i, [vp]),
         "xh_trainer_set_record_last_step": (i, [vp, i]),
+        "xh_trainer_set_stats": (i, [vp, i]),
+        "xh_trainer_stats_count": (i, [vp, C.POINTER(C.c_long)]),
+        "xh_trainer_get_stats": (i, [vp, C.c_long, i, vp]),
         "xh_tensor_reduce": (i, [vp, i, vp, vp, C.c_float, sz, i,
                                  C.POINTER(C.c_double),
                                  C.POINTER(C.c_int64)]),
@@ -154,6 +163,10 @@ for _name, _mirror in (("xh_config", Config), ("xh_eval", Eval),
         raise ImportError("ctypes mirror of %s is out of date (%d vs %d bytes)"
                           % (_name, C.sizeof(_mirror),
                              lib.xh_struct_size(_name.encode())))
+if lib.xh_struct_size(b"xh_stat_row") != STAT_COUNT * 8:
+    raise ImportError("STAT_* indices are out of date (%d entries, the library "
+                      "has %d)" % (STAT_COUNT,
+                                   lib.xh_struct_size(b"xh_stat_row") // 8))
 
 
 def check(status):

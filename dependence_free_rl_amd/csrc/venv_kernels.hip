@@ -278,7 +278,7 @@ static dim3 venv_grid(int N, int B) {
   const long waves = (N + epw - 1) / epw;
   return dim3((unsigned)((waves + 3) / 4));
 }
-// the step kernel's (VStepShape: 4 bins per lane)
+// the step kernel's (VStepShape: XH_VENV_BPL = 16 bins per lane, at most B)
 static dim3 venv_step_grid(int N, int B) {
   const int epw = 64 / (B / (XH_VENV_BPL < B ? XH_VENV_BPL : B));
   const long waves = (N + epw - 1) / epw;

@@ -438,6 +438,34 @@ hipError_t launch_adv_stats(const double *part, int nparts, double *stats,
                             hipStream_t s);
 hipError_t launch_adv_normalize(float *adv, long n, const double *stats,
                                 double count, hipStream_t s);
+
+// On-device training statistics (stats_kernels.hip; xh_trainer_set_stats):
+// double sums, one partial per workgroup ([gae_grid(N)][S] doubles), summed in
+// a fixed order by one wave into the iteration's row of XH_STAT_COUNT doubles.
+constexpr int kStatEpisodeSums = 4;  // episodes, len, len^2, -log p_old
+constexpr int kStatEpisodeSummed = 5;  // row entries EPISODES .. NEGLOGP_SUM
+constexpr int kStatLearnerSums = 6;  // row entries VERR_SUM .. ADV_SQSUM
+// episode part: ep_len[N] carries every env's running episode length
+hipError_t launch_episode_stats(const uint8_t *done, const float *pold, int N,
+                                int T, int *ep_len, double *part,
+                                hipStream_t s);
+// opens `row`: episode part from the partials, NaN in the learner part
+hipError_t launch_episode_row(const double *part, int nparts, double iter,
+                              double transitions_global,
+                              double transitions_local, double *row,
+                              hipStream_t s);
+// learner part: sums of target - V0, target and the advantage, and squares
+hipError_t launch_learner_stats(const float *v0, const float *targets,
+                                const float *adv, int N, int T, double *part,
+                                hipStream_t s);
+// squared L2 norms of the first / last policy gradient and the value gradient
+hipError_t launch_grad_norms(const float *g_first, const float *g_last, int np,
+                             const float *gv, int nv, double *out,
+                             hipStream_t s);
+// kl_last: the last epoch's XH_BUF_KL record, or nullptr (not KL-PPO)
+hipError_t launch_learner_row(const double *part, int nparts,
+                              const double *norms, const float *kl_last,
+                              double *row, hipStream_t s);
 // Slab entries the value net's reduced layer 0 leaves unwritten: the item
 // columns of bins b > 0 of its first [rows][in] block, whose sums equal bin
 // 0's (EpSlabRed).  B = 0: none.

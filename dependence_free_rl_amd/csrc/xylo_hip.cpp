@@ -114,6 +114,17 @@ struct xh_trainer {
     int *host_active = nullptr;  // pinned
     int slot_end = 0;            // slot holding the envs' current states
   } pg;
+  // xh_trainer_set_stats (opt-in; everything null / 0 while off): the device
+  // ring of rows, the envs' running episode lengths, the kernels' workgroup
+  // partials and the three gradient norms; rows = rows opened so far; open =
+  // the last row's window is not consumed yet (learn() fills its learner part)
+  struct stats_state {
+    int history = 0;
+    long rows = 0;
+    bool open = false;
+    double *ring = nullptr, *part = nullptr, *norms = nullptr;
+    int *ep_len = nullptr;
+  } stats;
   int Tb = 0;  // Batch steps: cfg.steps, or REINFORCE's per-iteration bound
   uint32_t jump_mul = 1;
   int rgrid = 0;
@@ -345,6 +356,7 @@ constexpr uint64_t kEvalStride = 1ull << 26;  // draws between env streams
 // (= BASELINE configs 3 and 5 per GPU: 131072 groups over 256 workgroups)
 constexpr int kMaxTrainDepth = 512;
 constexpr int kBinCapacity = 8;             // bin_packing.h:48, every dim
+constexpr int kMaxStatsRows = 1 << 20;      // xh_trainer_set_stats: 151 MB
 
 xh::EnvDesc make_env(int bins, int dims) {
   static const int ia[3][3] = {{4, 0, 0}, {4, 2, 0}, {4, 2, 2}};
@@ -508,6 +520,73 @@ int reduce_and_step(xh_trainer *t, int which, const float *slab, int nslab,
   return opt_apply(t, which, params, grad, n);
 }
 
+// ---------------------------------------------------------- statistics ----
+// xh_trainer_set_stats: one row per iteration in the device ring.  The summed
+// entries of each part are contiguous in the row, so with a communicator one
+// all-reduce per phase runs in place on the row between the kernels' partial
+// sums and any read of it; without a communicator none is launched.
+void stats_free(xh_trainer *t) {
+  auto &st = t->stats;
+  if (st.ring) (void)hipFree(st.ring);
+  if (st.part) (void)hipFree(st.part);
+  if (st.norms) (void)hipFree(st.norms);
+  if (st.ep_len) (void)hipFree(st.ep_len);
+  st = xh_trainer::stats_state{};
+}
+
+double *stats_row(xh_trainer *t, long row) {
+  return t->stats.ring + (size_t)(row % t->stats.history) * XH_STAT_COUNT;
+}
+
+// After the rollout launches: open row `rows` with the episode part.
+int stats_rollout(xh_trainer *t) {
+  auto &st = t->stats;
+  hipStream_t s = t->ctx->stream;
+  const int N = (int)t->N(), T = (int)t->T();
+  double *row = stats_row(t, st.rows);
+  CHK(timed(t, "stats", [&]() {
+    return xh::launch_episode_stats(t->done, t->pold, N, T, st.ep_len, st.part,
+                                    s);
+  }));
+  CHK(timed(t, "stats", [&]() {
+    return xh::launch_episode_row(st.part, xh::gae_grid(N), (double)st.rows,
+                                  (double)T * t->cfg.num_envs_global,
+                                  (double)T * N, row, s);
+  }));
+  CHK(allreduce_d(t, row + XH_STAT_EPISODES, xh::kStatEpisodeSummed));
+  ++st.rows;
+  st.open = true;
+  return XH_OK;
+}
+
+// At the end of learn(): the learner part of the open row (none is open when
+// statistics were switched on after this window's rollout).
+int stats_learn(xh_trainer *t) {
+  auto &st = t->stats;
+  if (!st.open) return XH_OK;
+  hipStream_t s = t->ctx->stream;
+  const int N = (int)t->N(), T = (int)t->T();
+  double *row = stats_row(t, st.rows - 1);
+  CHK(timed(t, "stats", [&]() {
+    return xh::launch_learner_stats(t->v_state0, t->targets, t->adv, N, T,
+                                    st.part, s);
+  }));
+  CHK(timed(t, "stats", [&]() {
+    return xh::launch_grad_norms(
+        t->pgrads, t->pgrads + (size_t)(t->cfg.epochs - 1) * t->np, t->np,
+        t->vgrad, t->nv, st.norms, s);
+  }));
+  CHK(timed(t, "stats", [&]() {
+    return xh::launch_learner_row(
+        st.part, xh::gae_grid(N), st.norms,
+        t->kl_log ? t->kl_log + 3 * (size_t)(t->cfg.epochs - 1) : nullptr, row,
+        s);
+  }));
+  CHK(allreduce_d(t, row + XH_STAT_VERR_SUM, xh::kStatLearnerSums));
+  st.open = false;
+  return XH_OK;
+}
+
 int do_pg_rollout(xh_trainer *t);
 int do_pg_learn(xh_trainer *t);
 
@@ -639,6 +718,7 @@ int do_rollout(xh_trainer *t) {
     t->bins_wide[step + 1] = 0;  // apply + reset on game over: bins >= 0
   }
   t->rolled = true;
+  if (t->stats.history) CHK(stats_rollout(t));
   return XH_OK;
 }
 
@@ -959,6 +1039,7 @@ int do_learn(xh_trainer *t) {
       }));
     }
   }
+  if (t->stats.history) CHK(stats_learn(t));
   t->need_shift = true;
   t->rolled = false;
   return XH_OK;
@@ -1282,6 +1363,7 @@ size_t xh_struct_size(const char *name) {
   if (!std::strcmp(name, "xh_config")) return sizeof(xh_config);
   if (!std::strcmp(name, "xh_eval")) return sizeof(xh_eval);
   if (!std::strcmp(name, "xh_layer")) return sizeof(xh_layer);
+  if (!std::strcmp(name, "xh_stat_row")) return XH_STAT_COUNT * sizeof(double);
   return 0;
 }
 
@@ -1591,6 +1673,7 @@ int xh_trainer_destroy(xh_trainer *t) {
     }
     for (hipEvent_t e : t->event_pool) (void)hipEventDestroy(e);
     for (void *p : t->allocs) (void)hipFree(p);
+    stats_free(t);
     if (t->pg.host_active) (void)hipHostFree(t->pg.host_active);
     xh_ctx *c = t->ctx;
     const bool counted = t->counted;
@@ -1720,6 +1803,85 @@ int xh_trainer_forget(xh_trainer *t) {
                   "forget()");
     t->need_shift = true;  // as at the end of do_learn / do_pg_learn
     t->rolled = false;
+    t->stats.open = false;  // the row's learner part stays NaN
+    return XH_OK;
+  });
+}
+
+int xh_trainer_set_stats(xh_trainer *t, int history_rows) {
+  return guard([&]() -> int {
+    if (!t) return fail(XH_ERR_INVALID, "null trainer");
+    if (t->cfg.algo == XH_PG)
+      return fail(XH_ERR_INVALID, "set_stats: not for XH_PG trainers (REINFORCE "
+                  "plays whole episodes: XH_BUF_LEN)");
+    if (history_rows < 0 || history_rows > kMaxStatsRows)
+      return fail(XH_ERR_INVALID, "set_stats: history_rows %d not in [0, %d]",
+                  history_rows, kMaxStatsRows);
+    HIPCHK(hipSetDevice(t->ctx->device));
+    hipStream_t s = t->ctx->stream;
+    HIPCHK(hipStreamSynchronize(s));
+    stats_free(t);
+    if (history_rows == 0) return XH_OK;
+    auto &st = t->stats;
+    const size_t ring = (size_t)history_rows * XH_STAT_COUNT * 8,
+                 part = (size_t)xh::gae_grid((int)t->N()) *
+                        xh::kStatLearnerSums * 8;
+    hipError_t e = hipMalloc((void **)&st.ring, ring);
+    if (e == hipSuccess) e = hipMalloc((void **)&st.part, part);
+    if (e == hipSuccess) e = hipMalloc((void **)&st.norms, 3 * 8);
+    if (e == hipSuccess) e = hipMalloc((void **)&st.ep_len, t->N() * 4);
+    // unwritten rows read as NaN (all-ones bytes); running lengths from zero
+    if (e == hipSuccess) e = hipMemsetAsync(st.ring, 0xFF, ring, s);
+    if (e == hipSuccess) e = hipMemsetAsync(st.ep_len, 0, t->N() * 4, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) {
+      stats_free(t);
+      return fail(XH_ERR_HIP, "set_stats(%d): %s", history_rows,
+                  hipGetErrorString(e));
+    }
+    st.history = history_rows;
+    return XH_OK;
+  });
+}
+
+int xh_trainer_stats_count(xh_trainer *t, long *total_rows) {
+  return guard([&]() -> int {
+    if (!t || !total_rows) return fail(XH_ERR_INVALID, "null arg");
+    if (!t->stats.history)
+      return fail(XH_ERR_STATE, "stats_count: statistics are off "
+                  "(xh_trainer_set_stats)");
+    *total_rows = t->stats.rows;
+    return XH_OK;
+  });
+}
+
+int xh_trainer_get_stats(xh_trainer *t, long first, int count, double *out) {
+  return guard([&]() -> int {
+    if (!t || (count > 0 && !out)) return fail(XH_ERR_INVALID, "null arg");
+    const auto &st = t->stats;
+    if (!st.history)
+      return fail(XH_ERR_STATE, "get_stats: statistics are off "
+                  "(xh_trainer_set_stats)");
+    if (first < 0 || count < 0 || first > st.rows - count)
+      return fail(XH_ERR_INVALID, "get_stats: %d rows from row %ld, %ld written",
+                  count, first, st.rows);
+    if (first < st.rows - st.history)
+      return fail(XH_ERR_INVALID, "get_stats: row %ld is overwritten (the ring "
+                  "holds rows %ld .. %ld)", first, st.rows - st.history,
+                  st.rows - 1);
+    HIPCHK(hipSetDevice(t->ctx->device));
+    hipStream_t s = t->ctx->stream;
+    HIPCHK(hipStreamSynchronize(s));
+    // at most two runs of the ring
+    const long at = first % st.history;
+    const long n1 = std::min<long>(count, st.history - at);
+    const size_t rowb = (size_t)XH_STAT_COUNT * 8;
+    if (n1 > 0)
+      HIPCHK(copy_to_host(out, st.ring + (size_t)at * XH_STAT_COUNT,
+                          (size_t)n1 * rowb, s));
+    if (count > n1)
+      HIPCHK(copy_to_host(out + (size_t)n1 * XH_STAT_COUNT, st.ring,
+                          (size_t)(count - n1) * rowb, s));
     return XH_OK;
   });
 }
@@ -1828,6 +1990,10 @@ int xh_trainer_set_buffer(xh_trainer *t, int which, const void *host,
     HIPCHK(copy_to_device(buffer_ptr(t, which), host, bytes, t->ctx->stream));
     HIPCHK(hipStreamSynchronize(t->ctx->stream));
     if (which == XH_BUF_BINS || which == XH_BUF_ITEMS) t->need_shift = false;
+    // statistics: uploaded bin states start new episodes, as
+    // xh_trainer_set_env_state's do
+    if (which == XH_BUF_BINS && t->stats.ep_len)
+      HIPCHK(hipMemsetAsync(t->stats.ep_len, 0, t->N() * 4, t->ctx->stream));
     if (!ok.empty()) t->items_ok = std::move(ok);
     if (!wide.empty()) t->bins_wide = std::move(wide);
     return XH_OK;
@@ -2056,6 +2222,13 @@ int xh_trainer_set_env_state(xh_trainer *t, int first, int count,
       std::memcpy(v.data(), bins + (size_t)e * BD, BD);
       std::memcpy(v.data() + BD, items + (size_t)e * D, D);
       t->env_override[first + e] = std::move(v);
+    }
+    // statistics: a replaced state starts a new episode (ordered on the
+    // stream after the last window's episode_stats_kernel)
+    if (t->stats.ep_len && count > 0) {
+      HIPCHK(hipSetDevice(t->ctx->device));
+      HIPCHK(hipMemsetAsync(t->stats.ep_len + first, 0, (size_t)count * 4,
+                            t->ctx->stream));
     }
     return XH_OK;
   });

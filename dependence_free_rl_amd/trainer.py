@@ -356,6 +356,7 @@ class Trainer:
         check(_lib.lib.xh_trainer_create(ctx.h, C.byref(cfg), C.byref(self.h)))
         self.np_ = _lib.lib.xh_trainer_num_params(self.h, POLICY)
         self.nv = _lib.lib.xh_trainer_num_params(self.h, VALUE)
+        self._stats_rows = 0  # set_stats: rows of the device ring (0 = off)
         if algo == "pg":  # steps = episodes per env; the batch has a step bound
             self.episodes = steps
             self.T = _lib.lib.xh_trainer_buffer_bytes(self.h, BUF_ACTION) // (
@@ -508,6 +509,68 @@ class Trainer:
         """Re-base the env streams on global engine state x (reference order:
         env g steps from x advanced 4*T*g draws)."""
         check(_lib.lib.xh_trainer_seed_streams(self.h, x))
+
+    # -------------------------------------------------------- statistics --
+    def set_stats(self, history_rows):
+        """On-device training statistics (xh_trainer_set_stats): from the next
+        rollout on every iteration leaves one row of STAT_COUNT doubles in a
+        device ring of `history_rows` rows; 0 turns them off (the default)."""
+        check(_lib.lib.xh_trainer_set_stats(self.h, int(history_rows)))
+        self._stats_rows = int(history_rows)
+
+    def stats_count(self):
+        """Rows written since set_stats (xh_trainer_stats_count)."""
+        n = C.c_long()
+        check(_lib.lib.xh_trainer_stats_count(self.h, C.byref(n)))
+        return n.value
+
+    def stats(self, first=None, count=None):
+        """Rows [first, first + count) as a float64 [rows][STAT_COUNT] array
+        (xh_trainer_get_stats; synchronises).  Default: every row still in
+        the ring, up to the last one written."""
+        total = self.stats_count()
+        if first is None:
+            first = max(0, total - self._stats_rows)
+        if count is None:
+            count = max(0, total - first)
+        out = np.zeros((count, _lib.STAT_COUNT), np.float64)
+        check(_lib.lib.xh_trainer_get_stats(self.h, first, count, _ptr(out)))
+        return out
+
+    def training_curve(self, first=None, count=None):
+        """Per-row series derived from stats(): a dict of float64 arrays.
+        mean_episode_len / mean_episode_return are NaN where no episode ended
+        (an episode's return is its length - 1: reward 1 per step, 0 on the
+        overflowing one); the learner series are NaN for a row learn() did
+        not fill; kl_beta / kl_mean are NaN unless KL-PPO."""
+        s = self.stats(first, count)
+        col = lambda k: s[:, k]  # noqa: E731
+        with np.errstate(divide="ignore", invalid="ignore"):
+            n = col(_lib.STAT_TRANSITIONS)
+            ep = col(_lib.STAT_EPISODES)
+            mean_len = np.where(ep > 0, col(_lib.STAT_EPLEN_SUM) / ep, np.nan)
+            verr = col(_lib.STAT_VERR_SUM) / n
+            mse = col(_lib.STAT_VERR_SQSUM) / n
+            tmean = col(_lib.STAT_TARGET_SUM) / n
+            tvar = col(_lib.STAT_TARGET_SQSUM) / n - tmean * tmean
+            amean = col(_lib.STAT_ADV_SUM) / n
+            avar = col(_lib.STAT_ADV_SQSUM) / n - amean * amean
+            return {
+                "iteration": col(_lib.STAT_ITER).copy(),
+                "episodes": ep.copy(),
+                "mean_episode_len": mean_len,
+                "mean_episode_return": mean_len - 1.0,
+                "entropy_estimate": col(_lib.STAT_NEGLOGP_SUM) / n,
+                "value_loss": mse,
+                "explained_variance": 1.0 - (mse - verr * verr) / tvar,
+                "adv_mean": amean,
+                "adv_std": np.sqrt(np.maximum(avar, 0.0)),
+                "policy_grad_norm_first": np.sqrt(col(_lib.STAT_PGRAD_SQ_FIRST)),
+                "policy_grad_norm_last": np.sqrt(col(_lib.STAT_PGRAD_SQ_LAST)),
+                "value_grad_norm": np.sqrt(col(_lib.STAT_VGRAD_SQ)),
+                "kl_beta": col(_lib.STAT_KL_BETA).copy(),
+                "kl_mean": col(_lib.STAT_KL_MEAN).copy(),
+            }
 
     # ------------------------------------------------------------ timing --
     def set_timing(self, on):

@@ -282,6 +282,87 @@ int xh_trainer_get_env_state(xh_trainer *t, int first, int count, int8_t *bins,
 int xh_trainer_set_env_state(xh_trainer *t, int first, int count,
                              const int8_t *bins, const int8_t *items);
 
+/* ------------------------------------------- training statistics ---- */
+/* On-device training statistics, off by default: with them off no launch is
+ * added and no buffer allocated.  With them on, every iteration leaves one
+ * row of XH_STAT_COUNT doubles in a device ring of `history_rows` rows, so
+ * that xh_trainer_iterate(t, n) can be followed by ONE synchronising read of
+ * its n rows (the reference drivers report only a separate 100-episode argmax
+ * evaluation every 100 rounds, ppo_training.cc:67-81; an episode spans
+ * several play_steps(T) windows, rl.h:325-360, so no single batch holds its
+ * return).
+ *
+ * The rollout opens a row and writes the episode part; learn() fills the
+ * learner part of the open row.  A row whose window xh_trainer_forget
+ * consumed, or nothing consumed yet, keeps NaN in its learner part.
+ *
+ * Every entry is a double sum formed on the device without floating-point
+ * atomics: per-workgroup partials, then a fixed-order sum in one wave, so a
+ * row is bit-identical from run to run.  In a world > 1 job the "summed"
+ * entries are the job's (one SUM all-reduce of doubles per phase); the others
+ * are job-wide already. */
+enum {
+  /* -- episode part (rollout); summed over ranks from EPISODES on -- */
+  XH_STAT_ITER = 0,        /* row index: rollouts since xh_trainer_set_stats */
+  XH_STAT_TRANSITIONS = 1, /* T * num_envs_global (every agent's
+                              play_steps(T), rl.h:356-360)                   */
+  XH_STAT_EPISODES = 2,    /* episodes that ended in this window (game_over,
+                              bin_packing.h:94-101; rl.h:341-346)            */
+  XH_STAT_EPLEN_SUM = 3,   /* over those episodes: length in env steps, the
+                              overflowing step included, counted across
+                              windows and the forget() shift (rl.h:274-291)  */
+  XH_STAT_EPLEN_SQSUM = 4, /* ... and its square                             */
+  XH_STAT_REWARD_SUM = 5,  /* reward of the window: 1 per step, 0 on the
+                              overflowing step (bin_packing.h:102-106) =
+                              transitions - dones; an episode's return is its
+                              length - 1                                     */
+  XH_STAT_NEGLOGP_SUM = 6, /* sum of -log((double)p_old) over the window
+                              (XH_BUF_POLD: distrib[choice], rl.h:27-30); its
+                              mean estimates the sampling policy's entropy   */
+  /* -- learner part (learn()), summed over ranks: over the T * N
+        transition rows of update_value_model / calculate_advantage
+        (policy_gradient.h:196-281) -- */
+  XH_STAT_VERR_SUM = 7,    /* target - V0: XH_BUF_TARGETS - XH_BUF_V_STATE0
+                              (the value step's -dL/dV, nn.h:548-550)        */
+  XH_STAT_VERR_SQSUM = 8,  /* its square: / rows = the value loss (mean
+                              squared error of the pre-update values)        */
+  XH_STAT_TARGET_SUM = 9,  /* TD target (policy_gradient.h:205-215)          */
+  XH_STAT_TARGET_SQSUM = 10,
+  XH_STAT_ADV_SUM = 11,    /* XH_BUF_ADV as the policy epochs read it (after
+                              xh_config.adv_normalize when that is on)       */
+  XH_STAT_ADV_SQSUM = 12,
+  /* -- learner part, job-wide after the gradient all-reduce -- */
+  XH_STAT_PGRAD_SQ_FIRST = 13, /* squared L2 norm of the first epoch's policy
+                              gradient (XH_BUF_POLICY_GRADS row 0;
+                              optimize_action, policy_gradient.h:297-307)    */
+  XH_STAT_PGRAD_SQ_LAST = 14,  /* ... of the last epoch's                     */
+  XH_STAT_VGRAD_SQ = 15,   /* squared L2 norm of XH_BUF_VALUE_GRAD           */
+  XH_STAT_KL_BETA = 16,    /* XH_KLPPO: the last epoch's new beta (XH_BUF_KL;
+                              policy_gradient.h:310-335); NaN otherwise      */
+  XH_STAT_KL_MEAN = 17,    /* XH_KLPPO: the last epoch's mean KL; NaN
+                              otherwise                                      */
+  XH_STAT_COUNT
+};
+/* history_rows > 0 (at most 2^20): statistics on, with a fresh device ring of
+ * history_rows x XH_STAT_COUNT doubles and an int32 [N] array of running
+ * episode lengths; every env's running length and the row counter restart at
+ * zero.  0: off, buffers freed.  XH_PG: XH_ERR_INVALID (REINFORCE plays whole
+ * episodes and reports XH_BUF_LEN).  xh_trainer_set_env_state on an env zeroes
+ * its running length: the replaced state starts a new episode and the
+ * replaced one is not counted as finished; xh_trainer_set_buffer(XH_BUF_BINS)
+ * does the same for every env (XH_BUF_ITEMS alone changes no count).
+ * In a world > 1 job every rank must switch statistics on and off at the same
+ * point of its loop: the statistics add one all-reduce per phase, which has
+ * to meet the same all-reduce on every other rank. */
+int xh_trainer_set_stats(xh_trainer *t, int history_rows);
+/* Rows written since statistics were switched on. */
+int xh_trainer_stats_count(xh_trainer *t, long *total_rows);
+/* Synchronises the stream and copies rows [first, first + count) to out
+ * [count][XH_STAT_COUNT].  XH_ERR_INVALID for rows the ring has overwritten
+ * (first < total - history_rows) or not written yet; XH_ERR_STATE when
+ * statistics are off. */
+int xh_trainer_get_stats(xh_trainer *t, long first, int count, double *out);
+
 /* ------------------------------------------------- vectorised envs ---- */
 /* N bp::environment instances (bin_packing.h:46-85, generalised to B bins /
  * D dims as the trainer's) whose state stays in HBM, for a caller that brings
@@ -497,7 +578,8 @@ int xh_tensor_transpose(xh_ctx *ctx, const float *in, float *out, int rows,
 
 /* sizeof of the ABI structs ("xh_config", "xh_eval", "xh_layer"; 0 if
  * unknown), so a
- * foreign-language binding can check its mirror of them. */
+ * foreign-language binding can check its mirror of them.  "xh_stat_row": the
+ * bytes of one statistics row, XH_STAT_COUNT * 8. */
 size_t xh_struct_size(const char *name);
 
 /* Kernel timing with HIP events on the trainer's stream (off by default).
@@ -507,6 +589,8 @@ size_t xh_struct_size(const char *name);
 #define XH_TIMING_TRAIN 2
 int xh_trainer_set_timing(xh_trainer *t, int on);
 /* name: "rollout_step" | "policy_train" | "value" | "reduce_sgd" | "allreduce"
+ * | "stats" (the statistics launches of xh_trainer_set_stats; their
+ * all-reduces count under "allreduce").
  * Returns accumulated milliseconds and launch count since the last reset. */
 int xh_trainer_kernel_time(xh_trainer *t, const char *name, double *ms,
                            long *launches);

@@ -98,9 +98,15 @@ $(SRC)/tensor_api.o: $(SRC)/tensor_api.cpp $(HDRS)
 
 # the variant library: the product objects + the superseded train kernels,
 # with the dispatch that reaches them (XH_TRAIN_KERNEL=split4w / split8w /
-# split8wp / split4p / split8wg / split128); loaded through XH_LIB_PATH only
+# split8wp / split4p / split8wg / split128 / spec8_3p); loaded through
+# XH_LIB_PATH only
 VDIR := build/variants
-VOBJS := $(patsubst %,$(VDIR)/%.o,$(VARIANT_KERNELS))
+VOBJS := $(patsubst %,$(VDIR)/%.o,$(VARIANT_KERNELS)) $(VDIR)/policy_spec8_3p_kernels.o
+# the wave-specialised config-3 epoch with dW2 on the three-part bf16 split
+# (its form before the f16-pair dW2; XH_TRAIN_KERNEL=spec8_3p)
+$(VDIR)/policy_spec8_3p_kernels.o: $(SRC)/policy_spec8_kernels.hip $(HDRS)
+	@mkdir -p $(VDIR)
+	$(HIPCC) $(HIPFLAGS) $(FLAGS_policy_spec8_kernels) -DXH_SP8_DW2_3P=1 -c $< -o $@
 $(VDIR)/%.o: research/variants/%.hip $(HDRS)
 	@mkdir -p $(VDIR)
 	$(HIPCC) $(HIPFLAGS) $(FLAGS_$*) -c $< -o $@

@@ -15,11 +15,24 @@
 // 1066 / 770 alone; 256 v_fma_f32: 1612 against 1066 / 1376), with the 32x32x16
 // shape (16x16x32: 1812).
 //
-// Numerics as policy_train_split8wh_kernel: layer 2 and
-// dH1 on f16 pairs scaled by powers of two (S_W W2, S_D W2' = S_D diag(w3)
-// W2, S_H H1; three / two f16 MFMAs per K slice), dW2 on the exact bf16
-// three-part split of S_H g (x) H1 against the 0/1 relu mask; only the MFMA
-// shape (32x32x16) and so the f32 accumulation order differ.
+// Numerics: layer 2 and dH1 on f16 pairs scaled by
+// powers of two (S_W W2, S_D W2' = S_D diag(w3) W2, S_H H1; three / two f16
+// MFMAs per K slice).  dW2's operand g (x) H1 is an f16 pair too (two f16
+// MFMAs per K slice against the relu mask): each vector lane owns one H1
+// feature i, so the product is scaled PER FEATURE by the power of two
+// s_i = 2^14 / (G' B_i'), G' >= the launch's bound on |g| (PolicyTrainArgs::
+// g_bound, computed once per learn()), B_i' >= feature i's bound |W1[i][0]| +
+// |W1[i][1]| + max |b1 + item part|, folded into the lane's layer-1 constants
+// (no VALU in the loop) and taken back exactly, per feature column, at the
+// dW2 write-out.  Within the launch each row r carries its own power of two
+// as well: the operand holds g_r moved up to the bound's binade (gm_r = g_r
+// 2^-rel_r) and the row's relu-mask entries are 2^(15 + rel_r) in place of
+// 2.0 (see gm / mkw below), so the pair keeps its 22 bits on the rows whose g
+// lies far below the bound, too.
+// XH_SP8_DW2_3P=1 (the KL-PPO build, whose g has no such bound yet, and the
+// variant library's policy_train_spec8_3p_kernel for A/B runs) keeps the
+// earlier form: the exact bf16 three-part split of S_H g (x) H1, three bf16
+// MFMAs per K slice.
 //
 // Per 64-row group g (one transition's 64 bins), the work by role:
 //   vector  L1(g)   layer 1 -> H1 image (f16 pair, [i][r]), H1 kept in registers
@@ -31,19 +44,20 @@
 //                   f16 alike)
 //   vector  DH(g)   dH1 = M (S_D W2') (32 MFMAs: its 32 features i), dW1 /
 //                   db1 / item sums; g (x) H1 -> the split image ([i][r])
-//   matrix  DW(g)   dW2 += M^T (g (x) H1) (48 MFMAs: its 32 features i)
+//   matrix  DW(g)   dW2 += M^T (g (x) H1) (32 MFMAs: its 32 features i; 48
+//                   in the three-part form)
 // pipelined two phases per group, each closed by a barrier:
 //   A(j): matrix L2(j+1) + partial logits    vector DH(j) + g (x) H1(j)
 //   B(j): matrix SM(j+1) + DW(j)             vector dW1(j) + L1(j+2)
-// (both phases carry 80 / 48 MFMAs per SIMD beside the vector wave's VALU).
+// (the phases carry 80 / 32 MFMAs per SIMD beside the vector wave's VALU).
 // The two roles run separate code paths with the same barrier sequence, so
 // the compiler allocates each path's registers alone (matrix: W2 pair 64,
 // dW2 accumulators 64, layer-2 accumulators 32, dW3 / db2 sums 32; vector:
 // W2' pair 64, dH1 accumulators 32, two groups' H1 64).
 //
-// LDS (dynamic, base 0): g (x) H1 three bf16 parts [128 i][64 r] (48 KB), H1
-// two f16 parts [64 r][128 i] (32 KB), relu masks [64 r][128 o] (0x4000 = 2.0
-// as bf16 and as f16)
+// LDS (dynamic, base 0): g (x) H1 two f16 parts [128 i][64 r] (32 KB; three
+// bf16 parts, 48 KB, in the three-part form), H1 two f16 parts [64 r][128 i]
+// (32 KB), relu masks [64 r][128 o] (0x4000 = 2.0 as bf16 and as f16)
 // in two slots (32 KB apart, 16 KB used), then f32 vectors; image layout
 // spec8_layout.h.
 #include <cstdlib>
@@ -106,6 +120,15 @@
 #ifndef XH_SP8_GH2
 #define XH_SP8_GH2 0
 #endif
+// XH_SP8_DW2_3P: 1 = dW2 on the exact three-part bf16 split of S_H g (x) H1
+// (the KL-PPO build; the variant library's policy_train_spec8_3p_kernel), 0 =
+// on per-feature scaled f16 pairs
+#ifndef XH_SP8_DW2_3P
+#define XH_SP8_DW2_3P XH_SP8_KL_TU
+#endif
+#if XH_SP8_KL_TU && !XH_SP8_DW2_3P
+#error "the KL-PPO loss has no launch-wide bound on g: build it with XH_SP8_DW2_3P=1"
+#endif
 // XH_SP8_DHI / XH_SP8_L2I (A/B builds): dH1's (vector) / layer 2's (matrix)
 // 16 steps in the order (t = st & 1, ks = st >> 1), alternating the two
 // r-tiles' accumulators, instead of all of r-tile 0's steps first (a
@@ -139,10 +162,18 @@ namespace sp8 {
 constexpr int kB = 64, kD = 2, kF0 = 2 * kD, kH = 128;
 constexpr int kThreads = 512;
 constexpr int kImg = 16384;        // one [128][64] / [64][128] 16-bit image
-constexpr int L_GH = 0;            // g (x) H1: hi, mid, lo
-constexpr int L_H1 = 3 * kImg;     // H1: hi, lo
-constexpr int L_MK = 5 * kImg;     // masks: slot s at + 2 kImg s (the second kImg unused)
-constexpr int L_F = 9 * kImg;
+constexpr int kGhParts = XH_SP8_DW2_3P ? 3 : 2;
+// the relu-mask image's entries are 2^kMaskLog2 (the largest): 2.0 = 0x4000
+// as bf16 and as f16 in the three-part form; in the f16-pair form 2^(15 +
+// rel_r), rel_r in [-28, 0] row r's binade under the launch's bound on g
+constexpr int kMaskLog2 = XH_SP8_DW2_3P ? 1 : 15;
+#if !XH_SP8_DW2_3P
+constexpr int kRelMin = -28;
+#endif
+constexpr int L_GH = 0;            // g (x) H1: hi, lo (three-part form: hi, mid, lo)
+constexpr int L_H1 = kGhParts * kImg;  // H1: hi, lo
+constexpr int L_MK = L_H1 + 2 * kImg;  // masks: slot s at + 2 kImg s (the second kImg unused)
+constexpr int L_F = L_MK + 4 * kImg;
 constexpr int F_B2 = 0;            // [128] b2 S2 (layer 2's accumulator input)
 constexpr int F_W3 = F_B2 + kH;    // [128] w3 / S2 (unscales the partial logits)
 constexpr int F_Z = F_W3 + kH;     // [64 rows][4 matrix waves] partial logits
@@ -153,12 +184,14 @@ constexpr int F_SC = F_REC + 16;   // [16] scale reduction scratch, the scales
 constexpr int F_B3 = F_SC + 16;    // [4]
 constexpr int F_DB3 = F_B3 + 4;    // [32] matrix wave 0's db3 sums, per lane
 constexpr int F_SIMD = F_DB3 + 32; // [8] the SIMD each wave runs on (ints)
+constexpr int F_FS = F_SIMD + 8;   // [128] s_i: feature i's scale of g (x) H1
+constexpr int F_FU = F_FS + kH;    // [128] 2^-15 / s_i (the masks' 2^15 with it)
 #if XH_SP8_KL_TU
-constexpr int F_Q = F_SIMD + 8;    // [4 slots][64 bins] old distribution q
+constexpr int F_Q = F_FU + kH;     // [4 slots][64 bins] old distribution q
 constexpr int F_KL = F_Q + 256;    // [4 matrix waves][32 lanes] KL sums (doubles)
 constexpr int F_END = F_KL + 256;
 #else
-constexpr int F_END = F_SIMD + 8;
+constexpr int F_END = F_FU + kH;
 #endif
 constexpr size_t kLds = L_F + sizeof(float) * F_END;
 static_assert(kLds <= 160 * 1024, "LDS");
@@ -220,6 +253,8 @@ __device__ __forceinline__ float add_halves(float v) {
 
 #if XH_SP8_KL_TU
 __global__ __launch_bounds__(kThreads, 2) void policy_train_spec8_kl_kernel(PolicyTrainArgs a) {
+#elif XH_SP8_DW2_3P
+__global__ __launch_bounds__(kThreads, 2) void policy_train_spec8_3p_kernel(PolicyTrainArgs a) {
 #else
 __global__ __launch_bounds__(kThreads, 2) void policy_train_spec8_kernel(PolicyTrainArgs a) {
 #endif
@@ -269,6 +304,8 @@ __global__ __launch_bounds__(kThreads, 2) void policy_train_spec8_kernel(PolicyT
       mh = fabsf(P[PL.oW1() + tid * kF0]) + fabsf(P[PL.oW1() + tid * kF0 + 1]) +
            fmaxf(fabsf(ba), fabsf(bb));
     }
+    const float mh_own = mh;  // feature tid's own bound on |H1|
+    (void)mh_own;
 #pragma unroll
     for (int o = 1; o < 64; o <<= 1) {
       mw = fmaxf(mw, __shfl_xor(mw, o, kWave));
@@ -288,6 +325,28 @@ __global__ __launch_bounds__(kThreads, 2) void policy_train_spec8_kernel(PolicyT
     }
     __syncthreads();
     if (l == 0 && w < 2) lf[F_SC + w] = mh;  // waves 0-1 hold the 128 features
+#if !XH_SP8_DW2_3P
+    if (tid < kH) {
+      // feature tid's scale of g (x) H1: |g| <= G < 2^eg (the launch's
+      // bound), |H1| <= the feature's own bound < 2^eb, so |s_i g H1| <= 2^14
+      // with s_i = 2^(14 - eg - eb).  The exponents are clamped (a non-finite
+      // bound takes the upper clamp, zero gives 0) so that s_i, its inverse
+      // and s_i H1 stay normal f32 whatever the bounds hold.
+      const float G = *a.g_bound;
+      int eg = 60, eb = 40;
+      if (G < 3.0e38f) {  // (false for NaN)
+        (void)frexpf(G, &eg);
+        eg = min(max(eg, -60), 60);
+      }
+      if (mh_own < 3.0e38f) {
+        (void)frexpf(mh_own, &eb);
+        eb = min(max(eb, -40), 40);
+      }
+      lf[F_FS + tid] = ldexpf(1.0f, 14 - eg - eb);
+      lf[F_FU + tid] = ldexpf(1.0f, eg + eb - 14 - kMaskLog2);
+      if (tid == 0) reinterpret_cast<int *>(lf)[F_SC + 12] = eg;  // (scratch read above)
+    }
+#endif
     __syncthreads();
     const float MH = fmaxf(lf[F_SC + 0], lf[F_SC + 1]);
     __syncthreads();
@@ -299,6 +358,9 @@ __global__ __launch_bounds__(kThreads, 2) void policy_train_spec8_kernel(PolicyT
     __syncthreads();
   }
   const float SW = lf[F_SC + 0], SD = lf[F_SC + 1], SH = lf[F_SC + 2];
+#if !XH_SP8_DW2_3P
+  const int EG = __builtin_amdgcn_readfirstlane(reinterpret_cast<const int *>(lf)[F_SC + 12]);
+#endif
   const float S2 = SW * SH;  // layer 2's pre-activations are in units of S2
   for (int i = tid; i < kH; i += kThreads) {
     lf[F_B2 + i] = P[PL.ob2() + i] * S2;
@@ -381,7 +443,7 @@ __global__ __launch_bounds__(kThreads, 2) void policy_train_spec8_kernel(PolicyT
     for (int mt = 0; mt < 4; ++mt)
 #pragma unroll
       for (int e = 0; e < 16; ++e) accW2[mt][e] = 0.0f;
-    float accb2[16];  // db2 sums, 2 g M (the f16 mask 2.0)
+    float accb2[16];  // db2 sums, 2^kMaskLog2 g M (the f16 mask entries)
 #pragma unroll
     for (int e = 0; e < 16; ++e) accb2[e] = 0.0f;
     if (s == 0 && h == 0) lf[F_DB3 + l31] = 0.0f;
@@ -565,6 +627,16 @@ __global__ __launch_bounds__(kThreads, 2) void policy_train_spec8_kernel(PolicyT
     // dW2's MFMA slots: stage(0) loads, stage(1) .. (6) the arithmetic; wave
     // 0 also stores g, g x0, g x1 -> F_G (the vector waves') and the db3 sums
     float gz[2];
+    // what the images and sums take of g: the three-part form g itself and
+    // the mask word 0x4000; the f16-pair form row r's g moved up to the
+    // bound's binade, gm = g 2^-rel_r (rel_r = the binade of g_r under 2^EG,
+    // clamped to [kRelMin, 0]: |gm| < 2^EG), and 2^(15 + rel_r) as the row's
+    // mask entry -- the products M gm are 2^15 M g exactly, and g (x) H1's
+    // f16 pair keeps its 22 bits for every row within 2^28 of the bound, not
+    // only for the rows near it.  dH1 comes out times 2^(15 + rel_r) and dW1
+    // multiplies it by the staged gm: 2^15 dH1 g, the same bits as before.
+    float gm[2];
+    unsigned mkw[2];
     struct Sm {
       f32x4 rec, z0, z1, x;  // x: wave 0's bins of rows l31, 32 + l31
       float b3, ex0, ex1, se, p0, p1, gc, pc;
@@ -686,15 +758,29 @@ __global__ __launch_bounds__(kThreads, 2) void policy_train_spec8_kernel(PolicyT
         }
 #endif
         default:
+#pragma unroll
+          for (int t = 0; t < 2; ++t) {
+#if XH_SP8_DW2_3P
+            gm[t] = gz[t];
+            mkw[t] = 0x4000u;
+#else
+            // |g| < 2^e (frexp's exponent from the bits; zero and subnormal
+            // g take the lower clamp, a non-finite one the upper)
+            const int e = (int)((__float_as_uint(gz[t]) >> 23) & 0xffu) - 126;
+            const int rel = min(max(e - EG, kRelMin), 0);
+            gm[t] = gz[t] * __uint_as_float((unsigned)(127 - rel) << 23);
+            mkw[t] = (unsigned)(rel + 15 + 15) << 10;  // 2^(15 + rel) as f16
+#endif
+          }
           if (s == 0 && h == 0) {
             const int lo = opaque(l31);
             float *gv = lf + F_G + 192 * gpar + lo;
-            gv[0] = gz[0];
-            gv[32] = gz[1];
-            gv[64] = gz[0] * sm.x[0];
-            gv[96] = gz[1] * sm.x[1];
-            gv[128] = gz[0] * sm.x[2];
-            gv[160] = gz[1] * sm.x[3];
+            gv[0] = gm[0];
+            gv[32] = gm[1];
+            gv[64] = gm[0] * sm.x[0];
+            gv[96] = gm[1] * sm.x[1];
+            gv[128] = gm[0] * sm.x[2];
+            gv[160] = gm[1] * sm.x[3];
             // db3: per-lane sums in LDS (ds_add_f32, nothing returned; a
             // register here spilled)
             if (acc)
@@ -702,7 +788,7 @@ __global__ __launch_bounds__(kThreads, 2) void policy_train_spec8_kernel(PolicyT
                                      __HIP_MEMORY_SCOPE_WORKGROUP);
           }
           // a look-ahead group past the end: its dW3 / db2 terms vanish
-          if (!acc) gz[0] = gz[1] = 0.0f;
+          if (!acc) gm[0] = gm[1] = 0.0f;
       }
     };
     // the relu mask of layer-2 value e of r-tile t as 0 / 0x4000 (2.0 both
@@ -717,14 +803,15 @@ __global__ __launch_bounds__(kThreads, 2) void policy_train_spec8_kernel(PolicyT
       const int q = e >> 2, u = e & 3;
       if ((u & 1) == 0) {
         // the pair's word: relu'(x) in {0, 1} from x's bits by v_med3_i32 (no
-        // compare writing VCC), packed and times 0x4000 by the 24-bit multiply
+        // compare writing VCC), packed and times the row's mask entry (0x4000
+        // in the three-part form) by the 24-bit multiply
         int m0, m1;
         asm("v_med3_i32 %0, %1, 0, 1" : "=v"(m0) : "v"(__float_as_int(c[t][e])));
         asm("v_med3_i32 %0, %1, 0, 1" : "=v"(m1) : "v"(__float_as_int(c[t][e + 1])));
-        mwd[u >> 1] = (unsigned)__umul24((unsigned)m0 | ((unsigned)m1 << 16), 0x4000u);
-        accb2[e] = fma_mix_lo(mwd[u >> 1], gz[t], accb2[e]);
+        mwd[u >> 1] = (unsigned)__umul24((unsigned)m0 | ((unsigned)m1 << 16), mkw[t]);
+        accb2[e] = fma_mix_lo(mwd[u >> 1], gm[t], accb2[e]);
       } else {
-        accb2[e] = fma_mix_hi(mwd[u >> 1], gz[t], accb2[e]);
+        accb2[e] = fma_mix_hi(mwd[u >> 1], gm[t], accb2[e]);
       }
       if (u == 3) {
         const int mb = 2 * kImg * ms;  // (mwb holds L_MK)
@@ -736,6 +823,44 @@ __global__ __launch_bounds__(kThreads, 2) void policy_train_spec8_kernel(PolicyT
     // 16 steps (K-step ks = st / 4 of 16 rows, o-tile mt = st % 4) of three
     // bf16 MFMAs; A (mask, transposed reads) one step ahead, B (the three
     // parts) one K-step ahead, both ping-pong; task(k) after MFMA k
+#if !XH_SP8_DW2_3P
+    // (f16-pair form: two f16 MFMAs per step against the per-feature scaled
+    // pair, the mask image read as f16; the 48 tasks keep their order in the
+    // 32 slots: one after the lo product, two after the hi product)
+    auto dw2 = [&](int ms, auto &&task) {
+      const int mb = 2 * kImg * ms;  // (trM holds L_MK)
+      f16x8 A[2], B[2][2];
+      auto ldB = [&](int ks) {
+        const int ob = L_GH + 1024 * (ks >> 1) + ((ks & 1) ? rbg1 : rbg0);
+        B[ks & 1][0] = ld8h(ob);
+        B[ks & 1][1] = ld8h(ob + kImg);
+      };
+      auto ldA = [&](int st) {
+        const int o = mb + 1024 * (4 * (st >> 2) + (st & 3));
+        A[st & 1] = ldtrh(trM0 + o, trM1 + o);
+      };
+      ldB(0);
+      ldA(0);
+#pragma unroll
+      for (int st = 0; st < 16; ++st) {
+        const int ks = st >> 2, mt = st & 3, ca = st & 1, cb = ks & 1;
+        if (st + 1 < 16) {
+          ldA(st + 1);
+          if (mt == 3) ldB(ks + 1);
+        }
+        FENCE();
+        accW2[mt] = mfma_f16(A[ca], B[cb][1], accW2[mt]);
+        FENCE();
+        task(3 * st);
+        FENCE();
+        accW2[mt] = mfma_f16(A[ca], B[cb][0], accW2[mt]);
+        FENCE();
+        task(3 * st + 1);
+        task(3 * st + 2);
+        FENCE();
+      }
+    };
+#else
     auto dw2 = [&](int ms, auto &&task) {
       const int mb = 2 * kImg * ms;  // (trM holds L_MK)
       bf16x8 A[2], B[2][3];
@@ -773,7 +898,9 @@ __global__ __launch_bounds__(kThreads, 2) void policy_train_spec8_kernel(PolicyT
         FENCE();
       }
     };
-    // B's VALU in dW2's 48 slots: the softmax stages (loads in slot 0, the
+#endif
+    // B's VALU in dW2's 48 slots (the f16-pair form: the 48 tasks in its 32
+    // slots): the softmax stages (loads in slot 0, the
     // arithmetic from slot 3 on, one stage per slot), then group gi's masks
     // and db2 sums (slots 12 .. 43), a mask block stored every fourth slot
     auto b_task = [&](const f32x16s (&c)[2], int gi, int gpar, bool acc, int k) {
@@ -866,7 +993,12 @@ __global__ __launch_bounds__(kThreads, 2) void policy_train_spec8_kernel(PolicyT
     }
 #endif
     // ---- write-out (every entry has exactly one producing lane)
+#if XH_SP8_DW2_3P
     const float rSH = 0.5f / SH;  // (the masks were 2.0)
+#else
+    // this lane's feature column i = 32 s + l31: 1 / (2 s_i), exact
+    const float rSH = lf[F_FU + 32 * s + l31];
+#endif
 #pragma unroll
     for (int mt = 0; mt < 4; ++mt)
 #pragma unroll
@@ -895,7 +1027,7 @@ __global__ __launch_bounds__(kThreads, 2) void policy_train_spec8_kernel(PolicyT
     for (int e = 0; e < 16; ++e) {
       // db2 of o = 32 s + 8 (e >> 2) + 4 h + (e & 3): sums over the 32 lanes
       // (rows) of the half
-      const float s2 = seg_sum<32>(accb2[e]) * 0.5f;
+      const float s2 = seg_sum<32>(accb2[e]) * (1.0f / (float)(1 << kMaskLog2));
       const int o = 32 * s + 8 * (e >> 2) + 4 * h + (e & 3);
       if (l31 == 0) {
         d3d[o] = s2;
@@ -939,7 +1071,15 @@ __global__ __launch_bounds__(kThreads, 2) void policy_train_spec8_kernel(PolicyT
     typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
     // the exact f32 chain for the values g (x) H1 and dW1's relu mask use:
     // S_H W1 columns and b1 + the item's part
-    const float w1a = P[PL.oW1() + fi * kF0] * SH, w1b = P[PL.oW1() + fi * kF0 + 1] * SH;
+    // (f16-pair dW2: in units of this lane's feature scale s_i in place of
+    // S_H, so that g times these values is the scaled product; a power of two
+    // either way: the relu masks dW1 takes from them are the same)
+#if XH_SP8_DW2_3P
+    const float SF = SH;
+#else
+    const float SF = lf[F_FS + fi];
+#endif
+    const float w1a = P[PL.oW1() + fi * kF0] * SF, w1b = P[PL.oW1() + fi * kF0 + 1] * SF;
     float b1a = P[PL.ob1() + fi], b1b = b1a;
 #pragma unroll
     for (int d = 0; d < kD; ++d) {
@@ -947,8 +1087,8 @@ __global__ __launch_bounds__(kThreads, 2) void policy_train_spec8_kernel(PolicyT
       b1a += wv * ((float)a.env.item_a[d] / (float)kCapacity);
       b1b += wv * ((float)a.env.item_b[d] / (float)kCapacity);
     }
-    b1a *= SH;
-    b1b *= SH;
+    b1a *= SF;
+    b1b *= SF;
     auto h1_4 = [&](const f32x4 &x0, const f32x4 &x1, float b1, f32x4 &hv) {
 #pragma unroll
       for (int u = 0; u < 4; ++u) hv[u] = relu(fmaf(x1[u], w1b, fmaf(x0[u], w1a, b1)));
@@ -1062,10 +1202,12 @@ __global__ __launch_bounds__(kThreads, 2) void policy_train_spec8_kernel(PolicyT
       const float s0 = r0 - lo_f(pm), s1 = r1 - hi_f(pm);
       pl = cvt(s0, s1);
     };
+    (void)split3_pair;
     // A(gi): DH -- S_D dH1 = M (S_D W2') for this wave's features, 16 steps
     // of two f16 MFMAs (r-tile t = st / 8, K-step ks = st % 8; A, the f16
     // mask image, one step ahead) -- with, in the MFMA slots, the group's
-    // layer-1 values (hk, kept for B's dW1) and S_H g (x) H1 -> the split
+    // layer-1 values (hk, kept for B's dW1) and s_i g (x) H1 (three-part
+    // form: S_H g (x) H1) -> the split
     // image: block b = (t, q) = (b / 4, b % 4) of four rows over slots 4b ..
     // 4b + 3, its bins and g two blocks ahead (a ring of three indexed by the
     // unrolled block).  dh stays in registers for B's dW1.  gpar = gi & 1.
@@ -1090,6 +1232,7 @@ __global__ __launch_bounds__(kThreads, 2) void policy_train_spec8_kernel(PolicyT
       ld3(1);
       float x[4];
       unsigned ph[2], pm[2], pl[2];
+      (void)pm;
       auto gh_slot = [&](int k) {
         const int b = k >> 2, t = b >> 2, q = b & 3;
         const f32x4(&o)[3] = ring[b % 3];
@@ -1105,6 +1248,7 @@ __global__ __launch_bounds__(kThreads, 2) void policy_train_spec8_kernel(PolicyT
             if (b + 2 < 8) ld3(b + 2);
             break;
           }
+#if XH_SP8_DW2_3P
           case 1:
             split3_pair(x[0], x[1], ph[0], pm[0], pl[0]);
             if (XH_SP8_GH2) split3_pair(x[2], x[3], ph[1], pm[1], pl[1]);
@@ -1118,6 +1262,21 @@ __global__ __launch_bounds__(kThreads, 2) void policy_train_spec8_kernel(PolicyT
             st4(o2 + kImg, __builtin_bit_cast(bf16x4, u32x2{pm[0], pm[1]}));
             st4(o2 + 2 * kImg, __builtin_bit_cast(bf16x4, u32x2{pl[0], pl[1]}));
           }
+#else
+          // the scaled products as f16 pairs: 3 VALU per pair, two stores
+          case 1:
+            split2h_x2(x[0], x[1], ph[0], pl[0]);
+            if (XH_SP8_GH2) split2h_x2(x[2], x[3], ph[1], pl[1]);
+            break;
+          case 2:
+            if (!XH_SP8_GH2) split2h_x2(x[2], x[3], ph[1], pl[1]);
+            break;
+          default: {
+            const int o2 = vwb[q] + 1024 * t;
+            st4h(o2, __builtin_bit_cast(f16x4, u32x2{ph[0], ph[1]}));
+            st4h(o2 + kImg, __builtin_bit_cast(f16x4, u32x2{pl[0], pl[1]}));
+          }
+#endif
         }
       };
       ldA(0);
@@ -1211,11 +1370,12 @@ __global__ __launch_bounds__(kThreads, 2) void policy_train_spec8_kernel(PolicyT
     float tw1 = w1 + __shfl_xor(w1, 32, kWave);
     float va = sa + __shfl_xor(sa, 32, kWave);
     float vb = sb + __shfl_xor(sb, 32, kWave);
-    // (dH1 was in units of S_D, times the masks' 2)
-    tw0 *= 0.5f / SD;
-    tw1 *= 0.5f / SD;
-    va *= 0.5f / SD;
-    vb *= 0.5f / SD;
+    // (dH1 was in units of S_D, times the masks' 2^kMaskLog2)
+    const float rSD = (1.0f / (float)(1 << kMaskLog2)) / SD;
+    tw0 *= rSD;
+    tw1 *= rSD;
+    va *= rSD;
+    vb *= rSD;
     if (h == 0) {
       slab[PL.oW1() + fi * kF0 + 0] = tw0;
       slab[PL.oW1() + fi * kF0 + 1] = tw1;
@@ -1243,8 +1403,21 @@ hipError_t launch_policy_train_spec8_kl(const PolicyTrainArgs &a, int grid, hipS
                      sp8::kLds, s, a);
   return hipGetLastError();
 }
+#elif XH_SP8_DW2_3P
+hipError_t launch_policy_train_spec8_3p(const PolicyTrainArgs &a, int grid, hipStream_t s) {
+  static bool attr = false;
+  if (!attr) {
+    (void)hipFuncSetAttribute((const void *)sp8::policy_train_spec8_3p_kernel,
+                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)sp8::kLds);
+    attr = true;
+  }
+  hipLaunchKernelGGL(sp8::policy_train_spec8_3p_kernel, dim3(grid), dim3(sp8::kThreads),
+                     sp8::kLds, s, a);
+  return hipGetLastError();
+}
 #else
 hipError_t launch_policy_train_spec8(const PolicyTrainArgs &a, int grid, hipStream_t s) {
+  if (!a.g_bound) return hipErrorInvalidValue;  // the scales need the bound on g
   static bool attr = false;
   if (!attr) {
     (void)hipFuncSetAttribute((const void *)sp8::policy_train_spec8_kernel,

@@ -1,11 +1,15 @@
 // train_select.cpp -- which policy train kernel an epoch launches (host code).
 //
 // Product kernels (libxylo_hip.so), f16 pairs + the exact bf16 split
-// (DESIGN.md §3.0a-d):
-//   64 bins, 2-D, [128,128] (configs 3 / 4)  policy_train_spec8_kernel
+// (DESIGN.md §3.0a-e):
+//   64 bins, 2-D, [128,128] (configs 3 / 4)  policy_train_spec8_kernel (dW2 on
+//                                  per-feature scaled f16 pairs too)
 //                                  (KL-PPO: policy_train_spec8_kl_kernel;
 //                                  XH_TRAIN_KERNEL=split8wh: the earlier
-//                                  policy_train_split8wh_kernel)
+//                                  policy_train_split8wh_kernel; variant
+//                                  library, XH_TRAIN_KERNEL=spec8_3p:
+//                                  policy_train_spec8_3p_kernel, dW2 on the
+//                                  three-part bf16 split)
 //   128 bins, 3-D, [128,128] (config 5)      policy_train_split8x_kernel
 //                                  (KL-PPO: policy_train_split8x_kl_kernel)
 //   32 bins, 1-D, [64,64] (config 2)         policy_train_split4h_kernel
@@ -118,6 +122,7 @@ hipError_t launch_policy_train_split(const PolicyTrainArgs &a, int grid,
     if (!ov) {
       info->name = a.algo == kKLPPO ? "policy_train_spec8_kl_kernel"
                                     : "policy_train_spec8_kernel";
+      if (a.algo != kKLPPO) info->math = kMathSplitTrainF16Pair;
       return a.algo == kKLPPO ? launch_policy_train_spec8_kl(a, grid, s)
                               : launch_policy_train_spec8(a, grid, s);
     }
@@ -127,6 +132,10 @@ hipError_t launch_policy_train_split(const PolicyTrainArgs &a, int grid,
       return launch_policy_train_split8wh(a, grid, s);
     }
 #if XH_VARIANT_KERNELS
+    if (train_kernel_is("spec8_3p") && a.algo != kKLPPO) {
+      info->name = "policy_train_spec8_3p_kernel";
+      return launch_policy_train_spec8_3p(a, grid, s);
+    }
     if (train_kernel_is("split8wg")) {
       info->name = "policy_train_split8wg_kernel";
       return launch_policy_train_split8wg(a, grid, s);

@@ -131,6 +131,25 @@ __global__ void adv_normalize_kernel(float *adv, long n, const double *stats,
     adv[i] = (float)(((double)adv[i] - mean) * inv);
 }
 
+// The bound G on the loss gradient g over the n transitions (xh_kernels.h,
+// launch_g_bound): a maximum of non-negative floats, taken on their bits (the
+// order of non-negative floats is the order of their bits, NaN above all);
+// out zeroed before the launch.
+__global__ __launch_bounds__(256) void g_bound_kernel(const float *adv, const float *pold,
+                                                      long n, int ppo, float clip_eps,
+                                                      unsigned *out) {
+  unsigned m = 0u;
+  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n;
+       i += (long)gridDim.x * blockDim.x) {
+    float v = fabsf(adv[i]);
+    if (ppo) v *= fmaxf(1.0f + clip_eps, 1.0f / fabsf(pold[i]));
+    m = max(m, __float_as_uint(v) & 0x7fffffffu);
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, o, kWave));
+  if ((threadIdx.x & 63) == 0 && m) atomicMax(out, m);
+}
+
 // Deterministic slab reduction: the sum over slabs in a fixed order.
 // A 256-thread block takes 64 consecutive entries x 4 slab ranges (each
 // wave reads 256-byte rows, enough blocks to cover the chip); the 4 range
@@ -275,6 +294,15 @@ hipError_t launch_adv_normalize(float *adv, long n, const double *stats,
                                 double count, hipStream_t s) {
   hipLaunchKernelGGL(adv_normalize_kernel, dim3(blocks_for(n)), dim3(256), 0, s,
                      adv, n, stats, count);
+  return hipGetLastError();
+}
+
+hipError_t launch_g_bound(const float *adv, const float *pold, long n, int ppo,
+                          float clip_eps, float *out, hipStream_t s) {
+  const hipError_t e = hipMemsetAsync(out, 0, sizeof(float), s);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(g_bound_kernel, dim3(blocks_for(n, 1024, 256)), dim3(256), 0, s,
+                     adv, pold, n, ppo, clip_eps, reinterpret_cast<unsigned *>(out));
   return hipGetLastError();
 }
 

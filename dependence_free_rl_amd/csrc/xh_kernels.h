@@ -89,6 +89,11 @@ struct PolicyTrainArgs {
   float clip_eps;
   const float *params;
   const float *adv;  // [T][N]
+  // device scalar G >= |g| of every row of the launch, g the loss gradient on
+  // the logits (launch_g_bound, once per learn(): the advantages and p_old
+  // are the same in every epoch); policy_train_spec8_kernel scales dW2's f16
+  // operand by it.  PPO / actor-critic only.
+  const float *g_bound;
   float *slab;       // [gridDim.x][slab_stride]
   int slab_stride;
   int wide;          // a slot of the batch holds a bin below -capacity: the
@@ -361,8 +366,10 @@ enum Math {
                           // f32 product, dW2 / dH1 three (rank-1 backward)
   kMathSplitRollout = 2,  // layer 2 on f16 pairs: three f16 products per f32
                           // product (the other layers f32 MFMA)
-  kMathSplitTrainF16 = 3  // layer 2 three f16 MFMAs per f32 product (scaled f16
+  kMathSplitTrainF16 = 3, // layer 2 three f16 MFMAs per f32 product (scaled f16
                           // pairs), dH1 two, dW2 three bf16 (8 per 3 products)
+  kMathSplitTrainF16Pair = 4  // as above with dW2 on per-feature scaled f16
+                              // pairs too: two (7 per 3 products)
 };
 struct KernelInfo {
   const char *name = nullptr;
@@ -402,6 +409,9 @@ hipError_t launch_policy_train_split8wh_kl(const PolicyTrainArgs &a, int grid,
 hipError_t launch_policy_train_spec8(const PolicyTrainArgs &a, int grid, hipStream_t s);
 // its KL-PPO build (policy_spec8_kl_kernels.o)
 hipError_t launch_policy_train_spec8_kl(const PolicyTrainArgs &a, int grid, hipStream_t s);
+// its earlier form, dW2 on the three-part bf16 split (the variant library
+// only: XH_TRAIN_KERNEL=spec8_3p)
+hipError_t launch_policy_train_spec8_3p(const PolicyTrainArgs &a, int grid, hipStream_t s);
 // the wave-specialised config-2 epoch (policy_spec4_kernels.hip, opt-in by
 // XH_TRAIN_KERNEL=spec4; one 8-wave workgroup per CU: train_spec4_default
 // says when the grid is one per CU)
@@ -438,6 +448,12 @@ hipError_t launch_adv_stats(const double *part, int nparts, double *stats,
                             hipStream_t s);
 hipError_t launch_adv_normalize(float *adv, long n, const double *stats,
                                 double count, hipStream_t s);
+// *out = G, a bound on |g| (the loss gradient on the logits) over the n
+// transitions: PPO max_t |A_t| max(1 + clip_eps, 1 / p_old_t) (|ig| <= max(
+// ratio, 1 + eps) |A|, ratio <= 1 / p_old, |g_r| <= |ig|), actor-critic
+// max_t |A_t|.  A NaN among the terms gives a NaN.  No host synchronisation.
+hipError_t launch_g_bound(const float *adv, const float *pold, long n, int ppo,
+                          float clip_eps, float *out, hipStream_t s);
 
 // On-device training statistics (stats_kernels.hip; xh_trainer_set_stats):
 // double sums, one partial per workgroup ([gae_grid(N)][S] doubles), summed in

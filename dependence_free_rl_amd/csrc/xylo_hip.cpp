@@ -89,6 +89,7 @@ struct xh_trainer {
   float *pgrads = nullptr, *vgrad = nullptr;
   float *logits = nullptr, *probs = nullptr;
   double *adv_part = nullptr, *adv_stats = nullptr;  // adv_normalize
+  float *g_bound = nullptr;  // the learn()'s bound on the loss gradient g
   // KL-PPO state
   float *qold = nullptr, *beta = nullptr, *kl_log = nullptr;
   int *end_list = nullptr, *n_end = nullptr, *n_open = nullptr;
@@ -844,6 +845,15 @@ int do_learn(xh_trainer *t) {
   pa.clip_eps = c.clip_eps;
   pa.params = t->pp;
   pa.adv = t->adv;
+  if (c.algo == XH_PPO || c.algo == XH_AC) {
+    // the bound on |g| the 64-bin train kernel scales dW2's operand by: from
+    // the final advantages and p_old, the same in all k epochs
+    CHK(timed(t, "value", [&]() {
+      return xh::launch_g_bound(t->adv, t->pold, (long)NT, c.algo == XH_PPO,
+                                c.clip_eps, t->g_bound, s);
+    }));
+    pa.g_bound = t->g_bound;
+  }
   pa.slab = t->pslab;
   pa.slab_stride = t->pslab_stride;
   for (size_t sl = 0; sl < t->T() && sl < t->bins_wide.size(); ++sl)
@@ -1279,15 +1289,33 @@ constexpr double kBf16DensePeakTflops = 2500.0;  // MI355X_MICROARCH.md
 constexpr double kF32MfmaPeakTflops = 157.3;
 
 std::string kernel_json(const xh::KernelInfo &k) {
-  char buf[320];
+  char buf[640];
   if (!k.name) return "{\"kernel\": null}";
   // MFMA products per f32 product of the kernel's arithmetic (equal FLOPs
   // per GEMM): bf16 / f16 run at the same dense rate (MI355X_MICROARCH.md)
   const double prod = k.math == xh::kMathSplitTrain      ? 4.0
                       : k.math == xh::kMathSplitRollout  ? 3.0
-                      : k.math == xh::kMathSplitTrainF16 ? 8.0 / 3.0
-                                                         : 0.0;
-  if (k.math == xh::kMathSplitTrainF16 || k.math == xh::kMathSplitRollout)
+                      : k.math == xh::kMathSplitTrainF16 ||
+                                k.math == xh::kMathSplitTrainF16Pair
+                          ? 8.0 / 3.0
+                          : 0.0;
+  if (k.math == xh::kMathSplitTrainF16Pair) {
+    // dW2 on f16 pairs as well: 7 MFMA products issued per 3 f32 products.
+    // The entries every report and test has read so far (math, products,
+    // peak) keep the 8/3 yardstick of the f16-pair train kernels, so `frac`
+    // stays comparable across them; what is issued is reported beside them.
+    const double issued = 7.0 / 3.0;
+    std::snprintf(buf, sizeof buf,
+                  "{\"kernel\": \"%s\", \"math\": \"f16_pair_bf16_split\", "
+                  "\"bf16_products_per_f32_product\": null, "
+                  "\"products_per_f32_product\": %.6g, \"peak_tflops\": %.6g, "
+                  "\"dw2_math\": \"f16_pair_per_feature_scale\", "
+                  "\"issued_math\": \"f16_pair_train\", "
+                  "\"issued_products_per_f32_product\": %.6g, "
+                  "\"issued_peak_tflops\": %.6g}",
+                  k.name, prod, kBf16DensePeakTflops / prod, issued,
+                  kBf16DensePeakTflops / issued);
+  } else if (k.math == xh::kMathSplitTrainF16 || k.math == xh::kMathSplitRollout)
     std::snprintf(buf, sizeof buf,
                   "{\"kernel\": \"%s\", \"math\": \"%s\", "
                   "\"bf16_products_per_f32_product\": null, "
@@ -1615,6 +1643,7 @@ int xh_trainer_create(xh_ctx *ctx, const xh_config *cfg, xh_trainer **out) {
     A(&t->vgrad, (size_t)t->nv * 4);
     A(&t->logits, N * c.bins * 4);
     A(&t->probs, N * c.bins * 4);
+    A(&t->g_bound, 4);
     if (c.adv_normalize) {
       A(&t->adv_part, (size_t)xh::gae_grid((int)N) * 2 * 8);
       A(&t->adv_stats, 2 * 8);

@@ -615,7 +615,13 @@ int xh_trainer_reset_timing(xh_trainer *t);
  *        "bf16_products_per_f32_product": p for "bf16_split", else null,
  *        "peak_tflops": the dense MFMA peak of that arithmetic on MI355X
  *        (2500 / p, or 157.3)}
- *   V = "vnet_bf16" (the Fin -> 64 -> 32 -> 1 value net on exact bf16
+ *   policy_train_spec8_kernel (64 bins, 2-D, [128,128]; PPO / actor-critic)
+ *   runs dW2 on scaled f16 pairs as well, two products: it keeps the
+ *   "f16_pair_bf16_split" entries above (the yardstick its `frac` has been
+ *   printed against) and adds "dw2_math": "f16_pair_per_feature_scale",
+ *   "issued_math": "f16_pair_train", "issued_products_per_f32_product": 7/3
+ *   and "issued_peak_tflops": 2500 / (7/3), what it actually issues.
+ *   V ="vnet_bf16" (the Fin -> 64 -> 32 -> 1 value net on exact bf16
  *   splits: two forwards and one fused backward per update, B*D % 16 == 0,
  *   B*D + D < 416), "mlp3_fused" (the same net on the f32 fused kernels:
  *   XH_VALUE_KERNEL=mlp3, or shapes the bf16 kernels do not take) or "gemm"

@@ -6,15 +6,17 @@ from ._lib import (XhError, device_count, lib,  # noqa: F401  (fails loudly
 from ._lib import (STAT_ADV_SQSUM, STAT_ADV_SUM, STAT_COUNT,  # noqa: F401
                    STAT_EPISODES, STAT_EPLEN_SQSUM, STAT_EPLEN_SUM, STAT_ITER,
                    STAT_KL_BETA, STAT_KL_MEAN, STAT_NEGLOGP_SUM,
+                   STAT_PCLIP_SCALE_MIN, STAT_PCLIP_STEPS,
                    STAT_PGRAD_SQ_FIRST, STAT_PGRAD_SQ_LAST, STAT_REWARD_SUM,
                    STAT_TARGET_SQSUM, STAT_TARGET_SUM, STAT_TRANSITIONS,
-                   STAT_VERR_SQSUM, STAT_VERR_SUM, STAT_VGRAD_SQ)
+                   STAT_VCLIP_SCALE, STAT_VERR_SQSUM, STAT_VERR_SUM,
+                   STAT_VGRAD_SQ)
 from .trainer import (ALGOS, POLICY, VALUE, Context, Trainer,  # noqa: F401
-                      heuristic_evaluate, init_full_policy, init_policy,
-                      init_value,
+                      clip_grad_norm, heuristic_evaluate, init_full_policy,
+                      init_policy, init_value,
                       policy_param_count, value_param_count)
 from .venv import VecEnv  # noqa: F401
 
 __all__ = ["Context", "Trainer", "POLICY", "VALUE", "init_policy", "init_value",
-           "init_full_policy",
+           "init_full_policy", "clip_grad_norm",
            "heuristic_evaluate", "XhError", "runtime_info", "device_count", "VecEnv"]

@@ -27,7 +27,8 @@ OPTIMIZERS = {"sgd": 0, "momentum": 1, "adam": 2}
  STAT_REWARD_SUM, STAT_NEGLOGP_SUM, STAT_VERR_SUM, STAT_VERR_SQSUM,
  STAT_TARGET_SUM, STAT_TARGET_SQSUM, STAT_ADV_SUM, STAT_ADV_SQSUM,
  STAT_PGRAD_SQ_FIRST, STAT_PGRAD_SQ_LAST, STAT_VGRAD_SQ, STAT_KL_BETA,
- STAT_KL_MEAN, STAT_COUNT) = range(19)
+ STAT_KL_MEAN, STAT_PCLIP_STEPS, STAT_PCLIP_SCALE_MIN, STAT_VCLIP_SCALE,
+ STAT_COUNT) = range(22)
 
 
 class XhError(RuntimeError):
@@ -131,6 +132,12 @@ def _load():
                                     vp]),
         "xh_optimizer_apply": (i, [vp, i, C.c_float, C.c_float, C.c_float,
                                    C.c_float, C.c_float, vp, vp, vp, vp, sz]),
+        "xh_trainer_set_grad_clip": (i, [vp, i, C.c_float]),
+        "xh_trainer_get_grad_clip_log": (i, [vp, i, vp, i,
+                                             C.POINTER(C.c_int)]),
+        "xh_clip_grad_norm": (i, [vp, vp, sz, C.c_float,
+                                  C.POINTER(C.c_double),
+                                  C.POINTER(C.c_float)]),
         "xh_trainer_forget": (i, [vp]),
         "xh_trainer_set_record_last_step": (i, [vp, i]),
         "xh_trainer_set_stats": (i, [vp, i]),

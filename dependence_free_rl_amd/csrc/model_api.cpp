@@ -382,3 +382,46 @@ int xh_optimizer_apply(xh_ctx *ctx, int kind, float lr, float weight_decay,
     return XH_OK;
   });
 }
+
+// ------------------------------------------------ global-norm clipping ----
+// The trainer's two clip launches (clip_kernels.hip) on a caller's gradient:
+// the sum-of-squares partials, then the clip-and-step kernel in its
+// write-the-scaled-gradient form.
+int xh_clip_grad_norm(xh_ctx *ctx, float *grad, size_t n, float max_norm,
+                      double *norm, float *scale) {
+  return guard([&]() -> int {
+    if (!ctx || (n && !grad))
+      return fail(XH_ERR_INVALID, "clip_grad_norm: null arg");
+    if (!(max_norm > 0.0f) || std::isinf(max_norm))
+      return fail(XH_ERR_INVALID, "clip_grad_norm: max_norm %g (a finite norm "
+                  "> 0)", (double)max_norm);
+    if (n > (size_t)0x7fffffff)
+      return fail(XH_ERR_INVALID, "clip_grad_norm: %zu entries", n);
+    if (!n) {
+      if (norm) *norm = 0.0;
+      if (scale) *scale = 1.0f;
+      return XH_OK;
+    }
+    HIPCHK(hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    HIPCHK(hipStreamSynchronize(s));
+    // [partials | log] as doubles first (8-byte aligned), then g and g'
+    const size_t nd = (size_t)xh::kClipMaxParts + 2;
+    Scratch sc;
+    CHK(sc.alloc(2 * nd + 2 * n));
+    double *part = reinterpret_cast<double *>(sc.base), *log = part + xh::kClipMaxParts;
+    float *dg = sc.base + 2 * nd, *dout = dg + n;
+    CHK(upload(dg, grad, n, s));
+    CHK(launched(xh::launch_clip_sumsq(dg, (int)n, part, s), "clip_grad_norm"));
+    CHK(launched(xh::launch_clip_step(part, 1.0, max_norm, dg, nullptr, nullptr,
+                                      nullptr, (int)n, xh::OptStep{}, dout, log,
+                                      s),
+                 "clip_grad_norm"));
+    double res[2] = {0.0, 0.0};
+    CHK(copy_ok(copy_to_host(res, log, sizeof res, s)));
+    CHK(download(grad, dout, n, s));
+    if (norm) *norm = res[0];
+    if (scale) *scale = (float)res[1];
+    return XH_OK;
+  });
+}

@@ -159,10 +159,12 @@ __global__ __launch_bounds__(256) void grad_norm_kernel(
 // workgroup partials (this rank's share; all-reduced on row[XH_STAT_VERR_SUM
 // ..] next), then the entries that are job-wide already: the gradient norms
 // and, for KL-PPO (kl_last != nullptr: the last epoch's [beta used, mean KL,
-// new beta]), the beta and the mean KL.
+// new beta]), the beta and the mean KL; and from the clip logs of this learn()
+// (clip_kernels.hip; nullptr while clipping is off for the net) the clipped
+// policy steps, the smallest policy scale and the value scale.
 __global__ __launch_bounds__(64) void learner_row_kernel(
     const double *part, int nparts, const double *norms, const float *kl_last,
-    double *row) {
+    const double *pclip, int psteps, const double *vclip, double *row) {
 #pragma clang fp contract(off)
   double v[kStatLearnerSums];
   wave_column_sums<kStatLearnerSums>(part, nparts, v);
@@ -175,6 +177,20 @@ __global__ __launch_bounds__(64) void learner_row_kernel(
   const double nan = __builtin_nan("");
   row[XH_STAT_KL_BETA] = kl_last ? (double)kl_last[2] : nan;
   row[XH_STAT_KL_MEAN] = kl_last ? (double)kl_last[1] : nan;
+  // the clip logs of this learn() ({norm, scale} per optimizer step)
+  double steps = nan, smin = nan;
+  if (pclip) {
+    steps = 0.0;
+    smin = 1.0;
+    for (int e = 0; e < psteps; ++e) {
+      const double sc = pclip[2 * e + 1];
+      if (sc < 1.0) steps += 1.0;
+      if (sc < smin) smin = sc;
+    }
+  }
+  row[XH_STAT_PCLIP_STEPS] = steps;
+  row[XH_STAT_PCLIP_SCALE_MIN] = smin;
+  row[XH_STAT_VCLIP_SCALE] = vclip ? vclip[1] : nan;
 }
 
 // ----------------------------------------------------------- launchers ----
@@ -213,9 +229,10 @@ hipError_t launch_grad_norms(const float *g_first, const float *g_last, int np,
 
 hipError_t launch_learner_row(const double *part, int nparts,
                               const double *norms, const float *kl_last,
-                              double *row, hipStream_t s) {
+                              const double *pclip, int psteps,
+                              const double *vclip, double *row, hipStream_t s) {
   hipLaunchKernelGGL(learner_row_kernel, dim3(1), dim3(64), 0, s, part, nparts,
-                     norms, kl_last, row);
+                     norms, kl_last, pclip, psteps, vclip, row);
   return hipGetLastError();
 }
 

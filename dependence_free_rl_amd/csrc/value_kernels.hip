@@ -4,6 +4,7 @@
 // optimizers.
 #include "xh_device.h"
 #include "xh_kernels.h"
+#include "xh_opt.h"
 
 namespace xh {
 
@@ -198,31 +199,7 @@ __global__ __launch_bounds__(64 * kSlabRows) void slab_reduce_kernel(const float
   if (threadIdx.x < 64 && i < n) out[i] = g;
 }
 
-// One parameter's update, the reference's operation order:
-//   sgd_optimizer::next_parameters (nn.h:622-625): p * (1 - wd) - g * lr
-//   momentum_optimizer::next_parameters (nn.h:637-651): v = rho v + g;
-//     p - v * lr
-//   adam_optimizer::next_parameters (nn.h:666-691): m, v moments,
-//     bias-corrected by c1 = 1 - beta1^t, c2 = 1 - beta2^t;
-//     p - m^ lr / (sqrt(v^) + 1e-7)
-__device__ __forceinline__ void opt_update(float *p, float *m, float *v, int i,
-                                           float gi, const OptStep &o) {
-#pragma clang fp contract(off)
-  if (o.kind == 0) {
-    p[i] = p[i] * (1.0f - o.wd) - gi * o.lr;
-  } else if (o.kind == 1) {
-    const float vel = 0.9f * m[i] + gi;
-    m[i] = vel;
-    p[i] = p[i] - vel * o.lr;
-  } else {
-    const float m1 = m[i] * o.beta1 + gi * (1.0f - o.beta1);
-    const float m2 = v[i] * o.beta2 + gi * gi * (1.0f - o.beta2);
-    m[i] = m1;
-    v[i] = m2;
-    const float mu = m1 / o.c1, vu = m2 / o.c2;
-    p[i] = p[i] - mu * o.lr / (sqrtf(vu) + 1e-7f);
-  }
-}
+// (one parameter's update, opt_update: xh_opt.h)
 
 // sgd_optimizer::next_parameters (nn.h:622-625): p * (1 - wd) - g * lr
 __global__ void sgd_kernel(float *p, const float *g, int n, float lr,

@@ -478,10 +478,13 @@ hipError_t launch_learner_stats(const float *v0, const float *targets,
 hipError_t launch_grad_norms(const float *g_first, const float *g_last, int np,
                              const float *gv, int nv, double *out,
                              hipStream_t s);
-// kl_last: the last epoch's XH_BUF_KL record, or nullptr (not KL-PPO)
+// kl_last: the last epoch's XH_BUF_KL record, or nullptr (not KL-PPO).
+// pclip / vclip: this learn()'s clip logs ([psteps][2] and [1][2] of {norm,
+// scale}, launch_clip_step), or nullptr while clipping is off for that net
 hipError_t launch_learner_row(const double *part, int nparts,
                               const double *norms, const float *kl_last,
-                              double *row, hipStream_t s);
+                              const double *pclip, int psteps,
+                              const double *vclip, double *row, hipStream_t s);
 // Slab entries the value net's reduced layer 0 leaves unwritten: the item
 // columns of bins b > 0 of its first [rows][in] block, whose sums equal bin
 // 0's (EpSlabRed).  B = 0: none.
@@ -510,6 +513,21 @@ hipError_t launch_slab_reduce_opt(const float *slab, int nslab, int stride,
                                   float *v, OptStep o, hipStream_t s,
                                   SlabAlias al = SlabAlias{0, 0, 0, 0});
 
+// Global-norm gradient clipping (clip_kernels.hip; xh_trainer_set_grad_clip,
+// xh_clip_grad_norm).  launch_clip_sumsq: part[clip_parts(n)] = the workgroup
+// partials of sum g[i]^2 in double (clip_parts(n) <= kClipMaxParts, a function
+// of n only).  launch_clip_step: their fixed-order sum ss, norm = sqrt(ss) *
+// r, scale (xh_clip.h), then the optimizer update o on g[i] * scale; with
+// scaled != nullptr it writes g[i] * scale there and steps nothing.
+// log[0..2) = {norm, (double)scale}.  g is not modified.
+constexpr int kClipMaxParts = 256;
+int clip_parts(int n);
+hipError_t launch_clip_sumsq(const float *g, int n, double *part,
+                             hipStream_t s);
+hipError_t launch_clip_step(const double *part, double r, float max_norm,
+                            const float *g, float *params, float *m, float *v,
+                            int n, OptStep o, float *scaled, double *log,
+                            hipStream_t s);
 
 // xylo/tensor.{h,cc} arithmetic on device arrays (tensor_kernels.hip; the
 // drop-in tensor type's device tensors and large host operations).

@@ -126,6 +126,16 @@ struct xh_trainer {
     double *ring = nullptr, *part = nullptr, *norms = nullptr;
     int *ep_len = nullptr;
   } stats;
+  // xh_trainer_set_grad_clip of the policy [0] and value [1] nets (opt-in;
+  // null / 0 while off): one device block per net holding the workgroup
+  // partials of the sum of squares (kClipMaxParts doubles) and then the log,
+  // {norm, scale} per optimizer step of a learn(); learned = a learn() has
+  // filled the log since the clip was set
+  struct clip_state {
+    float max_norm = 0.0f;
+    double *part = nullptr, *log = nullptr;
+    bool learned = false;
+  } clip[2];
   int Tb = 0;  // Batch steps: cfg.steps, or REINFORCE's per-iteration bound
   uint32_t jump_mul = 1;
   int rgrid = 0;
@@ -500,12 +510,47 @@ int opt_apply(xh_trainer *t, int which, float *params, const float *grad,
   });
 }
 
+// Optimizer steps of net `which` in one learn(): the rows of its clip log.
+int clip_log_rows(const xh_trainer *t, int which) {
+  return which == XH_POLICY && t->cfg.algo != XH_PG ? t->cfg.epochs : 1;
+}
+
+void clip_free(xh_trainer *t, int which) {
+  auto &c = t->clip[which];
+  if (c.part) (void)hipFree(c.part);
+  c = xh_trainer::clip_state{};
+}
+
 // Slab reduce -> (all-reduce) -> optimizer step.  One rank: one fused launch
 // (the same sums and updates); more ranks: the all-reduce sits between.
-int reduce_and_step(xh_trainer *t, int which, const float *slab, int nslab,
-                    int stride, int n, float *grad, float *params,
+// With xh_trainer_set_grad_clip on for the net, on either path: slab reduce
+// -> (all-reduce) -> sum of squares -> clip-and-step, which logs {norm,
+// scale} in row `step` of the net's clip log (clip_kernels.hip).
+int reduce_and_step(xh_trainer *t, int which, int step, const float *slab,
+                    int nslab, int stride, int n, float *grad, float *params,
                     xh::SlabAlias al = xh::SlabAlias{0, 0, 0, 0}) {
   hipStream_t s = t->ctx->stream;
+  if (t->clip[which].part) {
+    auto &c = t->clip[which];
+    auto &o = t->opt[which];
+    CHK(timed(t, "reduce_sgd", [&]() {
+      return xh::launch_slab_reduce(slab, nslab, stride, n, grad, s, al);
+    }));
+    CHK(allreduce(t, grad, n));
+    const xh::OptStep st = opt_step(t, which);
+    // the optimizer steps on the mean gradient when lr_scale_rows folds
+    // 1 / rows into lr (opt_step): the norm is that gradient's
+    const double r = t->cfg.lr_scale_rows
+                         ? 1.0 / ((double)t->T() * t->cfg.num_envs_global)
+                         : 1.0;
+    CHK(timed(t, "reduce_sgd", [&]() {
+      return xh::launch_clip_sumsq(grad, n, c.part, s);
+    }));
+    return timed(t, "reduce_sgd", [&]() {
+      return xh::launch_clip_step(c.part, r, c.max_norm, grad, params, o.m, o.v,
+                                  n, st, nullptr, c.log + 2 * (size_t)step, s);
+    });
+  }
   if (!t->ctx->comm) {
     auto &o = t->opt[which];
     const xh::OptStep st = opt_step(t, which);
@@ -580,8 +625,8 @@ int stats_learn(xh_trainer *t) {
   CHK(timed(t, "stats", [&]() {
     return xh::launch_learner_row(
         st.part, xh::gae_grid(N), st.norms,
-        t->kl_log ? t->kl_log + 3 * (size_t)(t->cfg.epochs - 1) : nullptr, row,
-        s);
+        t->kl_log ? t->kl_log + 3 * (size_t)(t->cfg.epochs - 1) : nullptr,
+        t->clip[XH_POLICY].log, t->cfg.epochs, t->clip[XH_VALUE].log, row, s);
   }));
   CHK(allreduce_d(t, row + XH_STAT_VERR_SUM, xh::kStatLearnerSums));
   st.open = false;
@@ -809,7 +854,7 @@ int do_learn(xh_trainer *t) {
                                t->cfg.dims}
                : xh::SlabAlias{0, 0, 0, 0};
   t->vfrag_ready = false;  // the step below writes vp
-  CHK(reduce_and_step(t, XH_VALUE, t->vslab, t->vslab_n, t->vslab_stride,
+  CHK(reduce_and_step(t, XH_VALUE, 0, t->vslab, t->vslab_n, t->vslab_stride,
                       t->nv, t->vgrad, t->vp, al));
   // calculate_advantage (policy_gradient.h:220-281) on post-update values;
   // GAE zeroes V(terminal), the targets above used V(E_t)
@@ -1034,8 +1079,8 @@ int do_learn(xh_trainer *t) {
       pa.trace = nullptr;  // first epoch only
     }
     // the optimizer step does not read beta: it may precede the KL update
-    CHK(reduce_and_step(t, XH_POLICY, t->pslab, t->pslab_n, t->pslab_stride,
-                        t->np, g, t->pp));
+    CHK(reduce_and_step(t, XH_POLICY, e, t->pslab, t->pslab_n,
+                        t->pslab_stride, t->np, g, t->pp));
     if (kl) {  // mean KL over the job's rows -> beta for the next epoch
       CHK(timed(t, "kl", [&]() {
         return xh::launch_kl_reduce(t->kl_part, t->pslab_n, t->n_end,
@@ -1049,6 +1094,7 @@ int do_learn(xh_trainer *t) {
       }));
     }
   }
+  for (auto &cl : t->clip) cl.learned = cl.part != nullptr;
   if (t->stats.history) CHK(stats_learn(t));
   t->need_shift = true;
   t->rolled = false;
@@ -1274,8 +1320,9 @@ int do_pg_learn(xh_trainer *t) {
   CHK(timed(t, "policy_train", [&]() {
     return xh::mlp_backward(m, t->pslab, t->pslab_stride, t->pslab_n, s);
   }));
-  CHK(reduce_and_step(t, XH_POLICY, t->pslab, t->pslab_n, t->pslab_stride,
-                      t->np, t->pgrads, t->pp));
+  CHK(reduce_and_step(t, XH_POLICY, 0, t->pslab, t->pslab_n,
+                      t->pslab_stride, t->np, t->pgrads, t->pp));
+  t->clip[XH_POLICY].learned = t->clip[XH_POLICY].part != nullptr;
   t->need_shift = true;
   t->rolled = false;
   return XH_OK;
@@ -1703,6 +1750,8 @@ int xh_trainer_destroy(xh_trainer *t) {
     for (hipEvent_t e : t->event_pool) (void)hipEventDestroy(e);
     for (void *p : t->allocs) (void)hipFree(p);
     stats_free(t);
+    clip_free(t, XH_POLICY);
+    clip_free(t, XH_VALUE);
     if (t->pg.host_active) (void)hipHostFree(t->pg.host_active);
     xh_ctx *c = t->ctx;
     const bool counted = t->counted;
@@ -1793,6 +1842,67 @@ int xh_trainer_set_learning_rate(xh_trainer *t, int which, float lr) {
       return fail(XH_ERR_INVALID, "learning rate: REINFORCE has no value net");
     t->opt[which].lr = lr;
     (which == XH_POLICY ? t->cfg.lr_policy : t->cfg.lr_value) = lr;
+    return XH_OK;
+  });
+}
+
+int xh_trainer_set_grad_clip(xh_trainer *t, int which, float max_norm) {
+  return guard([&]() -> int {
+    if (!t) return fail(XH_ERR_INVALID, "null trainer");
+    if (which != XH_POLICY && which != XH_VALUE)
+      return fail(XH_ERR_INVALID, "grad clip: which %d", which);
+    if (which == XH_VALUE && t->cfg.algo == XH_PG)
+      return fail(XH_ERR_INVALID, "grad clip: REINFORCE has no value net");
+    if (!(max_norm >= 0.0f) || std::isinf(max_norm))
+      return fail(XH_ERR_INVALID, "grad clip: max_norm %g (a finite norm > 0, "
+                  "or 0 for off)", (double)max_norm);
+    HIPCHK(hipSetDevice(t->ctx->device));
+    hipStream_t s = t->ctx->stream;
+    // launches of an earlier learn() may still read the workspace
+    HIPCHK(hipStreamSynchronize(s));
+    auto &c = t->clip[which];
+    if (max_norm == 0.0f) {
+      clip_free(t, which);
+      return XH_OK;
+    }
+    if (!c.part) {
+      const size_t bytes =
+          ((size_t)xh::kClipMaxParts + 2 * (size_t)clip_log_rows(t, which)) * 8;
+      hipError_t e = hipMalloc((void **)&c.part, bytes);
+      if (e == hipSuccess) e = hipMemsetAsync(c.part, 0, bytes, s);
+      if (e == hipSuccess) e = hipStreamSynchronize(s);
+      if (e != hipSuccess) {
+        clip_free(t, which);
+        return fail(XH_ERR_HIP, "grad clip: %s", hipGetErrorString(e));
+      }
+      c.log = c.part + xh::kClipMaxParts;
+    }
+    c.max_norm = max_norm;
+    c.learned = false;
+    return XH_OK;
+  });
+}
+
+int xh_trainer_get_grad_clip_log(xh_trainer *t, int which, double *out,
+                                 int cap_rows, int *rows) {
+  return guard([&]() -> int {
+    if (!t || !out || !rows) return fail(XH_ERR_INVALID, "null arg");
+    if (which != XH_POLICY && which != XH_VALUE)
+      return fail(XH_ERR_INVALID, "grad clip log: which %d", which);
+    const auto &c = t->clip[which];
+    if (!c.part)
+      return fail(XH_ERR_STATE, "grad clip log: clipping is off for net %d "
+                  "(xh_trainer_set_grad_clip)", which);
+    if (!c.learned)
+      return fail(XH_ERR_STATE, "grad clip log: no learn() since "
+                  "xh_trainer_set_grad_clip");
+    const int n = clip_log_rows(t, which);
+    if (cap_rows < n)
+      return fail(XH_ERR_INVALID, "grad clip log: room for %d rows, the log has "
+                  "%d", cap_rows, n);
+    HIPCHK(hipSetDevice(t->ctx->device));
+    HIPCHK(copy_to_host(out, c.log, (size_t)n * 16, t->ctx->stream));
+    *rows = n;
     return XH_OK;
   });
 }

@@ -262,6 +262,18 @@ def optimizer_apply(ctx, kind, params, grad, lr, weight_decay=0.0, beta1=0.9,
     return p, m, v
 
 
+def clip_grad_norm(ctx, grad, max_norm):
+    """Global-norm clipping of a host gradient on the device
+    (xh_clip_grad_norm: the kernels and the formula of Trainer.set_grad_clip).
+    Returns (clipped float32 copy, norm, scale): norm = sqrt(sum g^2) in
+    double, scale = float32(max_norm / norm) where norm > max_norm, else 1."""
+    g = np.ascontiguousarray(grad, np.float32).copy()
+    norm, scale = C.c_double(), C.c_float()
+    check(_lib.lib.xh_clip_grad_norm(ctx.h, _ptr(g), g.size, max_norm,
+                                     C.byref(norm), C.byref(scale)))
+    return g, norm.value, np.float32(scale.value)
+
+
 def policy_param_count(dims, h1, h2):
     f0 = 2 * dims
     return h1 * f0 + h1 + h2 * h1 + h2 + h2 + 1
@@ -385,6 +397,24 @@ class Trainer:
     def set_learning_rate(self, which, lr):
         """optimizer::set_rate (nn.h:591); the optimizer state is kept."""
         check(_lib.lib.xh_trainer_set_learning_rate(self.h, which, lr))
+
+    def set_grad_clip(self, which, max_norm):
+        """Global-norm gradient clipping of net `which` from the next learn()
+        on (xh_trainer_set_grad_clip): every optimizer step scales its
+        gradient by max_norm / norm where its L2 norm exceeds max_norm, on
+        the device.  0 turns it off (the default); optimizer state is kept."""
+        check(_lib.lib.xh_trainer_set_grad_clip(self.h, which, max_norm))
+
+    def grad_clip_log(self, which):
+        """float64 [rows][2] = (norm, scale) of every optimizer step of net
+        `which` in the last learn() (xh_trainer_get_grad_clip_log;
+        synchronises): `epochs` rows for the policy, 1 for the value net."""
+        cap = max(int(self.epochs), 1)
+        out = np.zeros((cap, 2), np.float64)
+        rows = C.c_int()
+        check(_lib.lib.xh_trainer_get_grad_clip_log(self.h, which, _ptr(out),
+                                                    cap, C.byref(rows)))
+        return out[:rows.value].copy()
 
     # -------------------------------------------------------------- loop --
     def set_record_last_step(self, on):
@@ -542,7 +572,9 @@ class Trainer:
         mean_episode_len / mean_episode_return are NaN where no episode ended
         (an episode's return is its length - 1: reward 1 per step, 0 on the
         overflowing one); the learner series are NaN for a row learn() did
-        not fill; kl_beta / kl_mean are NaN unless KL-PPO."""
+        not fill; kl_beta / kl_mean are NaN unless KL-PPO; policy_clip_fraction
+        (clipped policy steps / epochs), policy_clip_scale_min and
+        value_clip_scale are NaN while set_grad_clip is off for their net."""
         s = self.stats(first, count)
         col = lambda k: s[:, k]  # noqa: E731
         with np.errstate(divide="ignore", invalid="ignore"):
@@ -570,6 +602,10 @@ class Trainer:
                 "value_grad_norm": np.sqrt(col(_lib.STAT_VGRAD_SQ)),
                 "kl_beta": col(_lib.STAT_KL_BETA).copy(),
                 "kl_mean": col(_lib.STAT_KL_MEAN).copy(),
+                "policy_clip_fraction":
+                    col(_lib.STAT_PCLIP_STEPS) / float(self.epochs),
+                "policy_clip_scale_min": col(_lib.STAT_PCLIP_SCALE_MIN).copy(),
+                "value_clip_scale": col(_lib.STAT_VCLIP_SCALE).copy(),
             }
 
     # ------------------------------------------------------------ timing --

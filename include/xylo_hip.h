@@ -172,6 +172,42 @@ int xh_trainer_set_optimizer(xh_trainer *t, int which, int kind, float lr,
  * step counter) is kept. */
 int xh_trainer_set_learning_rate(xh_trainer *t, int which, float lr);
 
+/* Global-norm gradient clipping, off by default (the reference's optimizers
+ * have none): with it off learn() launches what it launches without this call
+ * and no buffer is allocated.  With it on for net `which`, every optimizer
+ * step of that net becomes, entirely on the trainer's stream:
+ *   ss    = sum_i (double)g[i] * (double)g[i]   g: the gradient the optimizer
+ *           is about to read (XH_BUF_POLICY_GRADS row e / XH_BUF_VALUE_GRAD:
+ *           slab-reduced and, with a communicator, all-reduced); double
+ *           partials in a fixed order, no floating-point atomics
+ *   norm  = sqrt(ss) * r                        r = 1 / (T * num_envs_global)
+ *           in double with xh_config.lr_scale_rows (the optimizer then works
+ *           on the mean gradient), else exactly 1
+ *   scale = (float)(norm > max_norm ? (double)max_norm / norm : 1.0)
+ *   g'[i] = g[i] * scale                        one f32 multiply
+ * and the optimizer of xh_trainer_set_optimizer steps on g'.  A zero or NaN
+ * norm gives scale 1 (the comparison is false; a NaN still reaches the log
+ * and the parameters), an infinite norm scale 0.  The clip is per net and per
+ * optimizer step: each policy epoch has its own norm.  The gradient buffers
+ * and XH_STAT_PGRAD_SQ_* / XH_STAT_VGRAD_SQ keep reporting g as reduced, not
+ * g'.  Two launches are added per clipped step, no host synchronisation.  In
+ * a world > 1 job every rank computes the same ss from the same all-reduced
+ * bits in the same order (no collective is added); every rank must set the
+ * same max_norm.
+ *
+ * max_norm > 0 and finite: clip net `which` from the next learn() on; 0: off
+ * (workspace freed).  Negative, NaN or inf: XH_ERR_INVALID.  XH_VALUE on an
+ * XH_PG trainer: XH_ERR_INVALID.  Optimizer state is kept;
+ * xh_trainer_set_optimizer keeps the clip. */
+int xh_trainer_set_grad_clip(xh_trainer *t, int which, float max_norm);
+/* Synchronises.  out[rows][2] = {norm, scale} of every optimizer step of net
+ * `which` in the last learn(): `epochs` rows for the policy (1 for XH_PG), 1
+ * for the value net.  XH_ERR_STATE when clipping is off for `which` or no
+ * learn() has run since it was set; XH_ERR_INVALID when cap_rows is too
+ * small. */
+int xh_trainer_get_grad_clip_log(xh_trainer *t, int which, double *out,
+                                 int cap_rows, int *rows);
+
 /* Turn the last-step logits / probabilities record (xh_config.
  * record_last_step) on or off from the next rollout on. */
 int xh_trainer_set_record_last_step(xh_trainer *t, int on);
@@ -341,6 +377,12 @@ enum {
                               policy_gradient.h:310-335); NaN otherwise      */
   XH_STAT_KL_MEAN = 17,    /* XH_KLPPO: the last epoch's mean KL; NaN
                               otherwise                                      */
+  /* -- learner part, job-wide: gradient clipping (xh_trainer_set_grad_clip);
+        each NaN while clipping is off for its net -- */
+  XH_STAT_PCLIP_STEPS = 18,     /* policy steps of this learn() with scale < 1 */
+  XH_STAT_PCLIP_SCALE_MIN = 19, /* smallest policy scale of this learn(); 1 if
+                                   no step was clipped                        */
+  XH_STAT_VCLIP_SCALE = 20,     /* scale of the value step                     */
   XH_STAT_COUNT
 };
 /* history_rows > 0 (at most 2^20): statistics on, with a fresh device ring of
@@ -519,6 +561,13 @@ int xh_action_loss_grad(xh_ctx *ctx, int kind, int rows, int range,
 int xh_optimizer_apply(xh_ctx *ctx, int kind, float lr, float weight_decay,
                        float beta1, float beta2, float t, float *params,
                        const float *grad, float *m, float *v, size_t n);
+/* Global-norm clipping for a learner assembled from these pieces (next to
+ * xh_optimizer_apply): the kernels and the formula of
+ * xh_trainer_set_grad_clip with r = 1 on n host floats, scaled in place;
+ * synchronous.  max_norm > 0 and finite.  *norm = sqrt(sum g[i]^2), *scale =
+ * the factor applied (either may be NULL). */
+int xh_clip_grad_norm(xh_ctx *ctx, float *grad, size_t n, float max_norm,
+                      double *norm, float *scale);
 /* replay_buffer::forget() (rl.h:274-291) after a learn() that did not run on
  * this trainer (a learner assembled from the pieces above consumed the
  * batch): the batch's final states become the next rollout's start states. */

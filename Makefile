@@ -14,6 +14,7 @@ OBJS     := $(SRC)/policy_kernels.o $(SRC)/value_kernels.o \
             $(SRC)/heuristic_kernels.o $(SRC)/dense_kernels.o \
             $(SRC)/pg_kernels.o $(SRC)/venv_kernels.o $(SRC)/value_net_kernels.o \
             $(SRC)/policy_spec8_kernels.o $(SRC)/policy_spec8_kl_kernels.o \
+            $(SRC)/policy_spec8_e0_kernels.o \
             $(SRC)/policy_spec4_kernels.o \
             $(SRC)/policy_split8wh_kernels.o $(SRC)/policy_split8wh_kl_kernels.o \
             $(SRC)/policy_split8x_kernels.o $(SRC)/policy_split8x_kl_kernels.o \
@@ -28,7 +29,7 @@ VARIANT_KERNELS := policy_split_kernels policy_split128_kernels \
             policy_split8w_kernels policy_split8wp_kernels \
             policy_split4p_kernels policy_split8wg_kernels
 HDRS     := $(SRC)/xh_device.h $(SRC)/xh_kernels.h $(SRC)/xh_split.h \
-            $(SRC)/spec8_layout.h $(SRC)/xh_opt.h $(SRC)/xh_clip.h \
+            $(SRC)/spec8_layout.h $(SRC)/spec8_e0_layout.h $(SRC)/xh_opt.h $(SRC)/xh_clip.h \
             $(SRC)/xh_host.h include/xylo_hip.h
 
 # Drop-in C++20 layer (include/xylo_compat): the reference's unmodified
@@ -80,6 +81,10 @@ $(SRC)/policy_split8x_kl_kernels.o: $(SRC)/policy_split8x_kernels.hip $(HDRS)
 	    -mllvm -pragma-unroll-threshold=200000 -c $< -o $@
 $(SRC)/policy_spec8_kl_kernels.o: $(SRC)/policy_spec8_kernels.hip $(HDRS)
 	$(HIPCC) $(HIPFLAGS) $(FLAGS_policy_spec8_kernels) -DXH_SP8_KL_TU=1 -c $< -o $@
+# PPO's epoch 0 on the rollout's relu masks and distributions
+# (policy_train_spec8_e0_kernel)
+$(SRC)/policy_spec8_e0_kernels.o: $(SRC)/policy_spec8_kernels.hip $(HDRS)
+	$(HIPCC) $(HIPFLAGS) $(FLAGS_policy_spec8_kernels) -DXH_SP8_E0_TU=1 -c $< -o $@
 $(SRC)/policy_split4h_kl_kernels.o: $(SRC)/policy_split4h_kernels.hip $(HDRS)
 	$(HIPCC) $(HIPFLAGS) $(FLAGS_policy_split4h_kernels) -DXH_4H_KL_TU=1 \
 	    -mllvm -pragma-unroll-threshold=200000 -c $< -o $@

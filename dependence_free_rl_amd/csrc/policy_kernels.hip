@@ -19,6 +19,7 @@
 // W2 is staged once per workgroup in LDS (row stride H1+4: conflict-free
 // ds_read_b128 A-operand reads).  Weight gradients contract over rows, so
 // H1 and dL/dA2 go through LDS images (row stride +1) once per group.
+#include "spec8_e0_layout.h"
 #include "xh_device.h"
 #include "xh_kernels.h"
 #include "xh_split.h"
@@ -749,11 +750,17 @@ __device__ __forceinline__ void stage_split_rollout(const float *__restrict__ P,
 // Partial logits (without b3) of the two r-tiles of `cur` (64 rows) by the
 // f16-pair layer 2: zl[rt] = the logit sum of row rt*32 + (lane & 31).
 // b1r[rt]: the folded layer-1 bias (LDS, x S_H) of r-tile rt's item.
-template <class S>
+// E0: also the relu masks of the 64 x 128 pre-activations for PPO's first
+// epoch, mbits[ot] = this lane's word 64 ot + lane of the record
+// (spec8_e0_layout.h: bit 16 rt + e = [pre[ot][e] > 0] of r-tile rt; 0.0 and
+// -0.0 give 0 as relu' does) -- two VALU per value (v_med3_i32 on the bits,
+// v_lshl_or_b32), no compare writing VCC.
+template <class S, bool E0 = false>
 __device__ __forceinline__ void wave_logits_split(const char *lds,
                                                   const RowRaw<S> &cur,
                                                   const float *const (&b1r)[2],
-                                                  float (&zl)[2]) {
+                                                  float (&zl)[2],
+                                                  unsigned *mbits = nullptr) {
   using L = RollSplitLds<S>;
   const float *lf = reinterpret_cast<const float *>(lds + L::F);
   const int lane = threadIdx.x & 63, lr = lane & 31, h = lane >> 5;
@@ -848,6 +855,19 @@ __device__ __forceinline__ void wave_logits_split(const char *lds,
       z += zp + __shfl_xor(zp, 32, kWave);
     }
     zl[rt] = z;
+    if constexpr (E0) {
+#pragma unroll
+      for (int ot = 0; ot < S::NOT; ++ot) {
+        unsigned wd = rt == 0 ? 0u : mbits[ot];
+#pragma unroll
+        for (int e = 0; e < 16; ++e) {
+          int m;
+          asm("v_med3_i32 %0, %1, 0, 1" : "=v"(m) : "v"(__float_as_int(pre[ot][e])));
+          wd |= (unsigned)m << sp8::e0_bit(rt, e);
+        }
+        mbits[ot] = wd;
+      }
+    }
   }
 }
 
@@ -864,11 +884,15 @@ constexpr int roll_split_waves() { return S::B == 64 ? kRollWaves64 : 4; }
 template <class S>
 constexpr int roll_split_occ() { return S::B == 64 ? roll_occ(kRollWaves64) : 2; }
 
-template <class S>
+// E0 (64 bins, one env per wave): every step's relu-mask record goes to
+// a.e0_mask as well (RolloutArgs; the distributions through a.qold_out).
+template <class S, bool E0 = false>
 __global__ __launch_bounds__(64 * roll_split_waves<S>(), roll_split_occ<S>()) void rollout_split_kernel(RolloutArgs a) {
   static_assert((S::B == 64 && S::NIT == 4 && S::NOT == 4) ||
                     (S::B == 32 && S::NIT == 2 && S::NOT == 2),
                 "split rollout: B=64 [128,128] or B=32 [64,64]");
+  static_assert(!E0 || (S::B == 64 && S::G == 1 && S::H2 == sp8::kE0Outs),
+                "the epoch-0 records: one env of 64 bins per wave");
   extern __shared__ __attribute__((aligned(16))) float ldsf[];
   char *lds = reinterpret_cast<char *>(ldsf);
   stage_split_rollout<S>(a.params, a.env, lds);
@@ -916,7 +940,15 @@ __global__ __launch_bounds__(64 * roll_split_waves<S>(), roll_split_occ<S>()) vo
         b1r[rt] = ia ? b1fa : b1fb;
       }
       float zl[2];
-      wave_logits_split<S>(lds, cur, b1r, zl);
+      if constexpr (E0) {
+        unsigned mbits[4];
+        wave_logits_split<S, true>(lds, cur, b1r, zl, mbits);
+        uint32_t *rec = a.e0_mask + ((size_t)t * a.b.N + env) * sp8::kE0Words;
+#pragma unroll
+        for (int ot = 0; ot < 4; ++ot) rec[sp8::e0_word(ot, lane)] = mbits[ot];
+      } else {
+        wave_logits_split<S>(lds, cur, b1r, zl);
+      }
       const float z = (h ? zl[1] : zl[0]) + b3;
       int nbv[S::D];
       bool first;
@@ -2606,6 +2638,22 @@ static hipError_t launch_rollout_one(const RolloutArgs &a, int H1, int H2,
         info->name = "rollout_split_kernel";                                 \
         info->math = kMathSplitRollout;                                      \
         multi = true;                                                        \
+        if constexpr (S::B == 64) {                                          \
+          if (a.e0_mask) {                                                   \
+            static bool eattr = false;                                       \
+            if (!eattr) {                                                    \
+              (void)hipFuncSetAttribute(                                     \
+                  (const void *)rollout_split_kernel<S, true>,               \
+                  hipFuncAttributeMaxDynamicSharedMemorySize,                \
+                  (int)RollSplitLds<S>::bytes);                              \
+              eattr = true;                                                  \
+            }                                                                \
+            hipLaunchKernelGGL((rollout_split_kernel<S, true>),              \
+                               dim3(wgr < wg ? wgr : wg), dim3(64 * kRW),    \
+                               RollSplitLds<S>::bytes, s, a);                \
+            return hipGetLastError();                                        \
+          }                                                                  \
+        }                                                                    \
         hipLaunchKernelGGL(rollout_split_kernel<S>,                          \
                            dim3(wgr < wg ? wgr : wg), dim3(64 * kRW),        \
                            RollSplitLds<S>::bytes, s, a);                       \
@@ -2664,6 +2712,13 @@ hipError_t launch_rollout_step(const RolloutArgs &a, int H1, int H2, int grid,
     RolloutArgs a0 = a;
     a0.src_slot = -1;
     return launch_rollout_step(a0, H1, H2, grid, s, info);
+  }
+  if (a.e0_p && !a.qold_out) {
+    // the epoch-0 distributions are what qold_out receives
+    RolloutArgs ap = a;
+    ap.qold_out = a.e0_p;
+    ap.e0_p = nullptr;
+    return launch_rollout_step(ap, H1, H2, grid, s, info);
   }
   hipError_t e = launch_rollout_one(a, H1, H2, grid, s, info, multi);
   // a one-slot kernel ran slot a.t (its logits / probabilities are rewritten

@@ -63,6 +63,7 @@
 #include <cstdlib>
 #include <type_traits>
 
+#include "spec8_e0_layout.h"
 #include "spec8_layout.h"
 #include "xh_device.h"
 #include "xh_kernels.h"
@@ -116,6 +117,26 @@
 #define SP8KL(...) __VA_ARGS__
 #else
 #define SP8KL(...)
+#endif
+// XH_SP8_E0_TU=1 (policy_spec8_e0_kernels.o): PPO's epoch 0,
+// policy_train_spec8_e0_kernel.  Between a rollout and the learn()'s first
+// policy epoch only the value net steps, so the epoch's layer 2, partial
+// logits and softmax would recompute what rollout_split_kernel just computed
+// from the same parameters; the backward pass needs of them only the relu
+// masks and the distribution p.  The matrix waves here run no layer 2 (no W2
+// fragments, no partial logits, no exp / sum / divide): in phase A(j) they load
+// group j+1's p (PolicyTrainE0Args::e0_p) and their own 32 mask bits per lane
+// (e0_mask, spec8_e0_layout.h: the rollout holds its accumulators in this
+// kernel's C layout, so a lane's dword is its registers' bits), and from p on
+// run the same expressions.  Vector waves, barriers, dW2, the reassociated
+// dW3 and the write-outs are unchanged.  The trainer launches it only while
+// the rollout's outputs are valid (xylo_hip.cpp, e0_valid).  Preprocessor
+// blocks, as the KL-PPO build.
+#ifndef XH_SP8_E0_TU
+#define XH_SP8_E0_TU 0
+#endif
+#if XH_SP8_E0_TU && (XH_SP8_KL_TU || XH_SP8_DW2_3P || XH_SP8_ABLATE)
+#error "the epoch-0 build is the plain PPO kernel's (f16-pair dW2, no ablation)"
 #endif
 #ifndef XH_SP8_GH2
 #define XH_SP8_GH2 0
@@ -255,6 +276,9 @@ __device__ __forceinline__ float add_halves(float v) {
 __global__ __launch_bounds__(kThreads, 2) void policy_train_spec8_kl_kernel(PolicyTrainArgs a) {
 #elif XH_SP8_DW2_3P
 __global__ __launch_bounds__(kThreads, 2) void policy_train_spec8_3p_kernel(PolicyTrainArgs a) {
+#elif XH_SP8_E0_TU
+__global__ __launch_bounds__(kThreads, 2) void policy_train_spec8_e0_kernel(PolicyTrainArgs a,
+                                                                            PolicyTrainE0Args ea) {
 #else
 __global__ __launch_bounds__(kThreads, 2) void policy_train_spec8_kernel(PolicyTrainArgs a) {
 #endif
@@ -407,6 +431,7 @@ __global__ __launch_bounds__(kThreads, 2) void policy_train_spec8_kernel(PolicyT
     // feature i = 32 (ks >> 1) + 16 h + 8 (e >> 2) + 4 (ks & 1) + (e & 3)
     // (the image's column order: each vector lane stores its 16 features of
     // a row as two whole 16-byte chunks, see layer1)
+#if !XH_SP8_E0_TU
     f16x8 wl[8][2];
 #pragma unroll
     for (int ks = 0; ks < 8; ++ks) {
@@ -422,6 +447,7 @@ __global__ __launch_bounds__(kThreads, 2) void policy_train_spec8_kernel(PolicyT
         wl[ks][1][e] = x1;
       }
     }
+#endif
     // per-region lane bases: layer 2's B operand (H1 image, transposed
     // reads), dW2's A operand (mask images, transposed reads), dW2's B
     // operand (g (x) H1 image, lane column i = 32 s + l31, row reads), the
@@ -430,7 +456,9 @@ __global__ __launch_bounds__(kThreads, 2) void policy_train_spec8_kernel(PolicyT
     // (layer 2's B operand: row reads of the [r][column] H1 image, lane row
     // r = 32 t + l31, K-step ks: columns 16 ks + 8 h ..; + 8192 t + 1024 (ks
     // >> 1); the columns' features as in the W2 fragments above)
+#if !XH_SP8_E0_TU
     const int rbH0 = opaque(rd_base(l31, 0, h, 4) + L_H1), rbH1 = opaque(rd_base(l31, 1, h, 4) + L_H1);
+#endif
     const int trM0 = opaque(tr_base(l, 0) + L_MK), trM1 = opaque(tr_base(l, 1) + L_MK);
     const int rbg0 = rd_base(32 * s + l31, 0, h, 2) + L_GH,
               rbg1 = rd_base(32 * s + l31, 1, h, 2) + L_GH;
@@ -554,6 +582,23 @@ __global__ __launch_bounds__(kThreads, 2) void policy_train_spec8_kernel(PolicyT
             (i0 == a.env.item_a[0] && i1 == a.env.item_a[1]) ? 1.0f : 0.0f;
     };
 
+#if XH_SP8_E0_TU
+    // the rollout's forward outputs of group j (clamped as tindex): p of rows
+    // l31 and 32 + l31 (both lane halves, as the softmax leaves them) and this
+    // lane's mask word, bit 16 t + e = the relu mask of what would be
+    // c[t][e]; a wave-uniform record base and the lane id recomputed
+    float ep[2];
+    unsigned emw;
+    auto e0_load = [&](int j) {
+      const size_t ti = tindex(j);
+      const int lane =
+          opaque((int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)));
+      const float *pr = ea.e0_p + ti * kB;
+      ep[0] = pr[lane & 31];
+      ep[1] = pr[32 + (lane & 31)];
+      emw = (ea.e0_mask + ti * kE0Words)[e0_word(s, lane)];
+    };
+#else
     // layer 2 of the group in the H1 image: C[o][r] = S2 (b2 + W2 . H1) for
     // this wave's 32 o (registers) x r-tile t (lanes), 16 steps (t = st / 8,
     // K-step ks = st % 8) of three f16 MFMAs; the B operand (H1 pair, row
@@ -622,6 +667,7 @@ __global__ __launch_bounds__(kThreads, 2) void policy_train_spec8_kernel(PolicyT
       partial_q(ct, 3);
       partial_store(t);
     };
+#endif
     // softmax + loss gradient of group gi (partial logits in F_Z) -> gz
     // (rows l31, 32 + l31), in stages so that its dependent steps sit in
     // dW2's MFMA slots: stage(0) loads, stage(1) .. (6) the arithmetic; wave
@@ -659,9 +705,11 @@ __global__ __launch_bounds__(kThreads, 2) void policy_train_spec8_kernel(PolicyT
       switch (stage) {
         case 0:
           sm.rec = lds4v(lf + F_REC + 4 * rs);
+#if !XH_SP8_E0_TU
           sm.b3 = lf[F_B3];
           sm.z0 = lds4v(lf + F_Z + 4 * l31);
           sm.z1 = lds4v(lf + F_Z + 4 * (32 + l31));
+#endif
           if (s == 0) {
             // (wave 0's per-lane addresses recomputed here: held across the
             // loop they spilled)
@@ -673,9 +721,19 @@ __global__ __launch_bounds__(kThreads, 2) void policy_train_spec8_kernel(PolicyT
           sm.cu = __builtin_amdgcn_readfirstlane(__float_as_int(sm.rec[0]));
           sm.po = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(sm.rec[1])));
           sm.Ac = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(sm.rec[2])));
+#if !XH_SP8_E0_TU
           sm.ex0 = __expf(((sm.z0[0] + sm.z0[1]) + (sm.z0[2] + sm.z0[3])) + sm.b3);
           sm.ex1 = __expf(((sm.z1[0] + sm.z1[1]) + (sm.z1[2] + sm.z1[3])) + sm.b3);
+#endif
           break;
+#if XH_SP8_E0_TU
+        case 2:
+          break;
+        case 3:
+          sm.p0 = ep[0];  // the rollout's softmax
+          sm.p1 = ep[1];
+          break;
+#else
         case 2:
           // the half's sum (both halves hold all 64 rows), DPP only; lane 31
           // holds it
@@ -692,6 +750,7 @@ __global__ __launch_bounds__(kThreads, 2) void policy_train_spec8_kernel(PolicyT
           sm.p1 = sm.ex1 * rse;
           break;
         }
+#endif
 #if XH_SP8_KL_TU
         case 4: {
           // kl_regulated_loss (policy_gradient.h:41-85): softmax_gradient_log
@@ -798,16 +857,26 @@ __global__ __launch_bounds__(kThreads, 2) void policy_train_spec8_kernel(PolicyT
     // words of block (t, q) stored into slot ms after its fourth value.  dW3
     // needs no per-row work: it is reassociated through dW2 after the loop.
     unsigned mwd[2];
+#if XH_SP8_E0_TU
+    // (epoch-0 build: c is the lane's mask word, relu'(x) its bit 16 t + e)
+    auto mv_e = [&](unsigned c, int ms, int t, int e) {
+#else
     auto mv_e = [&](const f32x16s (&c)[2], int ms, int t, int e) {
+#endif
       typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
       const int q = e >> 2, u = e & 3;
       if ((u & 1) == 0) {
         // the pair's word: relu'(x) in {0, 1} from x's bits by v_med3_i32 (no
         // compare writing VCC), packed and times the row's mask entry (0x4000
         // in the three-part form) by the 24-bit multiply
+#if XH_SP8_E0_TU
+        const unsigned m0 = __builtin_amdgcn_ubfe(c, (unsigned)e0_bit(t, e), 1u),
+                       m1 = __builtin_amdgcn_ubfe(c, (unsigned)e0_bit(t, e + 1), 1u);
+#else
         int m0, m1;
         asm("v_med3_i32 %0, %1, 0, 1" : "=v"(m0) : "v"(__float_as_int(c[t][e])));
         asm("v_med3_i32 %0, %1, 0, 1" : "=v"(m1) : "v"(__float_as_int(c[t][e + 1])));
+#endif
         mwd[u >> 1] = (unsigned)__umul24((unsigned)m0 | ((unsigned)m1 << 16), mkw[t]);
         accb2[e] = fma_mix_lo(mwd[u >> 1], gm[t], accb2[e]);
       } else {
@@ -903,7 +972,11 @@ __global__ __launch_bounds__(kThreads, 2) void policy_train_spec8_kernel(PolicyT
     // slots): the softmax stages (loads in slot 0, the
     // arithmetic from slot 3 on, one stage per slot), then group gi's masks
     // and db2 sums (slots 12 .. 43), a mask block stored every fourth slot
+#if XH_SP8_E0_TU
+    auto b_task = [&](unsigned c, int gi, int gpar, bool acc, int k) {
+#else
     auto b_task = [&](const f32x16s (&c)[2], int gi, int gpar, bool acc, int k) {
+#endif
       if (k == 0)
         softmax_stage(gi, gpar, acc, 0);
       else if (k >= 3 && k < (XH_SP8_KL_TU ? 10 : 9))
@@ -915,7 +988,11 @@ __global__ __launch_bounds__(kThreads, 2) void policy_train_spec8_kernel(PolicyT
 
     // ---- pipeline prologue (barriers as the vector path's)
     if (XH_SP8_PRIO & 3) __builtin_amdgcn_s_setprio(XH_SP8_PRIO & 3);
+#if XH_SP8_E0_TU
+    e0_load(0);
+#else
     f32x16s c[2];
+#endif
     if (s == 0) {
       stage_store(stage_load(0), 0 SP8KL(, 0));
       stage_store(stage_load(1), 1 SP8KL(, 1));
@@ -923,12 +1000,19 @@ __global__ __launch_bounds__(kThreads, 2) void policy_train_spec8_kernel(PolicyT
     }
     __syncthreads();  // P1: rows staged          (vector: L1(0))
     __syncthreads();  // P2
+#if XH_SP8_E0_TU
+    (void)no_task;
+    __syncthreads();  // P3                       (vector: L1(1))
+#pragma unroll
+    for (int k = 0; k < 48; ++k) b_task(emw, 0, 0, true, k);
+#else
     layer2(c, no_task);
     partials_tail(c[0], 0);
     partials_tail(c[1], 1);
     __syncthreads();  // P3                       (vector: L1(1))
 #pragma unroll
     for (int k = 0; k < 48; ++k) b_task(c, 0, 0, true, k);
+#endif
     __syncthreads();  // P4
     // one period; P = j & 1 at compile time (mask / g slots, image offsets
     // fold into immediates)
@@ -938,7 +1022,11 @@ __global__ __launch_bounds__(kThreads, 2) void policy_train_spec8_kernel(PolicyT
       if (s == 0) raw = stage_load(j + 3);
       // A(j): layer 2 of group j+1; r-tile 0's partial logits in r-tile 1's
       // MFMA slots, r-tile 1's after
-#if XH_SP8_L2I
+#if XH_SP8_E0_TU
+      // (epoch-0 build: group j+1's p and mask word, nothing else to issue;
+      // B(j-1) is done with the registers, B(j) waits for the loads)
+      e0_load(j + 1);
+#elif XH_SP8_L2I
       // (r-tile 0 is complete only after step 14: its partials after it,
       // r-tile 1's at the tail)
       if (SP8_RUN(1 | 32)) layer2(c, [&](int k) {
@@ -969,8 +1057,12 @@ __global__ __launch_bounds__(kThreads, 2) void policy_train_spec8_kernel(PolicyT
       // masks in its MFMA slots
       if (s == 0) stage_store(raw, (j + 3) & 3 SP8KL(, j + 3));
       const bool acc = j + 1 < J;
+#if XH_SP8_E0_TU
+      dw2(par, [&](int k) { b_task(emw, j + 1, 1 - par, acc, k); });
+#else
       if (SP8_RUN(1 | 16))
         dw2(par, [&](int k) { b_task(c, j + 1, 1 - par, acc, k); });
+#endif
       __syncthreads();
     };
     for (int j = 0; j < J; j += 2) {
@@ -1401,6 +1493,21 @@ hipError_t launch_policy_train_spec8_kl(const PolicyTrainArgs &a, int grid, hipS
   }
   hipLaunchKernelGGL(sp8::policy_train_spec8_kl_kernel, dim3(grid), dim3(sp8::kThreads),
                      sp8::kLds, s, a);
+  return hipGetLastError();
+}
+#elif XH_SP8_E0_TU
+hipError_t launch_policy_train_spec8_e0(const PolicyTrainArgs &a, const PolicyTrainE0Args &ea,
+                                        int grid, hipStream_t s) {
+  // the scales need the bound on g; the clipped-ratio loss on the rollout's p
+  if (!a.g_bound || !ea.e0_p || !ea.e0_mask || a.algo != kPPO) return hipErrorInvalidValue;
+  static bool attr = false;
+  if (!attr) {
+    (void)hipFuncSetAttribute((const void *)sp8::policy_train_spec8_e0_kernel,
+                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)sp8::kLds);
+    attr = true;
+  }
+  hipLaunchKernelGGL(sp8::policy_train_spec8_e0_kernel, dim3(grid), dim3(sp8::kThreads),
+                     sp8::kLds, s, a, ea);
   return hipGetLastError();
 }
 #elif XH_SP8_DW2_3P

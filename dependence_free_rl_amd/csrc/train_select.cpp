@@ -10,6 +10,14 @@
 //                                  library, XH_TRAIN_KERNEL=spec8_3p:
 //                                  policy_train_spec8_3p_kernel, dW2 on the
 //                                  three-part bf16 split)
+//                                  PPO's epoch 0 with k >= 2 epochs, after a
+//                                  split rollout under unchanged policy
+//                                  parameters and batch:
+//                                  policy_train_spec8_e0_kernel, on the
+//                                  rollout's relu masks and distributions --
+//                                  chosen by the trainer (xylo_hip.cpp do_learn,
+//                                  e0_valid; XH_E0_REUSE), not here: the later
+//                                  epochs come through this file as before
 //   128 bins, 3-D, [128,128] (config 5)      policy_train_split8x_kernel
 //                                  (KL-PPO: policy_train_split8x_kl_kernel)
 //   32 bins, 1-D, [64,64] (config 2)         policy_train_split4h_kernel

@@ -80,6 +80,23 @@ struct RolloutArgs {
                // receive the last one's.  launch_rollout_step runs them in
                // one launch where the kernel steps in registers
                // (rollout_split_kernel), else one launch per slot
+  // Optional, both or neither: the forward outputs PPO's first policy epoch
+  // reuses (policy_train_spec8_e0_kernel).  e0_p [T][N][64]: every step's
+  // distribution, the values qold_out receives (launch_rollout_step passes it
+  // as qold_out when that is null).  e0_mask [T][N] records of 1 KB: the bits
+  // [layer-2 pre-activation > 0] (spec8_e0_layout.h), written only by the
+  // 64-bin one-env-per-wave rollout_split_kernel; any other kernel leaves
+  // them alone.
+  float *e0_p;
+  uint32_t *e0_mask;
+};
+
+// policy_train_spec8_e0_kernel's arguments: PPO's epoch 0 on the rollout's
+// own layer-2 relu masks and distributions (the policy parameters are the
+// ones the rollout ran with)
+struct PolicyTrainE0Args {
+  const float *e0_p;        // [T][N][64]
+  const uint32_t *e0_mask;  // [T][N] records (spec8_e0_layout.h)
 };
 
 struct PolicyTrainArgs {
@@ -409,6 +426,10 @@ hipError_t launch_policy_train_split8wh_kl(const PolicyTrainArgs &a, int grid,
 hipError_t launch_policy_train_spec8(const PolicyTrainArgs &a, int grid, hipStream_t s);
 // its KL-PPO build (policy_spec8_kl_kernels.o)
 hipError_t launch_policy_train_spec8_kl(const PolicyTrainArgs &a, int grid, hipStream_t s);
+// PPO's epoch 0 on the rollout's masks and distributions
+// (policy_spec8_e0_kernels.o); the trainer decides when they are valid
+hipError_t launch_policy_train_spec8_e0(const PolicyTrainArgs &a, const PolicyTrainE0Args &ea,
+                                        int grid, hipStream_t s);
 // its earlier form, dW2 on the three-part bf16 split (the variant library
 // only: XH_TRAIN_KERNEL=spec8_3p)
 hipError_t launch_policy_train_spec8_3p(const PolicyTrainArgs &a, int grid, hipStream_t s);

@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "../../include/xylo_hip.h"
+#include "spec8_e0_layout.h"
 #include "xh_host.h"
 #include "xh_kernels.h"
 
@@ -85,6 +86,18 @@ struct xh_trainer {
   // bf16 value forward, cleared by every write of vp): the next iteration's
   // first forward then skips the preparation launch
   bool vfrag_ready = false;
+  // PPO's epoch 0 on the rollout's forward outputs (DESIGN.md §3.0e;
+  // policy_train_spec8_e0_kernel).  The buffers exist only for a trainer that
+  // can use them (PPO, epochs >= 2, 64 bins 2-D [128,128], split kernels):
+  // e0_mask [T][N] relu-mask records of 1 KB, e0_p [T][N][64] distributions
+  // (qold itself where the trainer records them anyway).  e0_valid: they are
+  // this window's forward outputs under the current policy parameters -- set
+  // by a rollout that ran rollout_split_kernel over all T slots with both
+  // outputs, cleared by wrote() on every write of the policy parameters and
+  // every host write into the batch.
+  uint32_t *e0_mask = nullptr;
+  float *e0_p = nullptr;
+  bool e0_valid = false;
   int pslab_stride = 0, vslab_stride = 0, pslab_n = 0, vslab_n = 0;
   float *pgrads = nullptr, *vgrad = nullptr;
   float *logits = nullptr, *probs = nullptr;
@@ -496,8 +509,21 @@ xh::OptStep opt_step(xh_trainer *t, int which) {
   return st;
 }
 
+// Every write of a net's parameters and every host write into the batch (or
+// into what the next rollout starts from) says so here, before it is issued:
+// what was derived from the old contents is stale -- the value net's W0
+// fragments (vfrag_ready), the rollout's forward outputs that PPO's epoch 0
+// reuses (e0_valid).
+enum { kWrotePolicy = 1, kWroteValue = 2, kWroteBatch = 4 };
+void wrote(xh_trainer *t, int what) {
+  if (what & kWroteValue) t->vfrag_ready = false;
+  if (what & (kWrotePolicy | kWroteBatch)) t->e0_valid = false;
+}
+int wrote_net(int which) { return which == XH_POLICY ? kWrotePolicy : kWroteValue; }
+
 int opt_apply(xh_trainer *t, int which, float *params, const float *grad,
               int n) {
+  wrote(t, wrote_net(which));
   hipStream_t s = t->ctx->stream;
   auto &o = t->opt[which];
   const xh::OptStep st = opt_step(t, which);
@@ -529,6 +555,7 @@ void clip_free(xh_trainer *t, int which) {
 int reduce_and_step(xh_trainer *t, int which, int step, const float *slab,
                     int nslab, int stride, int n, float *grad, float *params,
                     xh::SlabAlias al = xh::SlabAlias{0, 0, 0, 0}) {
+  wrote(t, wrote_net(which));
   hipStream_t s = t->ctx->stream;
   if (t->clip[which].part) {
     auto &c = t->clip[which];
@@ -742,6 +769,10 @@ int do_rollout(xh_trainer *t) {
   a.params = t->pp;
   a.forced = t->use_forced ? t->forced : nullptr;
   a.qold_out = t->qold;  // KL-PPO only (nullptr otherwise)
+  // PPO's epoch 0 reuses this window's masks and distributions
+  a.e0_p = t->e0_mask ? t->e0_p : nullptr;
+  a.e0_mask = t->e0_mask;
+  t->e0_valid = false;
   // all T slots in one call (one launch where the kernel steps in registers);
   // only slot 0 can hold a wide state
   a.t = 0;
@@ -764,6 +795,11 @@ int do_rollout(xh_trainer *t) {
     t->bins_wide[step + 1] = 0;  // apply + reset on game over: bins >= 0
   }
   t->rolled = true;
+  // valid only from the one kernel that writes both outputs for all T slots:
+  // not after a wide slot 0 (the f32 kernel ran it), the f32 rollouts or
+  // XH_ROLLOUT_KERNEL
+  t->e0_valid = a.e0_mask && !a.wide && t->last_rollout.name &&
+                std::strcmp(t->last_rollout.name, "rollout_split_kernel") == 0;
   if (t->stats.history) CHK(stats_rollout(t));
   return XH_OK;
 }
@@ -815,6 +851,31 @@ int do_learn(xh_trainer *t) {
                   "rollout yet)", sl);
   hipStream_t s = t->ctx->stream;
   const xh_config &c = t->cfg;
+  // Epoch 0 on the rollout's forward outputs (policy_train_spec8_e0_kernel):
+  // PPO with a later epoch to follow, the outputs valid, nothing that selects
+  // or instruments the train kernel.  XH_E0_REUSE (read per learn()): 0 never,
+  // unset / 1 when valid, 2 (tests) fail the learn() when epoch 0 cannot.
+  bool use_e0 = false;
+  {
+    const char *m = std::getenv("XH_E0_REUSE");
+    const int mode = m && *m ? std::atoi(m) : 1;
+    const char *ov = std::getenv("XH_TRAIN_KERNEL"), *ab = std::getenv("XH_ABLATE");
+    bool wide = false;
+    for (size_t sl = 0; sl < t->T() && sl < t->bins_wide.size(); ++sl)
+      wide |= t->bins_wide[sl] != 0;
+    use_e0 = mode != 0 && t->e0_valid && t->e0_mask && t->e0_p &&
+             c.algo == XH_PPO && c.epochs >= 2 && !(ov && *ov) && !wide &&
+             !(ab && std::atoi(ab)) &&
+             !(xh::diag_build() && std::getenv("XH_PHASE_TRACE"));
+    if (mode == 2 && !use_e0)
+      return fail(XH_ERR_STATE, "learn: XH_E0_REUSE=2, but epoch 0 cannot run on "
+                  "the rollout's forward outputs (%s)",
+                  !t->e0_mask ? "this trainer has none: PPO with epochs >= 2 at "
+                                "64 bins, 2-D, [128,128] only"
+                  : !t->e0_valid ? "not valid: no split rollout of this window "
+                                   "under the current policy parameters and batch"
+                                 : "a kernel override or a wide slot");
+  }
   xh::ValueArgs va = t->vargs();
   const int NS = (int)((t->T() + 1) * t->N()), NT = (int)(t->T() * t->N());
   // the transitions that ended an episode (env-major, t ascending); their
@@ -853,7 +914,6 @@ int do_learn(xh_trainer *t) {
       xh::value_reduced_slab(vm) ? xh::SlabAlias{t->cfg.value_h1, t->vl.Fin, t->cfg.bins,
                                t->cfg.dims}
                : xh::SlabAlias{0, 0, 0, 0};
-  t->vfrag_ready = false;  // the step below writes vp
   CHK(reduce_and_step(t, XH_VALUE, 0, t->vslab, t->vslab_n, t->vslab_stride,
                       t->nv, t->vgrad, t->vp, al));
   // calculate_advantage (policy_gradient.h:220-281) on post-update values;
@@ -939,10 +999,18 @@ int do_learn(xh_trainer *t) {
   }
   for (int e = 0; e < c.epochs; ++e) {
     float *g = t->pgrads + (size_t)e * t->np;
-    CHK(timed(t, "policy_train", [&]() {
-      return xh::launch_policy_train(pa, c.policy_h1, c.policy_h2, t->pslab_n,
-                                     s, &t->last_train);
-    }));
+    if (e == 0 && use_e0 && !pa.wide && !pa.ablate && !pa.trace) {
+      // (the later epochs' launches report the kernel: last_train)
+      const xh::PolicyTrainE0Args ea{t->e0_p, t->e0_mask};
+      CHK(timed(t, "policy_train", [&]() {
+        return xh::launch_policy_train_spec8_e0(pa, ea, t->pslab_n, s);
+      }));
+    } else {
+      CHK(timed(t, "policy_train", [&]() {
+        return xh::launch_policy_train(pa, c.policy_h1, c.policy_h2, t->pslab_n,
+                                       s, &t->last_train);
+      }));
+    }
     if (pa.trace) {
       std::vector<long long> tr(trace_n + 2 + 4096);
       if (hipMemcpyAsync(tr.data(), pa.trace, trace_n * 8 + 16 + 4096 * 8,
@@ -1697,6 +1765,19 @@ int xh_trainer_create(xh_ctx *ctx, const xh_config *cfg, xh_trainer **out) {
     }
     if (c.algo == XH_KLPPO || c.record_distrib)
       A(&t->qold, T * N * c.bins * 4);
+    {
+      // epoch 0's inputs from the rollout: N T (1024 + 256) bytes (134 MB +
+      // 33.5 MB at config 3), only where the e0 kernel can run
+      const char *rk = std::getenv("XH_ROLLOUT_KERNEL"), *tk = std::getenv("XH_TRAIN_KERNEL");
+      if (c.algo == XH_PPO && c.epochs >= 2 && c.bins == 64 && c.dims == 2 &&
+          c.policy_h1 == 128 && c.policy_h2 == 128 && !(rk && *rk) && !(tk && *tk)) {
+        A(&t->e0_mask, T * N * (size_t)xh::sp8::kE0RecordBytes);
+        if (t->qold)
+          t->e0_p = t->qold;
+        else
+          A(&t->e0_p, T * N * (size_t)xh::sp8::kE0PBytes);
+      }
+    }
     if (c.algo == XH_KLPPO) {
       A(&t->beta, 4);
       A(&t->kl_log, (size_t)c.epochs * 3 * 4);
@@ -1775,7 +1856,7 @@ int xh_trainer_set_params(xh_trainer *t, int which, const float *host,
       return fail(XH_ERR_INVALID, "params: got %zu floats, model has %zu", n,
                   want);
     HIPCHK(hipSetDevice(t->ctx->device));
-    if (which != XH_POLICY) t->vfrag_ready = false;
+    wrote(t, wrote_net(which));
     float *dst = which == XH_POLICY ? t->pp : t->vp;
     HIPCHK(copy_to_device(dst, host, n * 4, t->ctx->stream));
     HIPCHK(hipStreamSynchronize(t->ctx->stream));
@@ -1942,6 +2023,7 @@ int xh_trainer_forget(xh_trainer *t) {
                   "forget()");
     t->need_shift = true;  // as at the end of do_learn / do_pg_learn
     t->rolled = false;
+    wrote(t, kWroteBatch);  // the window is gone
     t->stats.open = false;  // the row's learner part stays NaN
     return XH_OK;
   });
@@ -2049,6 +2131,7 @@ int xh_trainer_set_forced_actions(xh_trainer *t, const int32_t *host) {
       if (host[i] < 0 || host[i] >= t->cfg.bins)
         return fail(XH_ERR_INVALID, "forced action %d out of range", host[i]);
     HIPCHK(hipSetDevice(t->ctx->device));
+    wrote(t, kWroteBatch);
     HIPCHK(copy_to_device(t->forced, host, n * 4, t->ctx->stream));
     HIPCHK(hipStreamSynchronize(t->ctx->stream));
     t->use_forced = true;
@@ -2126,6 +2209,7 @@ int xh_trainer_set_buffer(xh_trainer *t, int which, const void *host,
         }
     }
     HIPCHK(hipSetDevice(t->ctx->device));
+    wrote(t, kWroteBatch);
     HIPCHK(copy_to_device(buffer_ptr(t, which), host, bytes, t->ctx->stream));
     HIPCHK(hipStreamSynchronize(t->ctx->stream));
     if (which == XH_BUF_BINS || which == XH_BUF_ITEMS) t->need_shift = false;
@@ -2356,6 +2440,7 @@ int xh_trainer_set_env_state(xh_trainer *t, int first, int count,
         return fail(XH_ERR_INVALID, "env %d: item is not an item-table entry",
                     first + e);
     }
+    if (count > 0) wrote(t, kWroteBatch);
     for (int e = 0; e < count; ++e) {
       std::vector<int8_t> v(BD + D);
       std::memcpy(v.data(), bins + (size_t)e * BD, BD);

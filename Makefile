@@ -21,6 +21,7 @@ OBJS     := $(SRC)/policy_kernels.o $(SRC)/value_kernels.o \
             $(SRC)/policy_split4h_kernels.o $(SRC)/policy_split4h_kl_kernels.o \
             $(SRC)/loss_kernels.o $(SRC)/tensor_kernels.o \
             $(SRC)/stats_kernels.o $(SRC)/clip_kernels.o \
+            $(SRC)/diag_kernels.o \
             $(SRC)/train_select.o $(SRC)/model_api.o $(SRC)/tensor_api.o \
             $(SRC)/xylo_hip.o
 # superseded train kernels (the config-3 / config-5
@@ -30,6 +31,7 @@ VARIANT_KERNELS := policy_split_kernels policy_split128_kernels \
             policy_split4p_kernels policy_split8wg_kernels
 HDRS     := $(SRC)/xh_device.h $(SRC)/xh_kernels.h $(SRC)/xh_split.h \
             $(SRC)/spec8_layout.h $(SRC)/spec8_e0_layout.h $(SRC)/xh_opt.h $(SRC)/xh_clip.h \
+            $(SRC)/xh_diag.h $(SRC)/xh_sums.h \
             $(SRC)/xh_host.h include/xylo_hip.h
 
 # Drop-in C++20 layer (include/xylo_compat): the reference's unmodified

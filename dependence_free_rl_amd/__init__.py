@@ -11,6 +11,9 @@ from ._lib import (STAT_ADV_SQSUM, STAT_ADV_SUM, STAT_COUNT,  # noqa: F401
                    STAT_TARGET_SQSUM, STAT_TARGET_SUM, STAT_TRANSITIONS,
                    STAT_VCLIP_SCALE, STAT_VERR_SQSUM, STAT_VERR_SUM,
                    STAT_VGRAD_SQ)
+from ._lib import (UPD_CLIPPED, UPD_COUNT, UPD_ENTROPY_SUM,  # noqa: F401
+                   UPD_K3_SUM, UPD_KL_SUM, UPD_LEARN, UPD_LOGR_SQSUM,
+                   UPD_LOGR_SUM, UPD_ROWS, UPD_SURR_SUM)
 from .trainer import (ALGOS, POLICY, VALUE, Context, Trainer,  # noqa: F401
                       clip_grad_norm, heuristic_evaluate, init_full_policy,
                       init_policy, init_value,

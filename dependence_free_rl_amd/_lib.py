@@ -29,6 +29,10 @@ OPTIMIZERS = {"sgd": 0, "momentum": 1, "adam": 2}
  STAT_PGRAD_SQ_FIRST, STAT_PGRAD_SQ_LAST, STAT_VGRAD_SQ, STAT_KL_BETA,
  STAT_KL_MEAN, STAT_PCLIP_STEPS, STAT_PCLIP_SCALE_MIN, STAT_VCLIP_SCALE,
  STAT_COUNT) = range(22)
+# one row of PPO update diagnostics (the XH_UPD_* enum;
+# xh_trainer_set_update_diag)
+(UPD_LEARN, UPD_ROWS, UPD_LOGR_SUM, UPD_LOGR_SQSUM, UPD_K3_SUM, UPD_CLIPPED,
+ UPD_SURR_SUM, UPD_ENTROPY_SUM, UPD_KL_SUM, UPD_COUNT) = range(10)
 
 
 class XhError(RuntimeError):
@@ -143,6 +147,11 @@ def _load():
         "xh_trainer_set_stats": (i, [vp, i]),
         "xh_trainer_stats_count": (i, [vp, C.POINTER(C.c_long)]),
         "xh_trainer_get_stats": (i, [vp, C.c_long, i, vp]),
+        "xh_trainer_set_update_diag": (i, [vp, i, i]),
+        "xh_trainer_update_diag_count": (i, [vp, C.POINTER(C.c_long)]),
+        "xh_trainer_get_update_diag": (i, [vp, C.c_long, i, vp]),
+        "xh_trainer_get_update_diag_rows": (i, [vp, vp, vp, vp, sz]),
+        "xh_trainer_update_diag_info": (i, [vp, C.c_char_p, sz]),
         "xh_tensor_reduce": (i, [vp, i, vp, vp, C.c_float, sz, i,
                                  C.POINTER(C.c_double),
                                  C.POINTER(C.c_int64)]),
@@ -174,6 +183,10 @@ if lib.xh_struct_size(b"xh_stat_row") != STAT_COUNT * 8:
     raise ImportError("STAT_* indices are out of date (%d entries, the library "
                       "has %d)" % (STAT_COUNT,
                                    lib.xh_struct_size(b"xh_stat_row") // 8))
+if lib.xh_struct_size(b"xh_upd_row") != UPD_COUNT * 8:
+    raise ImportError("UPD_* indices are out of date (%d entries, the library "
+                      "has %d)" % (UPD_COUNT,
+                                   lib.xh_struct_size(b"xh_upd_row") // 8))
 
 
 def check(status):

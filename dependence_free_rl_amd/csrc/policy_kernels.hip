@@ -2813,4 +2813,280 @@ hipError_t launch_policy_train(const PolicyTrainArgs &a, int H1, int H2,
   return hipErrorInvalidValue;
 }
 
+// ======================================================= update diagnostics ==
+// xh_trainer_set_update_diag (opt-in): one more forward of the policy -- the
+// UPDATED parameters -- over the batch's T * N transitions, the rollouts'
+// forward blocks in the rollouts' order with the sampler replaced by the
+// row's record.  One wave holds the env's B probabilities on its lanes
+// (softmax by the sampler's expressions: expf(z), seg_sum<B>, ex / sum) and
+// leaves per (slot, env), by plain stores from the lane of bin 0:
+//   p_new   f32  the probability of the action taken (XH_BUF_ACTION)
+//   ent     f64  H = -sum_b p_b log((double)p_b), a term 0 where p_b == 0
+//   kl      f64  sum_b q_b (log q_b - log p_b), a term 0 where q_b == 0, q the
+//                recorded sampling distribution (DiagArgs::q); NaN without q
+// The double sums run over the env's segment in a fixed xor-shuffle tree
+// (seg_sum_d), contraction off.  Nothing is masked: a NaN or infinite logit
+// gives NaN records, p_b == 0 where q_b > 0 an infinite KL.
+template <int B>
+__device__ __forceinline__ void diag_record(const DiagArgs &a, size_t row,
+                                            double hterm, double kterm,
+                                            float pa, bool writer) {
+#pragma clang fp contract(off)
+  const double hs = seg_sum_d<(B < 64 ? B : 64)>(hterm);
+  const double ks = seg_sum_d<(B < 64 ? B : 64)>(kterm);
+  if (writer) {
+    a.p_new[row] = pa;
+    a.ent[row] = -hs;
+    a.kl[row] = a.q ? ks : __builtin_nan("");
+  }
+}
+
+// p log p and q (log q - log p) of one bin, in double
+__device__ __forceinline__ void diag_bin_terms(float p, const float *q,
+                                               double &hterm, double &kterm) {
+#pragma clang fp contract(off)
+  const double pd = (double)p, lp = log(pd);
+  hterm += p == 0.0f ? 0.0 : pd * lp;
+  if (q) {
+    const float qf = *q;
+    const double qd = (double)qf;
+    kterm += qf == 0.0f ? 0.0 : qd * (log(qd) - lp);
+  }
+}
+
+// B <= 64: lane = row = bin of env `env`, whose B rows sit in lanes seg0 ..
+template <class S>
+__device__ __forceinline__ void diag_step(const DiagArgs &a, int t, float z,
+                                          int env, int seg0, int bin) {
+  constexpr int B = S::B;
+  const float ex = expf(z);
+  const float sum = seg_sum<B>(ex);
+  const float p = ex / sum;
+  const size_t row = (size_t)t * a.b.N + env;
+  const float pa = wave_shfl(p, seg0 + a.b.action[row]);
+  double hterm = 0.0, kterm = 0.0;
+  diag_bin_terms(p, a.q ? a.q + row * B + bin : nullptr, hterm, kterm);
+  diag_record<B>(a, row, hterm, kterm, pa, bin == 0);
+}
+
+// B = 128: the lane holds bins lane and 64 + lane (sample_step128_x's softmax)
+template <class S>
+__device__ __forceinline__ void diag_step128(const DiagArgs &a, int t, int env,
+                                             const float (&z)[2]) {
+  const int lane = threadIdx.x & 63;
+  float p[2];
+  float se = 0.0f;
+#pragma unroll
+  for (int k = 0; k < 2; ++k) {
+    p[k] = expf(z[k]);
+    se += p[k];
+  }
+  se = seg_sum<64>(se);
+  p[0] = p[0] / se;
+  p[1] = p[1] / se;
+  const size_t row = (size_t)t * a.b.N + env;
+  const int act = a.b.action[row];
+  const float pa = act < 64 ? wave_shfl(p[0], act) : wave_shfl(p[1], act - 64);
+  double hterm = 0.0, kterm = 0.0;
+#pragma unroll
+  for (int k = 0; k < 2; ++k)
+    diag_bin_terms(p[k], a.q ? a.q + row * 128 + k * 64 + lane : nullptr, hterm,
+                   kterm);
+  diag_record<128>(a, row, hterm, kterm, pa, lane == 0);
+}
+
+// The f32-MFMA form, every shape: rollout_step_kernel's (HG == 1) or
+// rollout_step128_kernel's (128 bins) forward per (slot, 64-row group), the
+// (slot, group) pairs grid-strided as one list.
+template <class S>
+__global__ __launch_bounds__(256, 2) void policy_diag_kernel(DiagArgs a) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  stage_params<S>(a.params, lds);
+  __syncthreads();
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, lr = lane & 31;
+  const int N = a.b.N;
+  const int o2t = w % S::NOT;
+  const int rt0 = S::NOT >= 4 ? 0 : w / S::NOT;
+  const bool fwd_active = (w / S::NOT) * S::FJ < 2;
+  if constexpr (S::HG == 1) {
+    const int ngroups = N / S::G;
+    const int njobs = a.b.T * ngroups;
+    RowRaw<S> cur, nxt;
+    if ((int)blockIdx.x < njobs)
+      fetch_rows<S>(a.b, blockIdx.x / ngroups, (blockIdx.x % ngroups) * S::G, cur);
+    for (int j = blockIdx.x; j < njobs; j += gridDim.x) {
+      const int t = j / ngroups, e0 = (j - t * ngroups) * S::G;
+      const int jn = j + gridDim.x;
+      if (jn < njobs) fetch_rows<S>(a.b, jn / ngroups, (jn % ngroups) * S::G, nxt);
+      {
+        f32x16 h1[S::NIT][2];
+        layer1<S>(cur, lds, h1);
+        if (fwd_active) {
+          f32x16 pre[S::FJ];
+          layer2<S, S::FJ>(lds, h1, o2t, rt0, pre);
+#pragma unroll
+          for (int q = 0; q < S::FJ; ++q) {
+            const float zp = logit_part<S>(lds, pre[q], o2t);
+            if (lane < 32) lds[S::L_Z + o2t * 64 + (rt0 + q) * 32 + lr] = zp;
+          }
+        }
+      }
+      __syncthreads();
+      if (w == 0) {
+        constexpr int B = S::B;
+        const int e = lane / B, bin = lane % B, env = e0 + e, seg0 = e * B;
+        float zs = 0.0f;
+#pragma unroll
+        for (int o = 0; o < S::NOT; ++o) zs += lds[S::L_Z + o * 64 + lane];
+        const float z = zs + lds[S::L_B3];
+        diag_step<S>(a, t, z, env, seg0, bin);
+      }
+      __syncthreads();
+      cur = nxt;
+    }
+  } else {
+    static_assert(S::B == 128 && S::HG == 2, "128-bin form");
+    constexpr int R = S::R;
+    const int njobs = a.b.T * N;
+    for (int j = blockIdx.x; j < njobs; j += gridDim.x) {
+      const int t = j / N, env = j - t * N;
+#pragma unroll
+      for (int hg = 0; hg < 2; ++hg) {
+        RowRaw<S> rr;
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+          const int bin = hg * 64 + k * 32 + lr;
+          const size_t e = (size_t)t * N + env;
+          const int8_t *bp = a.b.bins + e * S::BD + bin * S::D;
+          const int8_t *ip = a.b.items + e * 4;
+#pragma unroll
+          for (int d = 0; d < S::D; ++d) {
+            rr.bv[k][d] = bp[d];
+            rr.iv[k][d] = ip[d];
+          }
+        }
+        f32x16 h1[S::NIT][2];
+        layer1<S>(rr, lds, h1);
+        if (fwd_active) {
+          f32x16 pre[S::FJ];
+          layer2<S, S::FJ>(lds, h1, o2t, rt0, pre);
+#pragma unroll
+          for (int q = 0; q < S::FJ; ++q) {
+            const float zp = logit_part<S>(lds, pre[q], o2t);
+            if (lane < 32) lds[S::L_Z + o2t * R + hg * 64 + (rt0 + q) * 32 + lr] = zp;
+          }
+        }
+      }
+      __syncthreads();
+      if (w == 0) {
+        float z[2];
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+          float zs = 0.0f;
+#pragma unroll
+          for (int o = 0; o < S::NOT; ++o) zs += lds[S::L_Z + o * R + k * 64 + lane];
+          z[k] = zs + lds[S::L_B3];
+        }
+        diag_step128<S>(a, t, env, z);
+      }
+      __syncthreads();
+    }
+  }
+}
+
+// The f16-pair form for the shapes rollout_split_kernel serves: its staging,
+// its folded item biases and wave_logits_split, groups dealt to waves as it
+// deals them; every slot's rows are read from HBM (nothing steps in
+// registers; the workgroup's other waves cover the load).
+template <class S>
+__global__ __launch_bounds__(64 * roll_split_waves<S>(), roll_split_occ<S>()) void policy_diag_split_kernel(DiagArgs a) {
+  static_assert((S::B == 64 && S::NIT == 4 && S::NOT == 4) ||
+                    (S::B == 32 && S::NIT == 2 && S::NOT == 2),
+                "split form: B=64 [128,128] or B=32 [64,64]");
+  extern __shared__ __attribute__((aligned(16))) float ldsf[];
+  char *lds = reinterpret_cast<char *>(ldsf);
+  stage_split_rollout<S>(a.params, a.env, lds);
+  __syncthreads();
+  const float *lfr = reinterpret_cast<const float *>(lds + RollSplitLds<S>::F);
+  const float b3 = lfr[RollSplitLds<S>::B3];
+  const float *b1fa = lfr + RollSplitLds<S>::B1F, *b1fb = b1fa + S::H1;
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, h = lane >> 5, lr = lane & 31;
+  const int wpb = blockDim.x >> 6;
+  const int ngroups = a.b.N / S::G;
+  const int eoff = S::G == 2 ? h : 0, seg0 = S::G == 2 ? 32 * h : 0;
+  const int bin = S::G == 2 ? lr : lane;
+  const int per = (ngroups + (int)gridDim.x - 1) / (int)gridDim.x;
+  const int g_end = min(ngroups, ((int)blockIdx.x + 1) * per);
+  for (int g = (int)blockIdx.x * per + w; g < g_end; g += wpb) {
+    const int e0 = g * S::G, env = e0 + eoff;
+    for (int t = 0; t < a.b.T; ++t) {
+      RowRaw<S> cur;
+      fetch_rows<S>(a.b, t, e0, cur);
+      const float *b1r[2];
+#pragma unroll
+      for (int rt = 0; rt < 2; ++rt) {
+        bool ia = true;
+#pragma unroll
+        for (int d = 0; d < S::D; ++d) ia &= cur.iv[rt][d] == a.env.item_a[d];
+        b1r[rt] = ia ? b1fa : b1fb;
+      }
+      float zl[2];
+      wave_logits_split<S>(lds, cur, b1r, zl);
+      const float z = (h ? zl[1] : zl[0]) + b3;
+      diag_step<S>(a, t, z, env, seg0, bin);
+    }
+  }
+}
+
+hipError_t launch_policy_diag(const DiagArgs &a, int H1, int H2, int wide,
+                              int grid, hipStream_t s, KernelInfo *info) {
+  const int B = a.env.B, D = a.env.D;
+  KernelInfo dummy;
+  if (!info) info = &dummy;
+  info->math = kMathF32Mfma;
+#define X(XB, XD, XH1, XH2)                                                  \
+  if (B == XB && D == XD && H1 == XH1 && H2 == XH2) {                        \
+    using S = PShape<XB, XD, XH1, XH2>;                                      \
+    const int ng = a.b.N / S::G;                                             \
+    if constexpr ((S::B == 64 && S::NIT == 4 && S::NOT == 4) ||             \
+                  (S::B == 32 && S::NIT == 2 && S::NOT == 2)) {              \
+      if (rollout_split() && !wide) {                                        \
+        static bool sattr = false;                                           \
+        if (!sattr) {                                                        \
+          (void)hipFuncSetAttribute(                                         \
+              (const void *)policy_diag_split_kernel<S>,                     \
+              hipFuncAttributeMaxDynamicSharedMemorySize,                    \
+              (int)RollSplitLds<S>::bytes);                                  \
+          sattr = true;                                                      \
+        }                                                                    \
+        constexpr int kRW = roll_split_waves<S>();                           \
+        const int wg = (ng + kRW - 1) / kRW;                                 \
+        const int wgr = S::B == 64 ? (kRW == 8 ? grid : cu_count()) : wg;    \
+        info->name = "policy_diag_split_kernel";                             \
+        info->math = kMathSplitRollout;                                      \
+        hipLaunchKernelGGL(policy_diag_split_kernel<S>,                      \
+                           dim3(wgr < wg ? wgr : wg), dim3(64 * kRW),        \
+                           RollSplitLds<S>::bytes, s, a);                    \
+        return hipGetLastError();                                            \
+      }                                                                      \
+    }                                                                        \
+    static bool attr = false;                                                \
+    if (!attr) {                                                             \
+      (void)hipFuncSetAttribute((const void *)policy_diag_kernel<S>,         \
+                                hipFuncAttributeMaxDynamicSharedMemorySize,  \
+                                (int)rollout_lds<S>());                      \
+      attr = true;                                                           \
+    }                                                                        \
+    const long jobs = (long)a.b.T * ng;                                      \
+    info->name = "policy_diag_kernel";                                       \
+    hipLaunchKernelGGL(policy_diag_kernel<S>,                                \
+                       dim3((unsigned)(grid < jobs ? grid : jobs)),          \
+                       dim3(256), rollout_lds<S>(), s, a);                   \
+    return hipGetLastError();                                                \
+  }
+  XH_POLICY_SHAPES(X)
+#undef X
+  return hipErrorInvalidValue;
+}
+
 }  // namespace xh

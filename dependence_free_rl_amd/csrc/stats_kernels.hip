@@ -13,6 +13,7 @@
 #include "../../include/xylo_hip.h"
 #include "xh_device.h"
 #include "xh_kernels.h"
+#include "xh_sums.h"
 
 namespace xh {
 
@@ -20,45 +21,6 @@ static_assert(XH_STAT_NEGLOGP_SUM - XH_STAT_EPISODES + 1 == kStatEpisodeSummed &
               XH_STAT_ADV_SQSUM - XH_STAT_VERR_SUM + 1 == kStatLearnerSums &&
               XH_STAT_VERR_SUM == XH_STAT_NEGLOGP_SUM + 1,
               "row layout: the entries summed over ranks are contiguous");
-
-namespace {
-
-// Sums of S values over a 256-thread workgroup -> part[0..S) (thread 0).
-template <int S>
-__device__ __forceinline__ void block_sums(double (&v)[S], double *part) {
-  __shared__ double red[S][4];
-#pragma unroll
-  for (int k = 0; k < S; ++k)
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v[k] += __shfl_xor(v[k], o, kWave);
-  const int w = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0)
-#pragma unroll
-    for (int k = 0; k < S; ++k) red[k][w] = v[k];
-  __syncthreads();
-  if (threadIdx.x == 0)
-#pragma unroll
-    for (int k = 0; k < S; ++k)
-      part[k] = (red[k][0] + red[k][1]) + (red[k][2] + red[k][3]);
-}
-
-// Column sums of part[nparts][S] in one wave: lane l adds rows l, l + 64, ...
-// in order, then the shuffle tree.  Every lane returns the sums.
-template <int S>
-__device__ __forceinline__ void wave_column_sums(const double *part, int nparts,
-                                                 double (&v)[S]) {
-#pragma unroll
-  for (int k = 0; k < S; ++k) v[k] = 0.0;
-  for (int i = threadIdx.x; i < nparts; i += 64)
-#pragma unroll
-    for (int k = 0; k < S; ++k) v[k] += part[(size_t)i * S + k];
-#pragma unroll
-  for (int k = 0; k < S; ++k)
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v[k] += __shfl_xor(v[k], o, kWave);
-}
-
-}  // namespace
 
 // One env per lane: walks done[0..T)[e] in slot order (coalesced across envs
 // in the [T][N] layout) with the env's running episode length, which persists

@@ -506,6 +506,39 @@ hipError_t launch_learner_row(const double *part, int nparts,
                               const double *norms, const float *kl_last,
                               const double *pclip, int psteps,
                               const double *vclip, double *row, hipStream_t s);
+// PPO update diagnostics (xh_trainer_set_update_diag, opt-in): a forward of
+// the updated policy over the batch's T * N transitions that leaves one
+// record per (slot, env) (policy_kernels.hip: policy_diag_kernel, f32 MFMA,
+// every shape; policy_diag_split_kernel, f16 pairs, the shapes
+// rollout_split_kernel serves), then their sums into a row of XH_UPD_COUNT
+// doubles (diag_kernels.hip), in double, fixed order, no floating-point
+// atomics.
+struct DiagArgs {
+  EnvDesc env;
+  Batch b;
+  const float *params;  // the policy after the update
+  const float *q;       // [T][N][B] the sampling distributions, or nullptr
+  float *p_new;         // [T][N] probability of the action taken
+  double *ent;          // [T][N] entropy of the row's distribution
+  double *kl;           // [T][N] KL(q || p); NaN without q
+};
+constexpr int kUpdSums = 7;  // row entries LOGR_SUM .. KL_SUM
+// wide: a slot of the batch holds a bin below -capacity (RolloutArgs::wide):
+// the f32 form runs, as it does under XH_ROLLOUT_KERNEL=f32 / =4
+hipError_t launch_policy_diag(const DiagArgs &a, int H1, int H2, int wide,
+                              int grid, hipStream_t s, KernelInfo *info);
+// part[gae_grid(N)][kUpdSums]: the workgroup partials of the xh_diag.h terms
+// of every row (p_new, pold, adv) and of the entropy and KL records
+hipError_t launch_update_diag_sum(const float *p_new, const float *pold,
+                                  const float *adv, const double *ent,
+                                  const double *kl, int N, int T, float clip_eps,
+                                  double *part, hipStream_t s);
+// their fixed-order sum (this rank's share) into row[XH_UPD_LOGR_SUM ..], with
+// row[XH_UPD_LEARN] = learn and row[XH_UPD_ROWS] = rows_global
+hipError_t launch_update_diag_row(const double *part, int nparts, double learn,
+                                  double rows_global, double *row,
+                                  hipStream_t s);
+
 // Slab entries the value net's reduced layer 0 leaves unwritten: the item
 // columns of bins b > 0 of its first [rows][in] block, whose sums equal bin
 // 0's (EpSlabRed).  B = 0: none.

@@ -149,6 +149,19 @@ struct xh_trainer {
     double *part = nullptr, *log = nullptr;
     bool learned = false;
   } clip[2];
+  // xh_trainer_set_update_diag (opt-in; everything null / 0 while off): one
+  // device block holding the ring of rows, the sum kernel's workgroup partials
+  // and the per-row records [T][N] of the last probed learn() (ent, kl, then
+  // p_new); learns = learn() calls since it was set, rows = probed ones (ring
+  // rows written); info / kl_source = what the last probed learn() ran
+  struct upd_state {
+    int history = 0, every = 1;
+    long learns = 0, rows = 0;
+    double *ring = nullptr, *part = nullptr, *ent = nullptr, *kl = nullptr;
+    float *p_new = nullptr;
+    xh::KernelInfo info;
+    const char *kl_source = nullptr;
+  } upd;
   int Tb = 0;  // Batch steps: cfg.steps, or REINFORCE's per-iteration bound
   uint32_t jump_mul = 1;
   int rgrid = 0;
@@ -381,6 +394,7 @@ constexpr uint64_t kEvalStride = 1ull << 26;  // draws between env streams
 constexpr int kMaxTrainDepth = 512;
 constexpr int kBinCapacity = 8;             // bin_packing.h:48, every dim
 constexpr int kMaxStatsRows = 1 << 20;      // xh_trainer_set_stats: 151 MB
+constexpr int kMaxUpdRows = 1 << 20;        // xh_trainer_set_update_diag: 75 MB
 
 xh::EnvDesc make_env(int bins, int dims) {
   static const int ia[3][3] = {{4, 0, 0}, {4, 2, 0}, {4, 2, 2}};
@@ -660,6 +674,55 @@ int stats_learn(xh_trainer *t) {
   return XH_OK;
 }
 
+// ---------------------------------------------------- update diagnostics ----
+// xh_trainer_set_update_diag: after the last epoch of every `every`-th
+// learn(), a forward of the updated policy over the batch, its records summed
+// into the next ring row; with a communicator one all-reduce on the row's
+// summed entries.  Nothing here synchronises the host.
+void upd_free(xh_trainer *t) {
+  if (t->upd.ring) (void)hipFree(t->upd.ring);
+  t->upd = xh_trainer::upd_state{};
+}
+
+// e0_at_entry: PPO's epoch-0 distributions (e0_p) were this window's when the
+// learn() began (its own optimizer steps have cleared e0_valid since).
+int upd_learn(xh_trainer *t, bool e0_at_entry) {
+  auto &u = t->upd;
+  const long learn = u.learns++;
+  if (learn % u.every) return XH_OK;
+  hipStream_t s = t->ctx->stream;
+  const int N = (int)t->N(), T = (int)t->T();
+  xh::DiagArgs a{};
+  a.env = t->env;
+  a.b = t->batch();
+  a.params = t->pp;
+  a.q = t->qold ? t->qold : (e0_at_entry && t->e0_p ? t->e0_p : nullptr);
+  u.kl_source = t->qold ? "qold" : (a.q ? "e0_p" : nullptr);
+  a.p_new = u.p_new;
+  a.ent = u.ent;
+  a.kl = u.kl;
+  int wide = 0;
+  for (size_t sl = 0; sl < t->T() && sl < t->bins_wide.size(); ++sl)
+    wide |= t->bins_wide[sl];
+  double *row = u.ring + (size_t)(u.rows % u.history) * XH_UPD_COUNT;
+  CHK(timed(t, "probe", [&]() {
+    return xh::launch_policy_diag(a, t->cfg.policy_h1, t->cfg.policy_h2, wide,
+                                  t->rgrid, s, &u.info);
+  }));
+  CHK(timed(t, "probe", [&]() {
+    return xh::launch_update_diag_sum(u.p_new, t->pold, t->adv, u.ent, u.kl, N,
+                                      T, t->cfg.clip_eps, u.part, s);
+  }));
+  CHK(timed(t, "probe", [&]() {
+    return xh::launch_update_diag_row(u.part, xh::gae_grid(N), (double)learn,
+                                      (double)T * t->cfg.num_envs_global, row,
+                                      s);
+  }));
+  CHK(allreduce_d(t, row + XH_UPD_LOGR_SUM, xh::kUpdSums));
+  ++u.rows;
+  return XH_OK;
+}
+
 int do_pg_rollout(xh_trainer *t);
 int do_pg_learn(xh_trainer *t);
 
@@ -851,6 +914,7 @@ int do_learn(xh_trainer *t) {
                   "rollout yet)", sl);
   hipStream_t s = t->ctx->stream;
   const xh_config &c = t->cfg;
+  const bool e0_at_entry = t->e0_valid;  // for the update diagnostics
   // Epoch 0 on the rollout's forward outputs (policy_train_spec8_e0_kernel):
   // PPO with a later epoch to follow, the outputs valid, nothing that selects
   // or instruments the train kernel.  XH_E0_REUSE (read per learn()): 0 never,
@@ -1163,6 +1227,7 @@ int do_learn(xh_trainer *t) {
     }
   }
   for (auto &cl : t->clip) cl.learned = cl.part != nullptr;
+  if (t->upd.history) CHK(upd_learn(t, e0_at_entry));
   if (t->stats.history) CHK(stats_learn(t));
   t->need_shift = true;
   t->rolled = false;
@@ -1507,6 +1572,7 @@ size_t xh_struct_size(const char *name) {
   if (!std::strcmp(name, "xh_eval")) return sizeof(xh_eval);
   if (!std::strcmp(name, "xh_layer")) return sizeof(xh_layer);
   if (!std::strcmp(name, "xh_stat_row")) return XH_STAT_COUNT * sizeof(double);
+  if (!std::strcmp(name, "xh_upd_row")) return XH_UPD_COUNT * sizeof(double);
   return 0;
 }
 
@@ -1831,6 +1897,7 @@ int xh_trainer_destroy(xh_trainer *t) {
     for (hipEvent_t e : t->event_pool) (void)hipEventDestroy(e);
     for (void *p : t->allocs) (void)hipFree(p);
     stats_free(t);
+    upd_free(t);
     clip_free(t, XH_POLICY);
     clip_free(t, XH_VALUE);
     if (t->pg.host_active) (void)hipHostFree(t->pg.host_active);
@@ -2103,6 +2170,142 @@ int xh_trainer_get_stats(xh_trainer *t, long first, int count, double *out) {
     if (count > n1)
       HIPCHK(copy_to_host(out + (size_t)n1 * XH_STAT_COUNT, st.ring,
                           (size_t)(count - n1) * rowb, s));
+    return XH_OK;
+  });
+}
+
+int xh_trainer_set_update_diag(xh_trainer *t, int history_rows, int every) {
+  return guard([&]() -> int {
+    if (!t) return fail(XH_ERR_INVALID, "null trainer");
+    if (t->cfg.algo == XH_PG)
+      return fail(XH_ERR_INVALID, "set_update_diag: not for XH_PG trainers "
+                  "(REINFORCE has no old policy to compare with)");
+    if (history_rows < 0 || history_rows > kMaxUpdRows)
+      return fail(XH_ERR_INVALID, "set_update_diag: history_rows %d not in "
+                  "[0, %d]", history_rows, kMaxUpdRows);
+    if (history_rows > 0 && every < 1)
+      return fail(XH_ERR_INVALID, "set_update_diag: every %d (>= 1)", every);
+    HIPCHK(hipSetDevice(t->ctx->device));
+    hipStream_t s = t->ctx->stream;
+    // launches of an earlier learn() may still write the buffers
+    HIPCHK(hipStreamSynchronize(s));
+    upd_free(t);
+    if (history_rows == 0) return XH_OK;
+    auto &u = t->upd;
+    const size_t rows = t->T() * t->N();
+    const size_t ring = (size_t)history_rows * XH_UPD_COUNT,
+                 part = (size_t)xh::gae_grid((int)t->N()) * xh::kUpdSums;
+    // doubles first (ring, partials, entropy, KL), then the f32 p_new
+    const size_t bytes = (ring + part + 2 * rows) * 8 + rows * 4;
+    hipError_t e = hipMalloc((void **)&u.ring, bytes);
+    // unwritten rows and records read as NaN (all-ones bytes)
+    if (e == hipSuccess) e = hipMemsetAsync(u.ring, 0xFF, bytes, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) {
+      upd_free(t);
+      return fail(XH_ERR_HIP, "set_update_diag(%d, %d): %s", history_rows, every,
+                  hipGetErrorString(e));
+    }
+    u.part = u.ring + ring;
+    u.ent = u.part + part;
+    u.kl = u.ent + rows;
+    u.p_new = reinterpret_cast<float *>(u.kl + rows);
+    u.history = history_rows;
+    u.every = every;
+    return XH_OK;
+  });
+}
+
+int xh_trainer_update_diag_count(xh_trainer *t, long *total_rows) {
+  return guard([&]() -> int {
+    if (!t || !total_rows) return fail(XH_ERR_INVALID, "null arg");
+    if (!t->upd.history)
+      return fail(XH_ERR_STATE, "update_diag_count: the diagnostics are off "
+                  "(xh_trainer_set_update_diag)");
+    *total_rows = t->upd.rows;
+    return XH_OK;
+  });
+}
+
+int xh_trainer_get_update_diag(xh_trainer *t, long first, int count, double *out) {
+  return guard([&]() -> int {
+    if (!t || (count > 0 && !out)) return fail(XH_ERR_INVALID, "null arg");
+    const auto &u = t->upd;
+    if (!u.history)
+      return fail(XH_ERR_STATE, "get_update_diag: the diagnostics are off "
+                  "(xh_trainer_set_update_diag)");
+    if (!u.rows)
+      return fail(XH_ERR_STATE, "get_update_diag: no probed learn() since "
+                  "xh_trainer_set_update_diag");
+    if (first < 0 || count < 0 || first > u.rows - count)
+      return fail(XH_ERR_INVALID, "get_update_diag: %d rows from row %ld, %ld "
+                  "written", count, first, u.rows);
+    if (first < u.rows - u.history)
+      return fail(XH_ERR_INVALID, "get_update_diag: row %ld is overwritten (the "
+                  "ring holds rows %ld .. %ld)", first, u.rows - u.history,
+                  u.rows - 1);
+    HIPCHK(hipSetDevice(t->ctx->device));
+    hipStream_t s = t->ctx->stream;
+    HIPCHK(hipStreamSynchronize(s));
+    // at most two runs of the ring
+    const long at = first % u.history;
+    const long n1 = std::min<long>(count, u.history - at);
+    const size_t rowb = (size_t)XH_UPD_COUNT * 8;
+    if (n1 > 0)
+      HIPCHK(copy_to_host(out, u.ring + (size_t)at * XH_UPD_COUNT,
+                          (size_t)n1 * rowb, s));
+    if (count > n1)
+      HIPCHK(copy_to_host(out + (size_t)n1 * XH_UPD_COUNT, u.ring,
+                          (size_t)(count - n1) * rowb, s));
+    return XH_OK;
+  });
+}
+
+int xh_trainer_get_update_diag_rows(xh_trainer *t, float *p_new, double *entropy,
+                                    double *kl, size_t n) {
+  return guard([&]() -> int {
+    if (!t) return fail(XH_ERR_INVALID, "null trainer");
+    const auto &u = t->upd;
+    if (!u.history)
+      return fail(XH_ERR_STATE, "get_update_diag_rows: the diagnostics are off "
+                  "(xh_trainer_set_update_diag)");
+    if (!u.rows)
+      return fail(XH_ERR_STATE, "get_update_diag_rows: no probed learn() since "
+                  "xh_trainer_set_update_diag");
+    const size_t rows = t->T() * t->N();
+    if (n != rows)
+      return fail(XH_ERR_INVALID, "get_update_diag_rows: n %zu, the batch has "
+                  "%zu transitions", n, rows);
+    HIPCHK(hipSetDevice(t->ctx->device));
+    hipStream_t s = t->ctx->stream;
+    HIPCHK(hipStreamSynchronize(s));
+    if (p_new) HIPCHK(copy_to_host(p_new, u.p_new, rows * 4, s));
+    if (entropy) HIPCHK(copy_to_host(entropy, u.ent, rows * 8, s));
+    if (kl) HIPCHK(copy_to_host(kl, u.kl, rows * 8, s));
+    return XH_OK;
+  });
+}
+
+int xh_trainer_update_diag_info(xh_trainer *t, char *buf, size_t cap) {
+  return guard([&]() -> int {
+    if (!t || !buf || cap == 0) return fail(XH_ERR_INVALID, "null arg");
+    const auto &u = t->upd;
+    if (!u.history)
+      return fail(XH_ERR_STATE, "update_diag_info: the diagnostics are off "
+                  "(xh_trainer_set_update_diag)");
+    auto quoted = [](const char *v) {
+      return v ? "\"" + std::string(v) + "\"" : std::string("null");
+    };
+    const std::string js =
+        "{\"kernel\": " + quoted(u.info.name) + ", \"math\": " +
+        quoted(u.info.math == xh::kMathSplitRollout ? "f16_pair" : "f32_mfma") +
+        ", \"kl_source\": " + quoted(u.kl_source) + ", \"history_rows\": " +
+        std::to_string(u.history) + ", \"every\": " + std::to_string(u.every) +
+        "}";
+    if (js.size() + 1 > cap)
+      return fail(XH_ERR_INVALID, "update_diag_info: %zu bytes needed",
+                  js.size() + 1);
+    std::memcpy(buf, js.c_str(), js.size() + 1);
     return XH_OK;
   });
 }

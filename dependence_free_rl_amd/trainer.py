@@ -369,6 +369,7 @@ class Trainer:
         self.np_ = _lib.lib.xh_trainer_num_params(self.h, POLICY)
         self.nv = _lib.lib.xh_trainer_num_params(self.h, VALUE)
         self._stats_rows = 0  # set_stats: rows of the device ring (0 = off)
+        self._upd_rows = 0  # set_update_diag: rows of its ring (0 = off)
         if algo == "pg":  # steps = episodes per env; the batch has a step bound
             self.episodes = steps
             self.T = _lib.lib.xh_trainer_buffer_bytes(self.h, BUF_ACTION) // (
@@ -606,6 +607,80 @@ class Trainer:
                     col(_lib.STAT_PCLIP_STEPS) / float(self.epochs),
                 "policy_clip_scale_min": col(_lib.STAT_PCLIP_SCALE_MIN).copy(),
                 "value_clip_scale": col(_lib.STAT_VCLIP_SCALE).copy(),
+            }
+
+    # ------------------------------------------------ update diagnostics --
+    def set_update_diag(self, history_rows, every=1):
+        """PPO update diagnostics (xh_trainer_set_update_diag): every
+        `every`-th learn() ends with a forward of the updated policy over the
+        batch and leaves one row of UPD_COUNT doubles in a device ring of
+        `history_rows` rows; 0 turns them off (the default)."""
+        check(_lib.lib.xh_trainer_set_update_diag(self.h, int(history_rows),
+                                                  int(every)))
+        self._upd_rows = int(history_rows)
+
+    def update_diag_count(self):
+        """Rows written (probed learns) since set_update_diag."""
+        n = C.c_long()
+        check(_lib.lib.xh_trainer_update_diag_count(self.h, C.byref(n)))
+        return n.value
+
+    def update_diag(self, first=None, count=None):
+        """Rows [first, first + count) as a float64 [rows][UPD_COUNT] array
+        (xh_trainer_get_update_diag; synchronises).  Default: every row still
+        in the ring, up to the last one written."""
+        total = self.update_diag_count()
+        if first is None:
+            first = max(0, total - self._upd_rows)
+        if count is None:
+            count = max(0, total - first)
+        out = np.zeros((count, _lib.UPD_COUNT), np.float64)
+        check(_lib.lib.xh_trainer_get_update_diag(self.h, first, count,
+                                                  _ptr(out)))
+        return out
+
+    def update_diag_rows(self):
+        """The per-row records of the last probed learn(), [T][N] each:
+        {"p_new": float32, "entropy": float64, "kl": float64 (NaN where no
+        sampling distributions were recorded)}.  Synchronises."""
+        shape = (self.T, self.N)
+        out = {"p_new": np.zeros(shape, np.float32),
+               "entropy": np.zeros(shape, np.float64),
+               "kl": np.zeros(shape, np.float64)}
+        check(_lib.lib.xh_trainer_get_update_diag_rows(
+            self.h, _ptr(out["p_new"]), _ptr(out["entropy"]), _ptr(out["kl"]),
+            self.T * self.N))
+        return out
+
+    def update_diag_info(self):
+        """What the last probed learn() ran (xh_trainer_update_diag_info):
+        {"kernel", "math", "kl_source", "history_rows", "every"}."""
+        import json
+        buf = C.create_string_buffer(512)
+        check(_lib.lib.xh_trainer_update_diag_info(self.h, buf, len(buf)))
+        return json.loads(buf.value.decode())
+
+    def update_curve(self, first=None, count=None):
+        """Per-row series derived from update_diag(): a dict of float64
+        arrays.  approx_kl = -mean log ratio, approx_kl_k2 = mean squared log
+        ratio / 2, approx_kl_k3 = mean of (ratio - 1) - log ratio,
+        clip_fraction, surrogate (mean clipped objective), entropy of the
+        updated policy and kl = mean KL(old || new) over the recorded
+        distributions (NaN where none were).  A non-finite entry means a row
+        of the batch had a zero or NaN probability: nothing is masked."""
+        u = self.update_diag(first, count)
+        col = lambda k: u[:, k]  # noqa: E731
+        with np.errstate(divide="ignore", invalid="ignore"):
+            n = col(_lib.UPD_ROWS)
+            return {
+                "learn": col(_lib.UPD_LEARN).copy(),
+                "approx_kl": -col(_lib.UPD_LOGR_SUM) / n,
+                "approx_kl_k2": col(_lib.UPD_LOGR_SQSUM) / (2.0 * n),
+                "approx_kl_k3": col(_lib.UPD_K3_SUM) / n,
+                "clip_fraction": col(_lib.UPD_CLIPPED) / n,
+                "surrogate": col(_lib.UPD_SURR_SUM) / n,
+                "entropy": col(_lib.UPD_ENTROPY_SUM) / n,
+                "kl": col(_lib.UPD_KL_SUM) / n,
             }
 
     # ------------------------------------------------------------ timing --

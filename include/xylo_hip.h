@@ -405,6 +405,69 @@ int xh_trainer_stats_count(xh_trainer *t, long *total_rows);
  * statistics are off. */
 int xh_trainer_get_stats(xh_trainer *t, long first, int count, double *out);
 
+/* ------------------------------------------- PPO update diagnostics ---- */
+/* What a learn() did to the policy, off by default: with them off no launch is
+ * added and no buffer allocated.  With them on, every `every`-th learn() ends
+ * with one more forward of the UPDATED policy over the batch's T * N
+ * transitions (the rollout's forward with the sampler replaced by a record per
+ * row), reduced on the device to one row of XH_UPD_COUNT doubles in a ring of
+ * `history_rows` rows of its own (the statistics row above is unchanged).
+ * Three launches and, with a communicator, one all-reduce of the seven sums;
+ * no host synchronisation.  The forward runs on f16 pairs where the rollout
+ * does (64 bins 2-D [128,128] and 32 bins 1-D [64,64], no wide slot, no
+ * XH_ROLLOUT_KERNEL override) and on f32 MFMA otherwise -- at 128 bins always.
+ *
+ * Per row, with p_new the updated policy's probability of the action taken,
+ * p_old = XH_BUF_POLD, A = XH_BUF_ADV as the epochs read it and eps =
+ * clip_eps (csrc/xh_diag.h, the function the kernel compiles):
+ *   r32     = p_new / p_old in f32, as the clipped loss forms it (rl.h:54-74)
+ *   clipped = 1 where r32 > 1.0f + eps or r32 < 1.0f - eps
+ *   surr    = min(clamp(r32, 1 - eps, 1 + eps) * A, r32 * A), f32: the
+ *             surrogate objective (without the loss's factor -1)
+ *   logr    = log((double)p_new) - log((double)p_old)
+ *   k3      = ((double)p_new / (double)p_old - 1) - logr
+ *   H       = -sum_b p_b log((double)p_b) over the row's B probabilities
+ *   KL      = sum_b q_b (log q_b - log p_b), q the sampling distribution: from
+ *             XH_BUF_QOLD where the trainer records it (XH_KLPPO,
+ *             record_distrib), else from the distributions PPO's epoch 0
+ *             reuses when they were valid at this learn() (64 bins), else NaN
+ * Nothing is masked: p_new == 0 gives logr = -inf, a NaN stays a NaN, and a
+ * non-finite entry in a row is the signal that the policy collapsed.
+ *
+ * Sums are double, fixed order, no floating-point atomics: a row is
+ * bit-identical from run to run.  -LOGR_SUM / ROWS is the usual approximate
+ * KL(old || new), LOGR_SQSUM / (2 ROWS) and K3_SUM / ROWS its lower-variance
+ * forms, CLIPPED / ROWS the clip fraction. */
+enum { XH_UPD_LEARN = 0,       /* learn() calls since the diagnostics were set, this one's index */
+       XH_UPD_ROWS = 1,        /* T * num_envs_global */
+       /* summed over ranks, contiguous: */
+       XH_UPD_LOGR_SUM = 2, XH_UPD_LOGR_SQSUM = 3, XH_UPD_K3_SUM = 4,
+       XH_UPD_CLIPPED = 5, XH_UPD_SURR_SUM = 6, XH_UPD_ENTROPY_SUM = 7,
+       XH_UPD_KL_SUM = 8,      /* NaN when no distributions were recorded */
+       XH_UPD_COUNT };
+/* history_rows > 0 (at most 2^20) with every >= 1: diagnostics on, with a
+ * fresh ring and fresh record buffers (f32 + 2 f64 per transition); the learn
+ * counter restarts at 0 and learn() number k is probed when k % every == 0.
+ * history_rows == 0: off, buffers freed.  xh_trainer_forget is no learn().
+ * XH_PG: XH_ERR_INVALID.  In a world > 1 job every rank sets the same values
+ * at the same point of its loop (the all-reduce has to meet its peers). */
+int xh_trainer_set_update_diag(xh_trainer *t, int history_rows, int every);
+/* Rows written (probed learns) since the diagnostics were switched on. */
+int xh_trainer_update_diag_count(xh_trainer *t, long *total_rows);
+/* Synchronises the stream and copies rows [first, first + count) to out
+ * [count][XH_UPD_COUNT].  XH_ERR_INVALID for rows the ring has overwritten or
+ * not written yet; XH_ERR_STATE when the diagnostics are off or no probed
+ * learn() has run. */
+int xh_trainer_get_update_diag(xh_trainer *t, long first, int count, double *out);
+/* The per-row records of the last probed learn(), [T][N] each: p_new, H, KL
+ * (NaN without distributions).  Synchronises. */
+int xh_trainer_get_update_diag_rows(xh_trainer *t, float *p_new, double *entropy,
+                                    double *kl, size_t n);   /* last probed learn, n = T*N; any may be NULL */
+/* JSON {"kernel": name|null, "math": "f32_mfma"|"f16_pair", "kl_source":
+ * "qold"|"e0_p"|null, "history_rows": n, "every": n}: what the last probed
+ * learn() ran (kernel null before the first). */
+int xh_trainer_update_diag_info(xh_trainer *t, char *buf, size_t cap);
+
 /* ------------------------------------------------- vectorised envs ---- */
 /* N bp::environment instances (bin_packing.h:46-85, generalised to B bins /
  * D dims as the trainer's) whose state stays in HBM, for a caller that brings
@@ -628,7 +691,8 @@ int xh_tensor_transpose(xh_ctx *ctx, const float *in, float *out, int rows,
 /* sizeof of the ABI structs ("xh_config", "xh_eval", "xh_layer"; 0 if
  * unknown), so a
  * foreign-language binding can check its mirror of them.  "xh_stat_row": the
- * bytes of one statistics row, XH_STAT_COUNT * 8. */
+ * bytes of one statistics row, XH_STAT_COUNT * 8; "xh_upd_row": of one
+ * update-diagnostics row, XH_UPD_COUNT * 8. */
 size_t xh_struct_size(const char *name);
 
 /* Kernel timing with HIP events on the trainer's stream (off by default).
@@ -639,7 +703,9 @@ size_t xh_struct_size(const char *name);
 int xh_trainer_set_timing(xh_trainer *t, int on);
 /* name: "rollout_step" | "policy_train" | "value" | "reduce_sgd" | "allreduce"
  * | "stats" (the statistics launches of xh_trainer_set_stats; their
- * all-reduces count under "allreduce").
+ * all-reduces count under "allreduce") | "probe" (the three launches of a
+ * probed learn(), xh_trainer_set_update_diag; its all-reduce counts under
+ * "allreduce").
  * Returns accumulated milliseconds and launch count since the last reset. */
 int xh_trainer_kernel_time(xh_trainer *t, const char *name, double *ms,
                            long *launches);

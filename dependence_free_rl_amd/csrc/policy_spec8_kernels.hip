@@ -59,7 +59,8 @@
 // bf16 parts, 48 KB, in the three-part form), H1 two f16 parts [64 r][128 i]
 // (32 KB), relu masks [64 r][128 o] (0x4000 = 2.0 as bf16 and as f16)
 // in two slots (32 KB apart, 16 KB used), then f32 vectors; image layout
-// spec8_layout.h.
+// spec8_layout.h.  (The epoch-0 build, XH_SP8_E0_TU below, has its own
+// schedule and LDS order.)
 #include <cstdlib>
 #include <type_traits>
 
@@ -124,14 +125,25 @@
 // logits and softmax would recompute what rollout_split_kernel just computed
 // from the same parameters; the backward pass needs of them only the relu
 // masks and the distribution p.  The matrix waves here run no layer 2 (no W2
-// fragments, no partial logits, no exp / sum / divide): in phase A(j) they load
-// group j+1's p (PolicyTrainE0Args::e0_p) and their own 32 mask bits per lane
-// (e0_mask, spec8_e0_layout.h: the rollout holds its accumulators in this
-// kernel's C layout, so a lane's dword is its registers' bits), and from p on
-// run the same expressions.  Vector waves, barriers, dW2, the reassociated
-// dW3 and the write-outs are unchanged.  The trainer launches it only while
-// the rollout's outputs are valid (xylo_hip.cpp, e0_valid).  Preprocessor
-// blocks, as the KL-PPO build.
+// fragments, no partial logits, no exp / sum / divide): they load a group's p
+// (PolicyTrainE0Args::e0_p) and their own 32 mask bits per lane (e0_mask,
+// spec8_e0_layout.h: the rollout holds its accumulators in this kernel's C
+// layout, so a lane's dword is its registers' bits) a group ahead, and from p
+// on run the same expressions.  With layer 2 gone nothing reads the H1 image,
+// so the vector waves run no layer 1 either (no W1 fragments, no layer-1
+// MFMAs, no H1 stores; g (x) H1 and dW1 take H1 from the exact f32 chain as
+// in every build), and the prologue computes neither S_W nor the b2 / w3 / b3
+// vectors.  What is left has one phase and one barrier per group:
+//   P(j): matrix DW(j-1) + SM(j+1)      vector DH(j) + g (x) H1(j) + dW1(j)
+// with the masks in a ring of four slots (DW reads j-1, DH j, SM writes j+1),
+// g (x) H1 and the staged g in two (group j's in slot j & 1), the loop
+// unrolled over four groups, SM(1) alone in P(0) and DW(J-1) after the loop.
+// Every sum keeps its order: the gradients are bit for bit those of the
+// two-phase form.  LDS: the f32 vectors first (8 KB, so their offsets stay
+// immediates), then the two g (x) H1 slots and the four mask slots (136 KB).
+// The reassociated dW3 and the write-outs are unchanged.  The trainer
+// launches it only while the rollout's outputs are valid (xylo_hip.cpp,
+// e0_valid).  Preprocessor blocks, as the KL-PPO build.
 #ifndef XH_SP8_E0_TU
 #define XH_SP8_E0_TU 0
 #endif
@@ -191,14 +203,35 @@ constexpr int kMaskLog2 = XH_SP8_DW2_3P ? 1 : 15;
 #if !XH_SP8_DW2_3P
 constexpr int kRelMin = -28;
 #endif
+#if XH_SP8_E0_TU
+// (epoch-0 build: no layer 2, so no H1 image.  One phase per group: g (x) H1
+// in two slots, group j's in slot j & 1 at + kGhSlot (j & 1); the masks in a
+// ring of four, group j's in slot j & 3 at + kMaskSlot (j & 3).  The f32
+// vectors come first, so that their offsets fold into the ds instructions'
+// 16-bit immediates: with four unrolled phases the addresses built in
+// registers for a base above 64 KB spilled.)
+constexpr int L_F = 0;
+constexpr int kFBytes = 8192;
+constexpr int L_GH = kFBytes;      // g (x) H1: hi, lo; two slots
+constexpr int kGhSlot = kGhParts * kImg;
+constexpr int kMaskSlot = kImg;
+constexpr int L_MK = L_GH + 2 * kGhSlot;
+#define SP8_GSLOT(ms) ((ms) & 1)  // the g / g (x) H1 slot of the group in mask slot ms
+#else
 constexpr int L_GH = 0;            // g (x) H1: hi, lo (three-part form: hi, mid, lo)
+constexpr int kGhSlot [[maybe_unused]] = 0;  // (one g (x) H1 slot)
+constexpr int kMaskSlot = 2 * kImg;
 constexpr int L_H1 = kGhParts * kImg;  // H1: hi, lo
 constexpr int L_MK = L_H1 + 2 * kImg;  // masks: slot s at + 2 kImg s (the second kImg unused)
+#define SP8_GSLOT(ms) (ms)
 constexpr int L_F = L_MK + 4 * kImg;
+#endif
+// (F_B2, F_W3, F_Z, F_B3: layer 2's and the softmax's; the epoch-0 build
+// neither fills nor reads them)
 constexpr int F_B2 = 0;            // [128] b2 S2 (layer 2's accumulator input)
 constexpr int F_W3 = F_B2 + kH;    // [128] w3 / S2 (unscales the partial logits)
 constexpr int F_Z = F_W3 + kH;     // [64 rows][4 matrix waves] partial logits
-constexpr int F_G = F_Z + 256;     // [2 parities][3][64] g, g x0, g x1 of a group
+constexpr int F_G = F_Z + 256;     // [2 slots][3][64] g, g x0, g x1 of a group
 constexpr int F_X = F_G + 384;     // [4 slots][2 dims][64 rows] bins / 8
 constexpr int F_REC = F_X + 512;   // [4 slots][action, pold, adv, item is item_a]
 constexpr int F_SC = F_REC + 16;   // [16] scale reduction scratch, the scales
@@ -214,7 +247,12 @@ constexpr int F_END = F_KL + 256;
 #else
 constexpr int F_END = F_FU + kH;
 #endif
+#if XH_SP8_E0_TU
+static_assert(sizeof(float) * F_END <= kFBytes, "the f32 vectors' region");
+constexpr size_t kLds = L_MK + 4 * kMaskSlot;
+#else
 constexpr size_t kLds = L_F + sizeof(float) * F_END;
+#endif
 static_assert(kLds <= 160 * 1024, "LDS");
 #define FENCE() __builtin_amdgcn_sched_barrier(0)
 
@@ -314,7 +352,9 @@ __global__ __launch_bounds__(kThreads, 2) void policy_train_spec8_kernel(PolicyT
     float mw = 0.0f, md = 0.0f, mh = 0.0f;
     for (int e = tid; e < kH * kH; e += kThreads) {
       const float v = P[PL.oW2() + e];
-      mw = fmaxf(mw, fabsf(v));
+#if !XH_SP8_E0_TU
+      mw = fmaxf(mw, fabsf(v));  // (S_W scales layer 2 only)
+#endif
       md = fmaxf(md, fabsf(v * P[PL.ow3() + (e >> 7)]));
     }
     if (tid < kH) {
@@ -332,19 +372,25 @@ __global__ __launch_bounds__(kThreads, 2) void policy_train_spec8_kernel(PolicyT
     (void)mh_own;
 #pragma unroll
     for (int o = 1; o < 64; o <<= 1) {
+#if !XH_SP8_E0_TU
       mw = fmaxf(mw, __shfl_xor(mw, o, kWave));
+#endif
       md = fmaxf(md, __shfl_xor(md, o, kWave));
       mh = fmaxf(mh, __shfl_xor(mh, o, kWave));
     }
     if (l == 0) {
+#if !XH_SP8_E0_TU
       lf[F_SC + w] = mw;
+#endif
       lf[F_SC + 8 + w] = md;
     }
     __syncthreads();
     float MW = 0.0f, MD = 0.0f;
 #pragma unroll
     for (int v = 0; v < 8; ++v) {
+#if !XH_SP8_E0_TU
       MW = fmaxf(MW, lf[F_SC + v]);
+#endif
       MD = fmaxf(MD, lf[F_SC + 8 + v]);
     }
     __syncthreads();
@@ -375,22 +421,33 @@ __global__ __launch_bounds__(kThreads, 2) void policy_train_spec8_kernel(PolicyT
     const float MH = fmaxf(lf[F_SC + 0], lf[F_SC + 1]);
     __syncthreads();
     if (tid == 0) {
+#if !XH_SP8_E0_TU
       lf[F_SC + 0] = f16_scale_for(MW);  // S_W
+#else
+      (void)mw, (void)MW;
+#endif
       lf[F_SC + 1] = f16_scale_for(MD);  // S_D
       lf[F_SC + 2] = f16_scale_for(MH);  // S_H
     }
     __syncthreads();
   }
-  const float SW = lf[F_SC + 0], SD = lf[F_SC + 1], SH = lf[F_SC + 2];
+#if !XH_SP8_E0_TU
+  const float SW = lf[F_SC + 0];
+#endif
+  const float SD = lf[F_SC + 1], SH = lf[F_SC + 2];
 #if !XH_SP8_DW2_3P
   const int EG = __builtin_amdgcn_readfirstlane(reinterpret_cast<const int *>(lf)[F_SC + 12]);
 #endif
+#if XH_SP8_E0_TU
+  (void)SH;  // (layer 1's image scale; the vector waves' chain takes s_i)
+#else
   const float S2 = SW * SH;  // layer 2's pre-activations are in units of S2
   for (int i = tid; i < kH; i += kThreads) {
     lf[F_B2 + i] = P[PL.ob2() + i] * S2;
     lf[F_W3 + i] = P[PL.ow3() + i] * (1.0f / S2);
   }
   if (tid == 0) lf[F_B3] = P[PL.ob3()];
+#endif
   float *slab = a.slab + (size_t)blockIdx.x * a.slab_stride;
   const float *w3g = P + PL.ow3();
   // (the loop's barriers order these LDS writes before their first reads)
@@ -587,9 +644,11 @@ __global__ __launch_bounds__(kThreads, 2) void policy_train_spec8_kernel(PolicyT
     // l31 and 32 + l31 (both lane halves, as the softmax leaves them) and this
     // lane's mask word, bit 16 t + e = the relu mask of what would be
     // c[t][e]; a wave-uniform record base and the lane id recomputed
-    float ep[2];
-    unsigned emw;
-    auto e0_load = [&](int j) {
+    // (two sets: group j+1's, which SM(j+1) reads through P(j), and group
+    // j+2's, loaded during P(j))
+    float ep[2], epn[2];
+    unsigned emw, emwn;
+    auto e0_load = [&](int j, float (&ep)[2], unsigned &emw) {
       const size_t ti = tindex(j);
       const int lane =
           opaque((int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)));
@@ -883,7 +942,7 @@ __global__ __launch_bounds__(kThreads, 2) void policy_train_spec8_kernel(PolicyT
         accb2[e] = fma_mix_hi(mwd[u >> 1], gm[t], accb2[e]);
       }
       if (u == 3) {
-        const int mb = 2 * kImg * ms;  // (mwb holds L_MK)
+        const int mb = kMaskSlot * ms;  // (mwb holds L_MK)
         const u32x2 mm = {mwd[0], mwd[1]};
         st4(mb + 8192 * t + mwb[q], __builtin_bit_cast(bf16x4, mm));
       }
@@ -897,10 +956,11 @@ __global__ __launch_bounds__(kThreads, 2) void policy_train_spec8_kernel(PolicyT
     // pair, the mask image read as f16; the 48 tasks keep their order in the
     // 32 slots: one after the lo product, two after the hi product)
     auto dw2 = [&](int ms, auto &&task) {
-      const int mb = 2 * kImg * ms;  // (trM holds L_MK)
+      const int mb = kMaskSlot * ms;  // (trM holds L_MK)
       f16x8 A[2], B[2][2];
       auto ldB = [&](int ks) {
-        const int ob = L_GH + 1024 * (ks >> 1) + ((ks & 1) ? rbg1 : rbg0);
+        // (rbg holds L_GH)
+        const int ob = kGhSlot * SP8_GSLOT(ms) + 1024 * (ks >> 1) + ((ks & 1) ? rbg1 : rbg0);
         B[ks & 1][0] = ld8h(ob);
         B[ks & 1][1] = ld8h(ob + kImg);
       };
@@ -977,10 +1037,11 @@ __global__ __launch_bounds__(kThreads, 2) void policy_train_spec8_kernel(PolicyT
 #else
     auto b_task = [&](const f32x16s (&c)[2], int gi, int gpar, bool acc, int k) {
 #endif
+      // (gpar: the group's mask slot; its g slot follows from it)
       if (k == 0)
-        softmax_stage(gi, gpar, acc, 0);
+        softmax_stage(gi, SP8_GSLOT(gpar), acc, 0);
       else if (k >= 3 && k < (XH_SP8_KL_TU ? 10 : 9))
-        softmax_stage(gi, gpar, acc, k - 2);
+        softmax_stage(gi, SP8_GSLOT(gpar), acc, k - 2);
       else if (k >= 12 && k < 44)
         mv_e(c, gpar, (k - 12) >> 4, (k - 12) & 15);
     };
@@ -989,7 +1050,7 @@ __global__ __launch_bounds__(kThreads, 2) void policy_train_spec8_kernel(PolicyT
     // ---- pipeline prologue (barriers as the vector path's)
     if (XH_SP8_PRIO & 3) __builtin_amdgcn_s_setprio(XH_SP8_PRIO & 3);
 #if XH_SP8_E0_TU
-    e0_load(0);
+    e0_load(0, ep, emw);
 #else
     f32x16s c[2];
 #endif
@@ -1001,10 +1062,10 @@ __global__ __launch_bounds__(kThreads, 2) void policy_train_spec8_kernel(PolicyT
     __syncthreads();  // P1: rows staged          (vector: L1(0))
     __syncthreads();  // P2
 #if XH_SP8_E0_TU
-    (void)no_task;
     __syncthreads();  // P3                       (vector: L1(1))
 #pragma unroll
     for (int k = 0; k < 48; ++k) b_task(emw, 0, 0, true, k);
+    e0_load(1, ep, emw);
 #else
     layer2(c, no_task);
     partials_tail(c[0], 0);
@@ -1014,6 +1075,56 @@ __global__ __launch_bounds__(kThreads, 2) void policy_train_spec8_kernel(PolicyT
     for (int k = 0; k < 48; ++k) b_task(c, 0, 0, true, k);
 #endif
     __syncthreads();  // P4
+#if XH_SP8_E0_TU
+    // one phase and one barrier per group, Q = j & 3 at compile time (the slot
+    // offsets fold into immediates):
+    //   P(j): matrix DW(j-1) + SM(j+1)       vector DH(j) + g (x) H1(j) + dW1(j)
+    // DW(j-1) reads mask slot Q-1 and g (x) H1 slot (j-1) & 1 while DH(j) reads
+    // mask slot Q, g (x) H1(j) goes to slot j & 1 and SM(j+1) writes mask slot
+    // Q+1 and g slot (j+1) & 1 (DH(j) and dW1(j) read g slot j & 1); group
+    // j+2's p and mask word are loaded meanwhile, wave 0 stages group j+3's
+    // rows into slot (j+3) & 3 = (j-1) & 3, whose readers finished in P(j-1).
+    // P(0) has no dW2 yet; DW(J-1) follows the loop.
+    auto phase_io = [&](int j, auto &&body) {
+      Raw raw;
+      if (s == 0) raw = stage_load(j + 3);
+      e0_load(j + 2, epn, emwn);
+      body();
+      if (s == 0) stage_store(raw, (j + 3) & 3);
+      ep[0] = epn[0];
+      ep[1] = epn[1];
+      emw = emwn;
+      __syncthreads();
+    };
+    auto period = [&](int j, auto Q) {
+      constexpr int q = decltype(Q)::value;
+      const bool acc = j + 1 < J;
+      phase_io(j, [&] {
+        dw2((q + 3) & 3, [&](int k) { b_task(emw, j + 1, (q + 1) & 3, acc, k); });
+      });
+    };
+    phase_io(0, [&] {
+      const bool acc = 1 < J;
+#pragma unroll
+      for (int k = 0; k < 48; ++k) b_task(emw, 1, 1, acc, k);
+    });
+    for (int j = 1; j < J; j += 4) {
+      period(j, Par<1>{});
+      if (j + 1 < J) period(j + 1, Par<2>{});
+      if (j + 2 < J) period(j + 2, Par<3>{});
+      if (j + 3 < J) period(j + 3, Par<0>{});
+    }
+    // DW(J-1); the barrier frees the g (x) H1 images for the dW3 partials
+    if (((J - 1) & 3) == 0)
+      dw2(0, no_task);
+    else if (((J - 1) & 3) == 1)
+      dw2(1, no_task);
+    else if (((J - 1) & 3) == 2)
+      dw2(2, no_task);
+    else
+      dw2(3, no_task);
+    __syncthreads();
+#else
     // one period; P = j & 1 at compile time (mask / g slots, image offsets
     // fold into immediates)
     auto period = [&](int j, auto P) {
@@ -1022,11 +1133,7 @@ __global__ __launch_bounds__(kThreads, 2) void policy_train_spec8_kernel(PolicyT
       if (s == 0) raw = stage_load(j + 3);
       // A(j): layer 2 of group j+1; r-tile 0's partial logits in r-tile 1's
       // MFMA slots, r-tile 1's after
-#if XH_SP8_E0_TU
-      // (epoch-0 build: group j+1's p and mask word, nothing else to issue;
-      // B(j-1) is done with the registers, B(j) waits for the loads)
-      e0_load(j + 1);
-#elif XH_SP8_L2I
+#if XH_SP8_L2I
       // (r-tile 0 is complete only after step 14: its partials after it,
       // r-tile 1's at the tail)
       if (SP8_RUN(1 | 32)) layer2(c, [&](int k) {
@@ -1057,18 +1164,15 @@ __global__ __launch_bounds__(kThreads, 2) void policy_train_spec8_kernel(PolicyT
       // masks in its MFMA slots
       if (s == 0) stage_store(raw, (j + 3) & 3 SP8KL(, j + 3));
       const bool acc = j + 1 < J;
-#if XH_SP8_E0_TU
-      dw2(par, [&](int k) { b_task(emw, j + 1, 1 - par, acc, k); });
-#else
       if (SP8_RUN(1 | 16))
         dw2(par, [&](int k) { b_task(c, j + 1, 1 - par, acc, k); });
-#endif
       __syncthreads();
     };
     for (int j = 0; j < J; j += 2) {
       period(j, Par<0>{});
       if (j + 1 < J) period(j + 1, Par<1>{});
     }
+#endif
 
 #if XH_SP8_KL_TU
     {
@@ -1190,6 +1294,7 @@ __global__ __launch_bounds__(kThreads, 2) void policy_train_spec8_kernel(PolicyT
           __builtin_amdgcn_readfirstlane(__float_as_int(lf[F_REC + 4 * (gi & 3) + 3])) != 0;
       return ia ? b1a : b1b;
     };
+#if !XH_SP8_E0_TU
     // the layer-1 image (layer 2's f16-pair operand) from the matrix cores:
     bf16x8 w1p[3];
     {
@@ -1211,12 +1316,14 @@ __global__ __launch_bounds__(kThreads, 2) void policy_train_spec8_kernel(PolicyT
         w1p[2][e] = y2;
       }
     }
+#endif
     // image stores (lane row i, values r = 32 t + 8 q + 4 h ..; + 1024 t):
     // the g (x) H1 image (region base 0) and the H1 image; dH1's A operand
     // (the mask image read as f16, lane row r = 32 t + l31)
     int vwb[4];
 #pragma unroll
     for (int q = 0; q < 4; ++q) vwb[q] = opaque(wr_base(fi, q, h, 2) + L_GH);
+#if !XH_SP8_E0_TU
     // the H1 image is [r][column]: lane row r = 32 t + l31 (+ 8192 t); this
     // lane's features i = 32 v + 8 q + 4 h + u go to columns 32 v + 16 h + 8
     // (q >> 1) + 4 (q & 1) + u, i.e. whole chunks 2 h and 2 h + 1 of column
@@ -1224,10 +1331,12 @@ __global__ __launch_bounds__(kThreads, 2) void policy_train_spec8_kernel(PolicyT
     int vwH[2];
 #pragma unroll
     for (int j = 0; j < 2; ++j) vwH[j] = opaque(poff(l31, 32 * v + 16 * h + 8 * j, 4) + L_H1);
+#endif
     const int rbm0 = opaque(rd_base(l31, 0, h, 4) + L_MK),
               rbm1 = opaque(rd_base(l31, 1, h, 4) + L_MK);
     float w0 = 0.0f, w1 = 0.0f, sa = 0.0f, sb = 0.0f;
 
+#if !XH_SP8_E0_TU
     // S_H pre-activations of layer 1 of group gi (its bins in slot gi & 3)
     // for this wave's features: two r-tiles of three bf16 MFMAs with W1 as
     // the A operand, C[i][r] (lane column r = 32 t + l31, registers i = 32 v
@@ -1276,6 +1385,7 @@ __global__ __launch_bounds__(kThreads, 2) void policy_train_spec8_kernel(PolicyT
         st8h(vwH[j] + kImg + 8192 * t, __builtin_bit_cast(f16x8, lo));
       }
     };
+#endif
     // x0, x1 -> three bf16 parts each, as bf16 pairs: v_cvt_pk_bf16_f32 and
     // the pair's f32 values from its bits (element 0 << 16, element 1 &
     // 0xffff0000; the compiler otherwise re-converts each element alone);
@@ -1304,8 +1414,10 @@ __global__ __launch_bounds__(kThreads, 2) void policy_train_spec8_kernel(PolicyT
     // 4b + 3, its bins and g two blocks ahead (a ring of three indexed by the
     // unrolled block).  dh stays in registers for B's dW1.  gpar = gi & 1.
     auto dh_gh = [&](int gi, int gpar, f32x16s (&hk)[2], f32x16s (&dh)[2]) {
-      const int mb = 2 * kImg * gpar;  // the masks of slot gpar, read as f16 (rbm holds L_MK)
-      const float *gv = lf + F_G + 192 * gpar;
+      // (epoch-0 build: gpar is the group's mask slot gi & 3, its g and g (x)
+      // H1 slot gi & 1)
+      const int mb = kMaskSlot * gpar;  // the masks of slot gpar, read as f16 (rbm holds L_MK)
+      const float *gv = lf + F_G + 192 * SP8_GSLOT(gpar);
       const float *xv = lf + F_X + (gi & 3) * 128;
       const float b1 = b1_of(gi);
       f16x8 A[2];
@@ -1364,7 +1476,7 @@ __global__ __launch_bounds__(kThreads, 2) void policy_train_spec8_kernel(PolicyT
             if (!XH_SP8_GH2) split2h_x2(x[2], x[3], ph[1], pl[1]);
             break;
           default: {
-            const int o2 = vwb[q] + 1024 * t;
+            const int o2 = vwb[q] + 1024 * t + kGhSlot * SP8_GSLOT(gpar);
             st4h(o2, __builtin_bit_cast(f16x4, u32x2{ph[0], ph[1]}));
             st4h(o2 + kImg, __builtin_bit_cast(f16x4, u32x2{pl[0], pl[1]}));
           }
@@ -1433,12 +1545,36 @@ __global__ __launch_bounds__(kThreads, 2) void policy_train_spec8_kernel(PolicyT
 
     f32x16s hk[2], dh[2];
     if (XH_SP8_PRIO >> 2) __builtin_amdgcn_s_setprio(XH_SP8_PRIO >> 2);
+    // (epoch-0 build: the H1 image's only reader, layer 2, does not exist;
+    // the vector waves run no layer 1, here or in the loop)
     __syncthreads();  // P1: rows staged
+#if !XH_SP8_E0_TU
     layer1(0);
+#endif
     __syncthreads();  // P2                       (matrix: L2(0))
     __syncthreads();  // P3
+#if !XH_SP8_E0_TU
     layer1(1);
+#endif
     __syncthreads();  // P4                       (matrix: SM(0))
+#if XH_SP8_E0_TU
+    // one phase per group (the matrix path's comment): DH(j) + g (x) H1(j),
+    // then dW1(j) from the registers
+    auto period = [&](int j, auto Q) {
+      constexpr int q = decltype(Q)::value;
+      dh_gh(j, q, hk, dh);
+      FENCE();  // (DH's slots stay as written: dW1's loads are not hoisted into them)
+      dw1(j, q & 1, hk, dh);
+      __syncthreads();  // P(j)
+    };
+    for (int j = 0; j < J; j += 4) {
+      period(j, Par<0>{});
+      if (j + 1 < J) period(j + 1, Par<1>{});
+      if (j + 2 < J) period(j + 2, Par<2>{});
+      if (j + 3 < J) period(j + 3, Par<3>{});
+    }
+    __syncthreads();  // the matrix waves' DW(J-1)
+#else
     auto period = [&](int j, auto P) {
       constexpr int par = decltype(P)::value;
       if (SP8_RUN(2 | 4)) dh_gh(j, par, hk, dh);
@@ -1451,6 +1587,7 @@ __global__ __launch_bounds__(kThreads, 2) void policy_train_spec8_kernel(PolicyT
       period(j, Par<0>{});
       if (j + 1 < J) period(j + 1, Par<1>{});
     }
+#endif
 
 #if XH_SP8_KL_TU
     __syncthreads();  // the matrix waves' KL sum

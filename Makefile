@@ -23,7 +23,7 @@ OBJS     := $(SRC)/policy_kernels.o $(SRC)/value_kernels.o \
             $(SRC)/stats_kernels.o $(SRC)/clip_kernels.o \
             $(SRC)/diag_kernels.o \
             $(SRC)/train_select.o $(SRC)/model_api.o $(SRC)/tensor_api.o \
-            $(SRC)/xylo_hip.o
+            $(SRC)/xylo_hip.o $(SRC)/digest_kernels.o $(SRC)/state_api.o
 # superseded train kernels (the config-3 / config-5
 # epoch's earlier forms), kept for A/B runs in the variant library only
 VARIANT_KERNELS := policy_split_kernels policy_split128_kernels \
@@ -32,6 +32,7 @@ VARIANT_KERNELS := policy_split_kernels policy_split128_kernels \
 HDRS     := $(SRC)/xh_device.h $(SRC)/xh_kernels.h $(SRC)/xh_split.h \
             $(SRC)/spec8_layout.h $(SRC)/spec8_e0_layout.h $(SRC)/xh_opt.h $(SRC)/xh_clip.h \
             $(SRC)/xh_diag.h $(SRC)/xh_sums.h \
+            $(SRC)/xh_digest.h $(SRC)/xh_state_blob.h $(SRC)/xh_trainer.h \
             $(SRC)/xh_host.h include/xylo_hip.h
 
 # Drop-in C++20 layer (include/xylo_compat): the reference's unmodified
@@ -101,6 +102,9 @@ $(SRC)/model_api.o: $(SRC)/model_api.cpp $(HDRS)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
 $(SRC)/tensor_api.o: $(SRC)/tensor_api.cpp $(HDRS)
+	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+
+$(SRC)/state_api.o: $(SRC)/state_api.cpp $(HDRS)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
 # the variant library: the product objects + the superseded train kernels,

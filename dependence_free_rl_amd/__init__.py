@@ -14,12 +14,18 @@ from ._lib import (STAT_ADV_SQSUM, STAT_ADV_SUM, STAT_COUNT,  # noqa: F401
 from ._lib import (UPD_CLIPPED, UPD_COUNT, UPD_ENTROPY_SUM,  # noqa: F401
                    UPD_K3_SUM, UPD_KL_SUM, UPD_LEARN, UPD_LOGR_SQSUM,
                    UPD_LOGR_SUM, UPD_ROWS, UPD_SURR_SUM)
+from ._lib import (DIG_COUNT, DIG_ENV_BINS, DIG_ENV_ITEMS,  # noqa: F401
+                   DIG_KL_BETA, DIG_POLICY_OPT_M, DIG_POLICY_OPT_V,
+                   DIG_POLICY_PARAMS, DIG_RNG, DIG_VALUE_OPT_M,
+                   DIG_VALUE_OPT_V, DIG_VALUE_PARAMS, STATE_ALL, STATE_NETS,
+                   STATE_VERSION)
 from .trainer import (ALGOS, POLICY, VALUE, Context, Trainer,  # noqa: F401
-                      clip_grad_norm, heuristic_evaluate, init_full_policy,
+                      clip_grad_norm, describe_state, digest,
+                      heuristic_evaluate, init_full_policy,
                       init_policy, init_value,
                       policy_param_count, value_param_count)
 from .venv import VecEnv  # noqa: F401
 
 __all__ = ["Context", "Trainer", "POLICY", "VALUE", "init_policy", "init_value",
-           "init_full_policy", "clip_grad_norm",
+           "init_full_policy", "clip_grad_norm", "describe_state", "digest",
            "heuristic_evaluate", "XhError", "runtime_info", "device_count", "VecEnv"]

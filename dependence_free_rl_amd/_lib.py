@@ -33,6 +33,15 @@ OPTIMIZERS = {"sgd": 0, "momentum": 1, "adam": 2}
 # xh_trainer_set_update_diag)
 (UPD_LEARN, UPD_ROWS, UPD_LOGR_SUM, UPD_LOGR_SQSUM, UPD_K3_SUM, UPD_CLIPPED,
  UPD_SURR_SUM, UPD_ENTROPY_SUM, UPD_KL_SUM, UPD_COUNT) = range(10)
+# trainer-state checkpoints (xh_trainer_save_state / load_state): the blob
+# version, what a load restores (the XH_STATE_* enum) and the entries of
+# xh_trainer_state_digest (the XH_DIG_* enum)
+STATE_VERSION = 1
+STATE_ALL, STATE_NETS = 0, 1
+(DIG_POLICY_PARAMS, DIG_VALUE_PARAMS, DIG_POLICY_OPT_M, DIG_POLICY_OPT_V,
+ DIG_VALUE_OPT_M, DIG_VALUE_OPT_V, DIG_ENV_BINS, DIG_ENV_ITEMS, DIG_RNG,
+ DIG_KL_BETA, DIG_COUNT) = range(11)
+STATE_HEADER_BYTES = 144
 
 
 class XhError(RuntimeError):
@@ -155,6 +164,12 @@ def _load():
         "xh_tensor_reduce": (i, [vp, i, vp, vp, C.c_float, sz, i,
                                  C.POINTER(C.c_double),
                                  C.POINTER(C.c_int64)]),
+        "xh_trainer_state_bytes": (sz, [vp]),
+        "xh_trainer_save_state": (i, [vp, vp, sz, C.POINTER(sz)]),
+        "xh_trainer_load_state": (i, [vp, vp, sz, i]),
+        "xh_state_describe": (i, [vp, sz, C.c_char_p, sz]),
+        "xh_trainer_state_digest": (i, [vp, C.POINTER(C.c_uint64)]),
+        "xh_digest_host": (i, [vp, sz, C.POINTER(C.c_uint64)]),
     }
     for name, (res, args) in sig.items():
         f = getattr(lib, name)
@@ -187,6 +202,10 @@ if lib.xh_struct_size(b"xh_upd_row") != UPD_COUNT * 8:
     raise ImportError("UPD_* indices are out of date (%d entries, the library "
                       "has %d)" % (UPD_COUNT,
                                    lib.xh_struct_size(b"xh_upd_row") // 8))
+if lib.xh_struct_size(b"xh_state_header") != STATE_HEADER_BYTES:
+    raise ImportError("the state blob's header has %d bytes in the library, %d "
+                      "here" % (lib.xh_struct_size(b"xh_state_header"),
+                                STATE_HEADER_BYTES))
 
 
 def check(status):

@@ -583,6 +583,29 @@ hipError_t launch_clip_step(const double *part, double r, float max_norm,
                             int n, OptStep o, float *scaled, double *log,
                             hipStream_t s);
 
+// The state digest of up to kDigestMaxEntries device arrays in one launch
+// pair (digest_kernels.hip; xh_trainer_state_digest, xh_trainer_load_state):
+// out[k] = sum_i splitmix64((i << 32) | word_i) mod 2^64 over the 32-bit words
+// of e[k] (xh_digest.h), 0 for an empty entry.  An entry may start at any byte
+// address and have any byte count; nothing outside [ptr, ptr + bytes) is read.
+// ws: kDigestWsWords uint64 of device workspace -- the workgroup partials
+// [kDigestMaxEntries][kDigestBlocks], then the kDigestMaxEntries results.
+constexpr int kDigestMaxEntries = 10;  // XH_DIG_COUNT
+constexpr int kDigestBlocks = 128;
+constexpr int kDigestWsWords = kDigestMaxEntries * (kDigestBlocks + 1);
+struct DigestTable {
+  struct {
+    const void *ptr;
+    unsigned long long bytes;
+  } e[kDigestMaxEntries];
+  int n;
+};
+inline unsigned long long *digest_results(unsigned long long *ws) {
+  return ws + kDigestMaxEntries * kDigestBlocks;
+}
+hipError_t launch_digest(const DigestTable &tab, unsigned long long *ws,
+                         hipStream_t s);
+
 // xylo/tensor.{h,cc} arithmetic on device arrays (tensor_kernels.hip; the
 // drop-in tensor type's device tensors and large host operations).
 enum TensorMapOp {

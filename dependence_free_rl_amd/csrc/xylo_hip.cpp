@@ -27,6 +27,7 @@
 #include "spec8_e0_layout.h"
 #include "xh_host.h"
 #include "xh_kernels.h"
+#include "xh_trainer.h"
 
 using namespace xh::host;
 
@@ -53,172 +54,6 @@ void ctx_free(xh_ctx *c) {
   delete c;
 }
 }  // namespace
-
-struct timed_event {
-  std::string name;
-  hipEvent_t start, stop;
-};
-
-struct xh_trainer {
-  xh_ctx *ctx = nullptr;
-  xh_config cfg{};
-  xh::EnvDesc env{};
-  xh::PolicyLayout pl{};
-  xh::ValueLayout vl{};
-  int np = 0, nv = 0;
-  // trajectory batch
-  int8_t *bins = nullptr, *items = nullptr;
-  int32_t *action = nullptr, *forced = nullptr;
-  float *pold = nullptr;
-  uint8_t *done = nullptr;
-  uint32_t *rng = nullptr;
-  // parameters and learner buffers
-  float *pp = nullptr, *vp = nullptr;
-  float *v_state = nullptr, *v_state0 = nullptr, *v_term = nullptr;
-  float *targets = nullptr, *adv = nullptr;
-  float *row_g = nullptr;               // [T*N] dL/dV of the value step
-  float *vact[2] = {nullptr, nullptr};  // value layer 1 / 2 outputs
-  float *vgr[2] = {nullptr, nullptr};   // their dL/d(pre-activation)
-  float *pslab = nullptr, *vslab = nullptr;
-  float *vw0red = nullptr;  // value layer 0 on the reduced observation
-  uint8_t *vw0frag = nullptr;  // W0's bf16 fragments (value_net_kernels.hip)
-  // vw0frag holds the fragments of the current value parameters (set by a
-  // bf16 value forward, cleared by every write of vp): the next iteration's
-  // first forward then skips the preparation launch
-  bool vfrag_ready = false;
-  // PPO's epoch 0 on the rollout's forward outputs (DESIGN.md §3.0e;
-  // policy_train_spec8_e0_kernel).  The buffers exist only for a trainer that
-  // can use them (PPO, epochs >= 2, 64 bins 2-D [128,128], split kernels):
-  // e0_mask [T][N] relu-mask records of 1 KB, e0_p [T][N][64] distributions
-  // (qold itself where the trainer records them anyway).  e0_valid: they are
-  // this window's forward outputs under the current policy parameters -- set
-  // by a rollout that ran rollout_split_kernel over all T slots with both
-  // outputs, cleared by wrote() on every write of the policy parameters and
-  // every host write into the batch.
-  uint32_t *e0_mask = nullptr;
-  float *e0_p = nullptr;
-  bool e0_valid = false;
-  int pslab_stride = 0, vslab_stride = 0, pslab_n = 0, vslab_n = 0;
-  float *pgrads = nullptr, *vgrad = nullptr;
-  float *logits = nullptr, *probs = nullptr;
-  double *adv_part = nullptr, *adv_stats = nullptr;  // adv_normalize
-  float *g_bound = nullptr;  // the learn()'s bound on the loss gradient g
-  // KL-PPO state
-  float *qold = nullptr, *beta = nullptr, *kl_log = nullptr;
-  int *end_list = nullptr, *n_end = nullptr, *n_open = nullptr;
-  int *vrows = nullptr;  // device: (T+1)N + n_end rows of the first V batch
-  int *end_scratch = nullptr;  // launch_end_list_par's block totals
-  double *kl_part = nullptr, *kl_sum = nullptr;
-  // optimizers of the policy [0] and value [1] nets (nn.h:589-698)
-  struct opt_state {
-    int kind = XH_OPT_SGD;
-    float lr = 0, wd = 0, beta1 = 0.9f, beta2 = 0.999f;
-    float t = 1.0f;                    // adam_optimizer::t (nn.h:694)
-    float *m = nullptr, *v = nullptr;  // velocity / moments (device)
-  } opt[2];
-  // REINFORCE (XH_PG): full-MLP policy buffers and episode bookkeeping
-  struct pg_state {
-    int nlayers = 0, w[4] = {0, 0, 0, 0};
-    float *act[3] = {nullptr, nullptr, nullptr};
-    float *grad[3] = {nullptr, nullptr, nullptr};
-    int *ep_done = nullptr, *len = nullptr, *active = nullptr;
-    int *row_off = nullptr, *list = nullptr, *nrows = nullptr;
-    float *rtg = nullptr;
-    double *ep_part = nullptr, *stats = nullptr;
-    int *host_active = nullptr;  // pinned
-    int slot_end = 0;            // slot holding the envs' current states
-  } pg;
-  // xh_trainer_set_stats (opt-in; everything null / 0 while off): the device
-  // ring of rows, the envs' running episode lengths, the kernels' workgroup
-  // partials and the three gradient norms; rows = rows opened so far; open =
-  // the last row's window is not consumed yet (learn() fills its learner part)
-  struct stats_state {
-    int history = 0;
-    long rows = 0;
-    bool open = false;
-    double *ring = nullptr, *part = nullptr, *norms = nullptr;
-    int *ep_len = nullptr;
-  } stats;
-  // xh_trainer_set_grad_clip of the policy [0] and value [1] nets (opt-in;
-  // null / 0 while off): one device block per net holding the workgroup
-  // partials of the sum of squares (kClipMaxParts doubles) and then the log,
-  // {norm, scale} per optimizer step of a learn(); learned = a learn() has
-  // filled the log since the clip was set
-  struct clip_state {
-    float max_norm = 0.0f;
-    double *part = nullptr, *log = nullptr;
-    bool learned = false;
-  } clip[2];
-  // xh_trainer_set_update_diag (opt-in; everything null / 0 while off): one
-  // device block holding the ring of rows, the sum kernel's workgroup partials
-  // and the per-row records [T][N] of the last probed learn() (ent, kl, then
-  // p_new); learns = learn() calls since it was set, rows = probed ones (ring
-  // rows written); info / kl_source = what the last probed learn() ran
-  struct upd_state {
-    int history = 0, every = 1;
-    long learns = 0, rows = 0;
-    double *ring = nullptr, *part = nullptr, *ent = nullptr, *kl = nullptr;
-    float *p_new = nullptr;
-    xh::KernelInfo info;
-    const char *kl_source = nullptr;
-  } upd;
-  int Tb = 0;  // Batch steps: cfg.steps, or REINFORCE's per-iteration bound
-  uint32_t jump_mul = 1;
-  int rgrid = 0;
-  bool need_shift = false;
-  // a rollout window exists that no learn() / forget() has consumed yet
-  // (xh_trainer_forget refuses to shift without one)
-  bool rolled = false;
-  // XH_BUF_LOGITS / XH_BUF_PROBS hold a recorded rollout step
-  bool last_step_recorded = false;
-  // xh_trainer_set_env_state: states the next rollout starts from, keyed by
-  // env (B*D bin bytes then D item bytes), applied after the forget() shift
-  std::map<int, std::vector<int8_t>> env_override;
-  bool use_forced = false;
-  // Slots of `items` whose every env holds an item-table entry.  The train
-  // kernels fold the item's layer-1 contribution into per-table-entry biases,
-  // so learn() refuses a batch that reads a slot with any other item
-  // (xh_trainer_set_buffer accepts them for rollout-only use).
-  std::vector<char> items_ok;
-  // Slots of `bins` that may hold a bin below -capacity (an overflowed state
-  // the reference reaches by applying to a game-over env again, bin_packing.h:
-  // 53-63, uploaded by hand).  The f16-pair kernels bound every observation
-  // feature by |bins / capacity| <= 1, so a rollout step
-  // or learn() that reads such a slot runs the f32-MFMA kernels instead.
-  std::vector<char> bins_wide;
-  // what the last rollout step / policy epoch launched (xh_trainer_kernel_info)
-  xh::KernelInfo last_rollout, last_train;
-  int timing = 0;  // 0 off, 1 every launch, XH_TIMING_TRAIN policy_train only
-  bool counted = false;  // holds a reference on ctx
-  std::vector<timed_event> events;
-  std::vector<hipEvent_t> event_pool;  // recycled by reset_timing
-  std::vector<void *> allocs;
-
-  xh::Batch batch() const {
-    xh::Batch b;
-    b.N = cfg.num_envs;
-    b.T = Tb;
-    b.bins = bins;
-    b.items = items;
-    b.action = action;
-    b.pold = pold;
-    b.done = done;
-    b.rng = rng;
-    return b;
-  }
-  xh::ValueArgs vargs() const {
-    xh::ValueArgs a{};
-    a.env = env;
-    a.b = batch();
-    a.v_state = v_state;
-    a.v_term = v_term;
-    a.row_g = row_g;
-    return a;
-  }
-  size_t N() const { return (size_t)cfg.num_envs; }
-  size_t T() const { return (size_t)Tb; }
-  size_t BD() const { return (size_t)cfg.bins * cfg.dims; }
-};
 
 // N vectorised envs for a caller's own policy (xh_venv_*, venv_kernels.hip).
 struct xh_venv {
@@ -392,7 +227,6 @@ constexpr uint64_t kEvalStride = 1ull << 26;  // draws between env streams
 // row groups one policy-train workgroup sums into its gradient slab at most
 // (= BASELINE configs 3 and 5 per GPU: 131072 groups over 256 workgroups)
 constexpr int kMaxTrainDepth = 512;
-constexpr int kBinCapacity = 8;             // bin_packing.h:48, every dim
 constexpr int kMaxStatsRows = 1 << 20;      // xh_trainer_set_stats: 151 MB
 constexpr int kMaxUpdRows = 1 << 20;        // xh_trainer_set_update_diag: 75 MB
 
@@ -523,16 +357,7 @@ xh::OptStep opt_step(xh_trainer *t, int which) {
   return st;
 }
 
-// Every write of a net's parameters and every host write into the batch (or
-// into what the next rollout starts from) says so here, before it is issued:
-// what was derived from the old contents is stale -- the value net's W0
-// fragments (vfrag_ready), the rollout's forward outputs that PPO's epoch 0
-// reuses (e0_valid).
-enum { kWrotePolicy = 1, kWroteValue = 2, kWroteBatch = 4 };
-void wrote(xh_trainer *t, int what) {
-  if (what & kWroteValue) t->vfrag_ready = false;
-  if (what & (kWrotePolicy | kWroteBatch)) t->e0_valid = false;
-}
+// wrote() (xh_trainer.h): every write of a net's parameters says so first
 int wrote_net(int which) { return which == XH_POLICY ? kWrotePolicy : kWroteValue; }
 
 int opt_apply(xh_trainer *t, int which, float *params, const float *grad,
@@ -1573,6 +1398,8 @@ size_t xh_struct_size(const char *name) {
   if (!std::strcmp(name, "xh_layer")) return sizeof(xh_layer);
   if (!std::strcmp(name, "xh_stat_row")) return XH_STAT_COUNT * sizeof(double);
   if (!std::strcmp(name, "xh_upd_row")) return XH_UPD_COUNT * sizeof(double);
+  if (!std::strcmp(name, "xh_state_header")) return sizeof(xh_state_header);
+  if (!std::strcmp(name, "xh_state_section")) return sizeof(xh_state_section);
   return 0;
 }
 

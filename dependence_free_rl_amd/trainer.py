@@ -274,6 +274,38 @@ def clip_grad_norm(ctx, grad, max_norm):
     return g, norm.value, np.float32(scale.value)
 
 
+# Trainer.state_digest()'s keys, in XH_DIG_* order
+DIGEST_NAMES = ("policy_params", "value_params", "policy_opt_m",
+                "policy_opt_v", "value_opt_m", "value_opt_v", "env_bins",
+                "env_items", "rng", "kl_beta")
+
+
+def digest(buf):
+    """The state digest of a bytes-like object or numpy array
+    (xh_digest_host): sum over its 32-bit little-endian words w_i of
+    splitmix64((i << 32) | w_i) mod 2^64, a byte tail zero-padded.  What
+    Trainer.state_digest() gives for the same bytes in device memory."""
+    a = np.ascontiguousarray(buf) if isinstance(buf, np.ndarray) else \
+        np.frombuffer(bytes(buf), np.uint8)
+    out = C.c_uint64()
+    check(_lib.lib.xh_digest_host(_ptr(a) if a.nbytes else None, a.nbytes,
+                                  C.byref(out)))
+    return int(out.value)
+
+
+def describe_state(blob):
+    """A state blob's header and section table as a dict (xh_state_describe;
+    host only, no device): {"version", "bytes", "config": {...}, "sections":
+    [{"id", "name", "bytes", "digest"}, ...]}.  XhError (status 1) for a
+    malformed or corrupted blob."""
+    import json
+    a = np.frombuffer(bytes(blob), np.uint8)
+    buf = C.create_string_buffer(4096)
+    check(_lib.lib.xh_state_describe(_ptr(a) if a.size else None, a.size, buf,
+                                     len(buf)))
+    return json.loads(buf.value.decode())
+
+
 def policy_param_count(dims, h1, h2):
     f0 = 2 * dims
     return h1 * f0 + h1 + h2 * h1 + h2 + h2 + 1
@@ -682,6 +714,71 @@ class Trainer:
                 "entropy": col(_lib.UPD_ENTROPY_SUM) / n,
                 "kl": col(_lib.UPD_KL_SUM) / n,
             }
+
+    # ------------------------------------------------------- checkpoints --
+    def state(self):
+        """Everything the run has learned or consumed as one bytes object
+        (xh_trainer_save_state): parameters, optimizer state, KL-PPO's beta,
+        the env engine states, the states the next rollout starts from and,
+        with statistics on, the running episode lengths.  Between iterations
+        only: XhError (status 4) after a rollout() that no learn() / forget()
+        has consumed.  Synchronises."""
+        n = _lib.lib.xh_trainer_state_bytes(self.h)
+        buf = np.zeros(n, np.uint8)
+        got = C.c_size_t()
+        check(_lib.lib.xh_trainer_save_state(self.h, _ptr(buf), n,
+                                             C.byref(got)))
+        return buf[:got.value].tobytes()
+
+    def set_state(self, blob, nets_only=False):
+        """Restore a state() blob (xh_trainer_load_state).  A run restored
+        into a new trainer continues with the bits of the run that was never
+        interrupted.  The shapes must match (XhError status 1 naming the
+        field); a blob of a global batch restores into a shard trainer, which
+        takes its env range.  nets_only: parameters, optimizers and beta only
+        (another num_envs / steps is fine; envs and streams are untouched).
+        All-or-nothing: a refused blob leaves the trainer as it was."""
+        buf = np.frombuffer(bytes(blob), np.uint8)
+        what = _lib.STATE_NETS if nets_only else _lib.STATE_ALL
+        check(_lib.lib.xh_trainer_load_state(self.h, _ptr(buf), buf.size, what))
+
+    def save_state(self, path):
+        """state() into `path`, atomically: a temporary file in the same
+        directory, then os.replace."""
+        import os
+        import tempfile
+        blob = self.state()
+        fd, tmp = tempfile.mkstemp(prefix=os.path.basename(path) + ".",
+                                   suffix=".tmp",
+                                   dir=os.path.dirname(os.path.abspath(path)))
+        try:
+            with os.fdopen(fd, "wb") as f:
+                f.write(blob)
+                f.flush()
+                os.fsync(f.fileno())
+            os.replace(tmp, path)
+        except BaseException:
+            try:
+                os.unlink(tmp)
+            except OSError:
+                pass
+            raise
+
+    def load_state(self, path, nets_only=False):
+        """set_state() of the file save_state() wrote."""
+        with open(path, "rb") as f:
+            self.set_state(f.read(), nets_only=nets_only)
+
+    def state_digest(self):
+        """{name: int} 64-bit digests of the state arrays as they lie in
+        device memory (xh_trainer_state_digest; one launch pair,
+        synchronises): equal digests on two trainers (two ranks) mean equal
+        bits.  0 for arrays the trainer does not have (sgd's moments, beta
+        outside KL-PPO).  XhError (status 4) while set_env_state overrides are
+        pending."""
+        out = (C.c_uint64 * _lib.DIG_COUNT)()
+        check(_lib.lib.xh_trainer_state_digest(self.h, out))
+        return {name: int(out[k]) for k, name in enumerate(DIGEST_NAMES)}
 
     # ------------------------------------------------------------ timing --
     def set_timing(self, on):

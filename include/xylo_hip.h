@@ -468,6 +468,134 @@ int xh_trainer_get_update_diag_rows(xh_trainer *t, float *p_new, double *entropy
  * learn() ran (kernel null before the first). */
 int xh_trainer_update_diag_info(xh_trainer *t, char *buf, size_t cap);
 
+/* ------------------------------------------------------ trainer state ---- */
+/* Everything a run has learned or consumed, as one flat buffer: a run that is
+ * saved, destroyed, restored into a new trainer and continued produces the
+ * bits of the run that was never interrupted (every sum of rollout() and
+ * learn() is formed in a fixed order).  Opt-in: without these calls rollout()
+ * and learn() launch what they launch without them and nothing is allocated.
+ *
+ * STATE (saved and restored):
+ *   - both nets' flat parameters (XH_PG: the policy only);
+ *   - per net the optimizer as xh_trainer_set_optimizer and
+ *     xh_trainer_set_learning_rate left it: kind, lr, weight decay, beta1,
+ *     beta2, the step counter t, and the device velocity / moments (absent
+ *     for sgd);
+ *   - XH_KLPPO's adaptive beta;
+ *   - the [N] per-env engine states (XH_BUF_RNG);
+ *   - the env states the next rollout starts from, [N][B][D] bins and [N][4]
+ *     items, resolved as xh_trainer_get_env_state resolves them (slot T after
+ *     a learn(), slot 0 otherwise, pending xh_trainer_set_env_state overrides
+ *     applied; XH_PG: the slot its last rollout ended in);
+ *   - the running episode lengths behind XH_STAT_EPLEN_*, while statistics
+ *     are on (the section is absent while they are off).
+ * SETTINGS (stay the loading trainer's own): the hyperparameter fields of
+ * xh_config (gamma, lambda, clip_eps, kl_target, adv_normalize,
+ * lr_scale_rows, the record_* flags), the gradient-clip thresholds, the
+ * statistics and update-diagnostics rings with their row counters
+ * (XH_STAT_ITER and the `every` phase restart in a new trainer), timing and
+ * forced actions.
+ *
+ * THE BLOB: little-endian, written to a file as it is.
+ *   [0, 144)       xh_state_header: magic "XHS1", version, its own size, the
+ *                  section count, the blob's total byte count, the digest of
+ *                  the payload = bytes [144, total_bytes), and the saving
+ *                  trainer's xh_config
+ *   [144, ...)     the section table: `sections` x xh_state_section {id,
+ *                  offset from the blob's start, bytes, digest of those
+ *                  bytes}, ids strictly increasing
+ *   then           the sections, each starting at a multiple of 16 (zero
+ *                  padding between them)
+ * Section ids 0 .. XH_DIG_COUNT - 1 are the XH_DIG_* arrays below, copied as
+ * they lie in device memory (f32 parameters and moments, int8 bins and items,
+ * uint32 engine states, f32 beta); XH_SEC_OPT: for the policy then the value
+ * net {int32 kind, f32 lr, wd, beta1, beta2, t, 2 x uint32 0}; XH_SEC_EP_LEN:
+ * int32 [N].
+ *
+ * THE DIGEST of a buffer, over its 32-bit little-endian words w_i (a byte tail
+ * zero-padded to a word), i = 0, 1, ...:
+ *   digest = sum_i splitmix64(((uint64)i << 32) | w_i)   mod 2^64
+ *   splitmix64(x): x += 0x9E3779B97F4A7C15; x = (x ^ (x >> 30)) *
+ *   0xBF58476D1CE4E5B9; x = (x ^ (x >> 27)) * 0x94D049BB133111EB;
+ *   return x ^ (x >> 31)
+ * The sum depends on every word's position (swapping two different words
+ * changes it) but not on the order of the additions, which are integers mod
+ * 2^64: the device forms it in a reduction tree (digest_kernels.hip),
+ * xh_digest_host in a loop, with the same result.  It detects corruption and
+ * misplaced writes; it is not a cryptographic hash. */
+#define XH_STATE_VERSION 1
+#define XH_STATE_MAGIC 0x31534858u /* "XHS1" */
+enum { XH_STATE_ALL = 0, XH_STATE_NETS = 1 };
+typedef struct {
+  uint32_t magic, version, header_bytes, sections;
+  uint64_t total_bytes, payload_digest;
+  xh_config cfg;
+  uint32_t reserved; /* 0 */
+} xh_state_header;   /* 144 bytes: xh_struct_size("xh_state_header") */
+typedef struct {
+  uint32_t id, reserved; /* reserved: 0 */
+  uint64_t offset, bytes, digest;
+} xh_state_section;  /* 32 bytes: xh_struct_size("xh_state_section") */
+
+enum { XH_DIG_POLICY_PARAMS = 0, XH_DIG_VALUE_PARAMS = 1,
+       XH_DIG_POLICY_OPT_M = 2, XH_DIG_POLICY_OPT_V = 3,
+       XH_DIG_VALUE_OPT_M = 4, XH_DIG_VALUE_OPT_V = 5, XH_DIG_ENV_BINS = 6,
+       XH_DIG_ENV_ITEMS = 7, XH_DIG_RNG = 8, XH_DIG_KL_BETA = 9,
+       XH_DIG_COUNT };
+/* blob sections that are no device array of the digest call */
+enum { XH_SEC_OPT = 10, XH_SEC_EP_LEN = 11, XH_SEC_COUNT };
+
+/* Bytes xh_trainer_save_state writes for the trainer as it stands (it grows
+ * with a non-sgd optimizer and with statistics on).  0 for null. */
+size_t xh_trainer_state_bytes(const xh_trainer *t);
+/* Synchronises the trainer's stream and writes the blob into blob[cap];
+ * *written (may be NULL) = its size.  Only at an iteration boundary:
+ * XH_ERR_STATE while a rollout window exists that no learn() / forget() has
+ * consumed; a fresh trainer that has not rolled out yet can be saved.
+ * XH_ERR_INVALID when cap is too small. */
+int xh_trainer_save_state(xh_trainer *t, void *blob, size_t cap, size_t *written);
+/* Restores a blob.  All-or-nothing: the whole blob is validated before the
+ * first device write (magic, version, sizes against this trainer, every
+ * section's bounds, the payload digest, bin values <= capacity and items that
+ * are item-table entries, as xh_trainer_set_env_state checks them), and a
+ * refused load leaves the trainer exactly as it was.
+ *   what = XH_STATE_ALL: algo, bins, dims, steps, epochs, the four hidden
+ *     widths and num_envs_global must equal the trainer's (XH_ERR_INVALID
+ *     naming the first field that differs), and the blob's env slice
+ *     [env_offset, env_offset + num_envs) must cover the trainer's; of a
+ *     larger slice the trainer takes its own sub-range, so one checkpoint of
+ *     a global batch restores into the trainers of its shards.  With
+ *     statistics on, a blob without running episode lengths restarts them at
+ *     zero.  XH_ERR_STATE while an unconsumed rollout window exists.
+ *   what = XH_STATE_NETS: parameters, optimizers and beta only; the algo
+ *     family (XH_PG or not), bins, dims and the hidden widths must match.
+ *     Envs, engine states, episode lengths, num_envs and steps are untouched
+ *     (continuing with a larger batch; handing nets to an evaluation trainer).
+ * An accepted load uploads on the trainer's stream, drops pending
+ * xh_trainer_set_env_state overrides (the restored states replace them),
+ * allocates optimizer moments as xh_trainer_set_optimizer would, and then
+ * digests every restored array on the device and compares it with the blob's
+ * digest of it: XH_ERR_HIP naming the section on a mismatch (an upload that
+ * did not land as ordered). */
+int xh_trainer_load_state(xh_trainer *t, const void *blob, size_t bytes, int what);
+/* Host only (no device, no trainer): parses a blob and writes one JSON object
+ * {"version", "bytes", "config": {the saved xh_config}, "sections": [{"id",
+ * "name", "bytes", "digest" (16 hex digits)}, ...]} NUL-terminated into
+ * buf[cap].  XH_ERR_INVALID for a malformed blob: too short, bad magic,
+ * unknown version, a section past the end, a payload digest mismatch. */
+int xh_state_describe(const void *blob, size_t bytes, char *buf, size_t cap);
+/* out[XH_DIG_COUNT] = the digests of the trainer's state arrays as they lie
+ * in device memory (one launch pair; synchronises): what load verifies, and
+ * what the ranks of a job compare to see that their replicated parameters and
+ * optimizer state hold the same bits, in 80 bytes.  Absent arrays give 0
+ * (sgd's moments, beta outside XH_KLPPO, the value net of an XH_PG trainer).
+ * XH_ERR_STATE while xh_trainer_set_env_state overrides are pending: the
+ * device does not hold those states yet. */
+int xh_trainer_state_digest(xh_trainer *t, uint64_t *out /* [XH_DIG_COUNT] */);
+/* The digest above of `bytes` bytes of host memory (data may be NULL for 0
+ * bytes: digest 0). */
+int xh_digest_host(const void *data, size_t bytes, uint64_t *out);
+
 /* ------------------------------------------------- vectorised envs ---- */
 /* N bp::environment instances (bin_packing.h:46-85, generalised to B bins /
  * D dims as the trainer's) whose state stays in HBM, for a caller that brings
@@ -692,7 +820,8 @@ int xh_tensor_transpose(xh_ctx *ctx, const float *in, float *out, int rows,
  * unknown), so a
  * foreign-language binding can check its mirror of them.  "xh_stat_row": the
  * bytes of one statistics row, XH_STAT_COUNT * 8; "xh_upd_row": of one
- * update-diagnostics row, XH_UPD_COUNT * 8. */
+ * update-diagnostics row, XH_UPD_COUNT * 8.  "xh_state_header" (144) and
+ * "xh_state_section" (32): the fixed parts of a state blob. */
 size_t xh_struct_size(const char *name);
 
 /* Kernel timing with HIP events on the trainer's stream (off by default).

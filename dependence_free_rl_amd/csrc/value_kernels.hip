@@ -46,7 +46,9 @@ __global__ __launch_bounds__(256) void gae_kernel(ValueArgs a, float gamma,
   // done bytes and the 9 values V(S_t0-7) .. V(S_t0+1)) issued before the
   // chunk's arithmetic and unconditionally (the terminal step's V(S_t+1) is
   // loaded and then not used), so one HBM round trip per chunk instead of
-  // two dependent ones per step; the arithmetic is unchanged (bit-identical)
+  // two dependent ones per step; the arithmetic is unchanged (bit-identical:
+  // tests/test_gpu_long_window.py against long_window_ref.gae_f32, which has
+  // no chunks)
   constexpr int C = 8;
   for (int env = blockIdx.x * blockDim.x + threadIdx.x; env < N;
        env += gridDim.x * blockDim.x) {

@@ -30,7 +30,8 @@ VARIANT_KERNELS := policy_split_kernels policy_split128_kernels \
             policy_split8w_kernels policy_split8wp_kernels \
             policy_split4p_kernels policy_split8wg_kernels
 HDRS     := $(SRC)/xh_device.h $(SRC)/xh_kernels.h $(SRC)/xh_split.h \
-            $(SRC)/spec8_layout.h $(SRC)/spec8_e0_layout.h $(SRC)/xh_opt.h $(SRC)/xh_clip.h \
+            $(SRC)/spec8_layout.h $(SRC)/spec8_e0_layout.h $(SRC)/spec8_l1_layout.h \
+            $(SRC)/xh_opt.h $(SRC)/xh_clip.h \
             $(SRC)/xh_diag.h $(SRC)/xh_sums.h \
             $(SRC)/xh_digest.h $(SRC)/xh_state_blob.h $(SRC)/xh_trainer.h \
             $(SRC)/xh_host.h include/xylo_hip.h
@@ -205,3 +206,27 @@ variant: $(OBJS)
 	$(HIPCC) $(HIPFLAGS) $(FLAGS_$(VSRC)) $(VFLAGS) -c $(SRC)/$(VSRC).hip -o build/$(V)/$(VSRC).o
 	$(HIPCC) --offload-arch=$(ARCH) -shared -o build/$(V)/libxylo_hip.so build/$(V)/$(VSRC).o \
 	    $(filter-out $(SRC)/$(VSRC).o,$(OBJS)) -L/opt/rocm/lib -lrccl -Wl,-rpath,/opt/rocm/lib
+
+# the config-3 epoch's three objects of policy_spec8_kernels.hip (plain,
+# KL-PPO, epoch 0) with XH_SP8_* switches turned, for the same A/B runs
+# (`variant` with VSRC=policy_spec8_kernels would rebuild the plain one only):
+#   make variant_spec8 V=l1pk0 VFLAGS="-DXH_SP8_L1PK=0"
+#   make variant_spec8 V=ghf_e0 VFLAGS="" VFLAGS_E0="-DXH_SP8_GHF=1"
+#     (VFLAGS_E0 / VFLAGS_KL: the epoch-0 / KL-PPO object's, default VFLAGS)
+VFLAGS_E0 ?= $(VFLAGS)
+VFLAGS_KL ?= $(VFLAGS)
+SP8_OBJS := $(SRC)/policy_spec8_kernels.o $(SRC)/policy_spec8_kl_kernels.o \
+            $(SRC)/policy_spec8_e0_kernels.o
+.PHONY: variant_spec8
+variant_spec8: $(OBJS)
+	@mkdir -p build/$(V)
+	$(HIPCC) $(HIPFLAGS) $(FLAGS_policy_spec8_kernels) $(VFLAGS) \
+	    -c $(SRC)/policy_spec8_kernels.hip -o build/$(V)/policy_spec8_kernels.o
+	$(HIPCC) $(HIPFLAGS) $(FLAGS_policy_spec8_kernels) $(VFLAGS_KL) -DXH_SP8_KL_TU=1 \
+	    -c $(SRC)/policy_spec8_kernels.hip -o build/$(V)/policy_spec8_kl_kernels.o
+	$(HIPCC) $(HIPFLAGS) $(FLAGS_policy_spec8_kernels) $(VFLAGS_E0) -DXH_SP8_E0_TU=1 \
+	    -c $(SRC)/policy_spec8_kernels.hip -o build/$(V)/policy_spec8_e0_kernels.o
+	$(HIPCC) --offload-arch=$(ARCH) -shared -o build/$(V)/libxylo_hip.so \
+	    build/$(V)/policy_spec8_kernels.o build/$(V)/policy_spec8_kl_kernels.o \
+	    build/$(V)/policy_spec8_e0_kernels.o $(filter-out $(SP8_OBJS),$(OBJS)) \
+	    -L/opt/rocm/lib -lrccl -Wl,-rpath,/opt/rocm/lib

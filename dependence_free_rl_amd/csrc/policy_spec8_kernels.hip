@@ -55,16 +55,20 @@
 // dW2 accumulators 64, layer-2 accumulators 32, dW3 / db2 sums 32; vector:
 // W2' pair 64, dH1 accumulators 32, two groups' H1 64).
 //
-// LDS (dynamic, base 0): g (x) H1 two f16 parts [128 i][64 r] (32 KB; three
-// bf16 parts, 48 KB, in the three-part form), H1 two f16 parts [64 r][128 i]
-// (32 KB), relu masks [64 r][128 o] (0x4000 = 2.0 as bf16 and as f16)
-// in two slots (32 KB apart, 16 KB used), then f32 vectors; image layout
-// spec8_layout.h.  (The epoch-0 build, XH_SP8_E0_TU below, has its own
-// schedule and LDS order.)
+// LDS (dynamic, base 0): the f32 vectors first (8 KB; 9 KB in the KL-PPO
+// build: their offsets are the ds instructions' immediates), then g (x) H1
+// two f16 parts [128 i][64 r] (32 KB; three bf16 parts, 48 KB, in the
+// three-part form), H1 two f16 parts [64 r][128 i] (32 KB), relu masks [64 r]
+// [128 o] (0x4000 = 2.0 as bf16 and as f16) in two packed slots of 16 KB: 104
+// KB in the f16-pair form; image layout spec8_layout.h.  (XH_SP8_LDSF=0: the
+// images first, the mask slots 32 KB apart, the f32 vectors behind them, 138
+// KB.  The epoch-0 build, XH_SP8_E0_TU below, has its own schedule and LDS
+// order.)
 #include <cstdlib>
 #include <type_traits>
 
 #include "spec8_e0_layout.h"
+#include "spec8_l1_layout.h"
 #include "spec8_layout.h"
 #include "xh_device.h"
 #include "xh_kernels.h"
@@ -176,6 +180,27 @@
 #ifndef XH_SP8_VBF
 #define XH_SP8_VBF 0
 #endif
+// XH_SP8_L1PK: 1 = layer 1 of the H1 image as ONE bf16 MFMA per r-tile, the
+// three exact bf16 parts of the five constants packed along K (slot 5 part +
+// input, spec8_l1_layout.h), 0 = three dependent MFMAs, one per part, each
+// using 5 of the 16 K slots.  (No layer 1 in the epoch-0 build.)
+#ifndef XH_SP8_L1PK
+#define XH_SP8_L1PK 1
+#endif
+// XH_SP8_GHF (A/B builds, f16-pair form): 1 = g (x) H1's f16 pair straight
+// from the two factors (split2h_x2g: four v_fma_mix per pair, the f32 product
+// never formed: two VALU fewer per block of four rows), 0 = four v_mul_f32 per
+// block and split2h_x2 of the products.  Measured slower in both the plain and
+// the epoch-0 launch ("measured and dropped"): off.
+#ifndef XH_SP8_GHF
+#define XH_SP8_GHF 0
+#endif
+// XH_SP8_LDSF (the builds with an H1 image; the epoch-0 build has its own
+// order): 1 = the f32 vectors first and the two mask slots packed, 0 = the
+// images first, the mask slots 2 kImg apart and the f32 vectors behind them
+#ifndef XH_SP8_LDSF
+#define XH_SP8_LDSF 1
+#endif
 // XH_SP8_VAF (A/B builds): 0 lets the compiler schedule the vector waves'
 // phase-A slots (g (x) H1) across the dH1 MFMAs
 #ifndef XH_SP8_VAF
@@ -217,6 +242,21 @@ constexpr int kGhSlot = kGhParts * kImg;
 constexpr int kMaskSlot = kImg;
 constexpr int L_MK = L_GH + 2 * kGhSlot;
 #define SP8_GSLOT(ms) ((ms) & 1)  // the g / g (x) H1 slot of the group in mask slot ms
+#elif XH_SP8_LDSF
+// (two phases per group: one g (x) H1 slot, the H1 image, the masks in two
+// slots, group j's in slot j & 1.  The f32 vectors first here too -- their
+// offsets are immediates, not addresses built in registers -- then g (x) H1,
+// below 64 KB with them, then H1 and the mask slots, packed: 104 KB in the
+// f16-pair form.  Every base is a multiple of 256 bytes: the images' bank
+// behaviour is that of spec8_layout.h at base 0.)
+constexpr int L_F = 0;
+constexpr int kFBytes = XH_SP8_KL_TU ? 9216 : 8192;
+constexpr int L_GH = kFBytes;      // g (x) H1: hi, lo (three-part form: hi, mid, lo)
+constexpr int kGhSlot [[maybe_unused]] = 0;  // (one g (x) H1 slot)
+constexpr int kMaskSlot = kImg;
+constexpr int L_H1 = L_GH + kGhParts * kImg;  // H1: hi, lo
+constexpr int L_MK = L_H1 + 2 * kImg;
+#define SP8_GSLOT(ms) (ms)
 #else
 constexpr int L_GH = 0;            // g (x) H1: hi, lo (three-part form: hi, mid, lo)
 constexpr int kGhSlot [[maybe_unused]] = 0;  // (one g (x) H1 slot)
@@ -250,6 +290,11 @@ constexpr int F_END = F_FU + kH;
 #if XH_SP8_E0_TU
 static_assert(sizeof(float) * F_END <= kFBytes, "the f32 vectors' region");
 constexpr size_t kLds = L_MK + 4 * kMaskSlot;
+#elif XH_SP8_LDSF
+static_assert(sizeof(float) * F_END <= kFBytes, "the f32 vectors' region");
+static_assert(kFBytes % 256 == 0 && L_GH % 256 == 0 && L_H1 % 256 == 0 && L_MK % 256 == 0,
+              "image bases: whole 256-byte rows");
+constexpr size_t kLds = L_MK + 2 * kMaskSlot;
 #else
 constexpr size_t kLds = L_F + sizeof(float) * F_END;
 #endif
@@ -991,10 +1036,11 @@ __global__ __launch_bounds__(kThreads, 2) void policy_train_spec8_kernel(PolicyT
     };
 #else
     auto dw2 = [&](int ms, auto &&task) {
-      const int mb = 2 * kImg * ms;  // (trM holds L_MK)
+      const int mb = kMaskSlot * ms;  // (trM holds L_MK)
       bf16x8 A[2], B[2][3];
       auto ldB = [&](int ks) {
-        const int ob = L_GH + 1024 * (ks >> 1) + ((ks & 1) ? rbg1 : rbg0);
+        // (rbg holds L_GH)
+        const int ob = 1024 * (ks >> 1) + ((ks & 1) ? rbg1 : rbg0);
         B[ks & 1][0] = ld8(ob);
         B[ks & 1][1] = ld8(ob + kImg);
         B[ks & 1][2] = ld8(ob + 2 * kImg);
@@ -1296,6 +1342,34 @@ __global__ __launch_bounds__(kThreads, 2) void policy_train_spec8_kernel(PolicyT
     };
 #if !XH_SP8_E0_TU
     // the layer-1 image (layer 2's f16-pair operand) from the matrix cores:
+#if XH_SP8_L1PK
+    // one A fragment: K slot 5 part + input holds part `part` of constant
+    // `input` (spec8_l1_layout.h), slots 8 h .. 8 h + 7 in lane half h
+    bf16x8 w1pk;
+    {
+      float ia = 0.0f, ib = 0.0f;
+#pragma unroll
+      for (int d = 0; d < kD; ++d) {
+        const float wv = P[PL.oW1() + fi * kF0 + kD + d];
+        ia += wv * ((float)a.env.item_a[d] / (float)kCapacity);
+        ib += wv * ((float)a.env.item_b[d] / (float)kCapacity);
+      }
+      const float bv[kL1Inputs] = {P[PL.oW1() + fi * kF0], P[PL.oW1() + fi * kF0 + 1],
+                                   P[PL.ob1() + fi], ia, ib};
+      unsigned short pb[kL1Parts][kL1Inputs];
+#pragma unroll
+      for (int e = 0; e < kL1Inputs; ++e) {
+        __bf16 y0, y1, y2;
+        split3(bv[e] * SH, y0, y1, y2);
+        pb[0][e] = __builtin_bit_cast(unsigned short, y0);
+        pb[1][e] = __builtin_bit_cast(unsigned short, y1);
+        pb[2][e] = __builtin_bit_cast(unsigned short, y2);
+      }
+#pragma unroll
+      for (int e = 0; e < 8; ++e)
+        w1pk[e] = __builtin_bit_cast(__bf16, h ? l1_a_elem(pb, 1, e) : l1_a_elem(pb, 0, e));
+    }
+#else
     bf16x8 w1p[3];
     {
       float ia = 0.0f, ib = 0.0f;
@@ -1317,8 +1391,9 @@ __global__ __launch_bounds__(kThreads, 2) void policy_train_spec8_kernel(PolicyT
       }
     }
 #endif
+#endif
     // image stores (lane row i, values r = 32 t + 8 q + 4 h ..; + 1024 t):
-    // the g (x) H1 image (region base 0) and the H1 image; dH1's A operand
+    // the g (x) H1 image (region base L_GH) and the H1 image; dH1's A operand
     // (the mask image read as f16, lane row r = 32 t + l31)
     int vwb[4];
 #pragma unroll
@@ -1338,9 +1413,37 @@ __global__ __launch_bounds__(kThreads, 2) void policy_train_spec8_kernel(PolicyT
 
 #if !XH_SP8_E0_TU
     // S_H pre-activations of layer 1 of group gi (its bins in slot gi & 3)
-    // for this wave's features: two r-tiles of three bf16 MFMAs with W1 as
-    // the A operand, C[i][r] (lane column r = 32 t + l31, registers i = 32 v
-    // + 8 q + 4 h + u): the [r][i] image's layout
+    // for this wave's features: two r-tiles of one bf16 MFMA (XH_SP8_L1PK=0:
+    // three, one per bf16 part) with W1 as the A operand, C[i][r] (lane
+    // column r = 32 t + l31, registers i = 32 v + 8 q + 4 h + u): the [r][i]
+    // image's layout
+#if XH_SP8_L1PK
+    // (packed form: ONE MFMA per r-tile over the 15 (part, input) slots; the
+    // hardware sums the 15 exact products in its own order, where the three
+    // MFMAs summed "small parts first": the pre-activations differ in the
+    // last places, and only layer 2 reads the image, rounding it to a 22-bit
+    // f16 pair.  g (x) H1 and dW1 keep the exact f32 chain.)
+    auto l1_mfma = [&](int gi, f32x16s (&pre)[2]) {
+      const int sl = gi & 3;
+      const bool ia =
+          __builtin_amdgcn_readfirstlane(__float_as_int(lf[F_REC + 4 * sl + 3])) != 0;
+      // X fragment (the B operand), lane column r = 32 t + l31, k = 8 h + e:
+      // the row's five inputs three times over (l1_x_word); both lane halves
+      // carry data
+      const float *xv = lf + F_X + sl * 128 + l31;
+#pragma unroll
+      for (int t = 0; t < 2; ++t) {
+        const unsigned xx = __builtin_bit_cast(
+            unsigned, bf16x2{(__bf16)xv[32 * t], (__bf16)xv[64 + 32 * t]});
+        typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+        u32x4 X;
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          X[j] = h ? l1_x_word(1, j, xx, ia) : l1_x_word(0, j, xx, ia);
+        pre[t] = mfma_bf16(w1pk, __builtin_bit_cast(bf16x8, X), f32x16s{});
+      }
+    };
+#else
     auto l1_mfma = [&](int gi, f32x16s (&pre)[2]) {
       const int sl = gi & 3;
       const bool ia =
@@ -1361,6 +1464,7 @@ __global__ __launch_bounds__(kThreads, 2) void policy_train_spec8_kernel(PolicyT
         pre[t] = mfma_bf16(w1p[0], X, pre[t]);
       }
     };
+#endif
     // B: layer 1 of group gi -> the H1 image (f16 pairs), block b = (t, q)
     // of four rows at a time; the values are recomputed where DH needs them
     auto layer1 = [&](int gi) {
@@ -1447,7 +1551,9 @@ __global__ __launch_bounds__(kThreads, 2) void policy_train_spec8_kernel(PolicyT
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
               hk[t][4 * q + u] = hv[u];
-              x[u] = hv[u] * o[2][u];
+              // (fused split: slots 1 and 2 take the two factors, hk and the
+              // ring's g, which block b + 3's loads overwrite only later)
+              if (XH_SP8_DW2_3P || !XH_SP8_GHF) x[u] = hv[u] * o[2][u];
             }
             if (b + 2 < 8) ld3(b + 2);
             break;
@@ -1467,6 +1573,19 @@ __global__ __launch_bounds__(kThreads, 2) void policy_train_spec8_kernel(PolicyT
             st4(o2 + 2 * kImg, __builtin_bit_cast(bf16x4, u32x2{pl[0], pl[1]}));
           }
 #else
+#if XH_SP8_GHF
+          // the scaled products as f16 pairs straight from the factors: 4
+          // VALU per pair and no v_mul_f32 before them, two stores
+          case 1:
+            split2h_x2g(hk[t][4 * q], o[2][0], hk[t][4 * q + 1], o[2][1], ph[0], pl[0]);
+            if (XH_SP8_GH2)
+              split2h_x2g(hk[t][4 * q + 2], o[2][2], hk[t][4 * q + 3], o[2][3], ph[1], pl[1]);
+            break;
+          case 2:
+            if (!XH_SP8_GH2)
+              split2h_x2g(hk[t][4 * q + 2], o[2][2], hk[t][4 * q + 3], o[2][3], ph[1], pl[1]);
+            break;
+#else
           // the scaled products as f16 pairs: 3 VALU per pair, two stores
           case 1:
             split2h_x2(x[0], x[1], ph[0], pl[0]);
@@ -1475,6 +1594,7 @@ __global__ __launch_bounds__(kThreads, 2) void policy_train_spec8_kernel(PolicyT
           case 2:
             if (!XH_SP8_GH2) split2h_x2(x[2], x[3], ph[1], pl[1]);
             break;
+#endif
           default: {
             const int o2 = vwb[q] + 1024 * t + kGhSlot * SP8_GSLOT(gpar);
             st4h(o2, __builtin_bit_cast(f16x4, u32x2{ph[0], ph[1]}));

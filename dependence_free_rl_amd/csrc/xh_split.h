@@ -236,6 +236,26 @@ __device__ __forceinline__ void split2h_x2s(float a0, float a1, float s, unsigne
       : "+v"(lo2)
       : "v"(a1), "v"(s), "v"(hi2));
 }
+// split2h of two products (a0 g0, a1 g1), packed, each with a factor of its
+// own (split2h_x2s's two-scale sibling; the factors need not be powers of
+// two): hi = the exact product a g rounded ONCE to f16 (v_fma_mixlo / mixhi_f16
+// of a g + 0), lo = a g - hi with hi read as f16, the fused difference rounded
+// once to f16.  Four instructions per pair; the f32 product is never formed,
+// so hi has no double rounding and lo is taken from the exact product: hi +
+// lo is at least as close to a g as split2h of the rounded f32 product
+// (tests/l1pack_check.cc restates both on the host).  The single rounding of
+// the fused result to f16 is assumed from the instruction's description, not
+// verified on the hardware; the GPU tests hold either way (the pair's error
+// bound does not depend on it).
+__device__ __forceinline__ void split2h_x2g(float a0, float g0, float a1, float g1,
+                                            unsigned &hi2, unsigned &lo2) {
+  asm("v_fma_mixlo_f16 %0, %1, %2, 0" : "=v"(hi2) : "v"(a0), "v"(g0));
+  asm("v_fma_mixhi_f16 %0, %1, %2, 0" : "+v"(hi2) : "v"(a1), "v"(g1));
+  asm("v_fma_mixlo_f16 %0, %1, %2, -%3 op_sel_hi:[0,0,1]" : "=v"(lo2) : "v"(a0), "v"(g0), "v"(hi2));
+  asm("v_fma_mixhi_f16 %0, %1, %2, -%3 op_sel:[0,0,1] op_sel_hi:[0,0,1]"
+      : "+v"(lo2)
+      : "v"(a1), "v"(g1), "v"(hi2));
+}
 // split2h of two values, packed: hi2 = {hi(x0), hi(x1)} (v_cvt_pk_f16_f32,
 // round to nearest), lo2 = {lo(x0), lo(x1)} by v_fma_mixlo / mixhi_f16:
 // x * 1 - hi with hi read as f16 (op_sel_hi) is exact in f32 and rounded once

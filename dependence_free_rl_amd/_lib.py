@@ -18,7 +18,13 @@ HEURISTICS = {"random": 0, "firstfit": 1, "bestfit": 2, "minwaste": 3}
 XH_POLICY, XH_VALUE = 0, 1
 OPTIMIZERS = {"sgd": 0, "momentum": 1, "adam": 2}
 (VENV_ACTIONS, VENV_REWARD, VENV_DONE, VENV_BINS, VENV_ITEMS, VENV_RNG,
- VENV_OBS, VENV_MASK) = range(8)
+ VENV_OBS, VENV_MASK, VENV_POLICY, VENV_PCHOICE) = range(10)
+# xh_venv_act: what the policy rows hold, how the bin is chosen
+ACT_PROBS, ACT_LOGITS = 0, 1
+ACT_SAMPLE, ACT_ARGMAX = 0, 1
+# the trajectory record's arrays (xh_venv_set_record)
+(VREC_ACTION, VREC_PCHOICE, VREC_REWARD, VREC_DONE, VREC_BINS, VREC_ITEMS,
+ VREC_COUNT) = range(7)
 (BUF_BINS, BUF_ITEMS, BUF_ACTION, BUF_POLD, BUF_DONE, BUF_RNG, BUF_V_STATE,
  BUF_V_TERM, BUF_TARGETS, BUF_ADV, BUF_VALUE_GRAD, BUF_POLICY_GRADS,
  BUF_LOGITS, BUF_PROBS, BUF_V_STATE0, BUF_QOLD, BUF_KL, BUF_LEN) = range(18)
@@ -127,6 +133,13 @@ def _load():
         "xh_venv_get": (i, [vp, i, vp, sz]),
         "xh_venv_set": (i, [vp, i, vp, sz]),
         "xh_venv_step": (i, [vp, i]),
+        "xh_venv_act": (i, [vp, vp, i, i, i]),
+        "xh_venv_set_record": (i, [vp, i, i]),
+        "xh_venv_record_pos": (i, [vp, C.POINTER(C.c_int)]),
+        "xh_venv_record_rewind": (i, [vp]),
+        "xh_venv_record_bytes": (sz, [vp, i]),
+        "xh_venv_record_ptr": (vp, [vp, i]),
+        "xh_venv_get_record": (i, [vp, i, vp, sz]),
         "xh_venv_apply": (i, [vp, i]),
         "xh_venv_reset": (i, [vp, i]),
         "xh_venv_observe": (i, [vp]),

@@ -12,6 +12,8 @@
 // row loads; the env's verdicts (game over = any bin negative) are segment
 // ballots and the item / RNG / reward record is written by the env's bin-0
 // lane.  HBM-bound: 2 * B * D + 4 + 4 + 4 + 1 bytes per env step.
+// venv_act_kernel (xh_venv_act) picks the action from the caller's policy
+// row first -- react's sampling -- and writes the trajectory record.
 #include "xh_device.h"
 #include "xh_kernels.h"
 
@@ -205,6 +207,293 @@ __global__ __launch_bounds__(256) void venv_step_kernel(VenvArgs a) {
   }
 }
 
+// ------------------------------------------------------------------ act --
+// xh_venv_act: policy_gradient_policy::react's pick (policy_gradient.h:343-350,
+// discrete_action::from_vector rl.h:27-30) from the caller's policy row, then
+// agent::step with it (rl.h:325-349) -- venv_step_kernel's mode 1 with the
+// action produced here instead of read.
+//
+// Layout: the step kernel's (VStepShape): a lane owns XH_VENV_BPL (16)
+// consecutive bins of one env -- their int8 words and their 16 policy floats,
+// read as 16-byte loads -- so B / 16 lanes (at most 8) share an env.  Every
+// global load (row, bins, item, stream state) is issued first and
+// unconditionally, as in venv_step_kernel; an out-of-range lane reads env
+// 0's and a refused env's values are not used.
+//
+// The pick.  std::discrete_distribution (or_discrete) divides each double
+// p_j by the sequential double sum, accumulates the quotients sequentially,
+// sets the last entry to 1.0 and takes the lower bound of u.  Here the lane
+// keeps its bins' partial sums unnormalised, C_k = (sum of the env's earlier
+// lanes) + p_first + .. + p_k in double (the lane's own terms sequentially,
+// the lanes' totals by a scan and an xor butterfly), and counts C_k < u sd,
+// sd the env's sum: no division per bin.  C_k / sd differs from the
+// reference's k-th boundary only by rounding -- the two summation orders of
+// at most 128 non-negative terms, one division per term, and the product u
+// sd: under (3 B + 2) 2^-53 < 5e-14 relative to a table that ends at 1 -- so
+// the counts can differ only when a boundary lies that close to u.  Whenever
+// some |C_k - u sd| < 1e-9 sd the env's lanes restate the table in the
+// reference's order (the row's floats shuffled in bin order) and take that
+// pick.
+//
+// Logits: p_j = e_j / se with e_j = expf(z_j - m), m the row's maximum, all
+// f32; se adds the lane's e_j in bin order, then the env's lanes' sums by
+// seg_sum's xor butterfly (partners 1, 2, 4).
+//
+// A row is refused (env untouched, DONE 0, error bit 2) when a probability is
+// NaN or negative or the double-precision sum is zero or not finite.
+template <int S>
+__device__ __forceinline__ float seg_max(float v) {
+#pragma unroll
+  for (int o = 1; o < S; o <<= 1) v = fmaxf(v, __shfl_xor(v, o, kWave));
+  return v;
+}
+template <int S>
+__device__ __forceinline__ int seg_sum_i(int v) {
+#pragma unroll
+  for (int o = 1; o < S; o <<= 1) v += __shfl_xor(v, o, kWave);
+  return v;
+}
+
+template <int B, int D>
+__global__ __launch_bounds__(256) void venv_act_kernel(VenvActArgs a) {
+  using S = VStepShape<B, D>;
+  static_assert(S::BPL % 4 == 0, "the lane's floats as 16-byte loads");
+  const int lane = threadIdx.x & 63;
+  const int wave = (xcd_block() * (int)blockDim.x + (int)threadIdx.x) >> 6;
+  const int el = lane / S::LPE, li = lane % S::LPE;
+  const int env = wave * S::EPW + el;
+  const int seg0 = el * S::LPE;
+  const bool in_range = env < a.v.N;
+  const size_t ec = in_range ? (size_t)env : 0;
+  int8_t *bp = a.v.bins + ec * S::BD;
+  int8_t *ip = a.v.items + ec * 4;
+  // every load first
+  float z[S::BPL];
+  {
+    const float4 *zp = reinterpret_cast<const float4 *>(
+        __builtin_assume_aligned(a.policy + ec * B + li * S::BPL, 16));
+#pragma unroll
+    for (int q = 0; q < S::BPL / 4; ++q) {
+      const float4 t = zp[q];
+      z[4 * q] = t.x;
+      z[4 * q + 1] = t.y;
+      z[4 * q + 2] = t.z;
+      z[4 * q + 3] = t.w;
+    }
+  }
+  const uint32_t *wp = reinterpret_cast<const uint32_t *>(
+      __builtin_assume_aligned(bp + li * S::BPL * D, S::ALIGN));
+  uint32_t wv[S::NW];
+#pragma unroll
+  for (int q = 0; q < S::NW; ++q) wv[q] = wp[q];
+  const unsigned itw = *reinterpret_cast<const unsigned *>(ip);
+  uint32_t x = a.v.rng[ec];
+
+  // the row's probabilities
+  float p[S::BPL];
+  if (a.logits) {
+    float m = z[0];
+#pragma unroll
+    for (int k = 1; k < S::BPL; ++k) m = fmaxf(m, z[k]);
+    m = seg_max<S::LPE>(m);
+    float se = 0.0f;
+#pragma unroll
+    for (int k = 0; k < S::BPL; ++k) {
+      p[k] = expf(z[k] - m);
+      se += p[k];
+    }
+    se = seg_sum<S::LPE>(se);
+#pragma unroll
+    for (int k = 0; k < S::BPL; ++k) p[k] = p[k] / se;
+  } else {
+#pragma unroll
+    for (int k = 0; k < S::BPL; ++k) p[k] = z[k];
+  }
+  bool bad = false;
+  double lsum = 0.0;
+#pragma unroll
+  for (int k = 0; k < S::BPL; ++k) {
+    bad |= !(p[k] >= 0.0f);  // NaN or negative
+    lsum += (double)p[k];
+  }
+  const double sd = seg_sum_d<S::LPE>(lsum);
+  bad |= !(sd > 0.0 && sd < (double)INFINITY);
+  const unsigned long long segmask =
+      S::LPE == 64 ? ~0ull : ((1ull << S::LPE) - 1ull) << seg0;
+  const bool refused = (__ballot(bad) & segmask) != 0;
+
+  // the pick (all lanes: the cross-lane steps need the whole wave)
+  int choice;
+  if (a.argmax) {  // first maximum of the values as given (tensor.cc:464-466)
+    float best = z[0];
+    int bi = li * S::BPL;
+#pragma unroll
+    for (int k = 1; k < S::BPL; ++k)
+      if (z[k] > best) {
+        best = z[k];
+        bi = li * S::BPL + k;
+      }
+#pragma unroll
+    for (int o = 1; o < S::LPE; o <<= 1) {
+      const float ov = __shfl_xor(best, o, kWave);
+      const int oi = __shfl_xor(bi, o, kWave);
+      if (ov > best || (ov == best && oi < bi)) {
+        best = ov;
+        bi = oi;
+      }
+    }
+    choice = bi;
+    x = mstd_mulmod(x, a.v.skip_mul);  // the venv's policy draws, unused
+  } else {
+    const double u = canonical(x);  // discrete_distribution's two draws
+    const double t = u * sd;
+    double c = seg_scan_d<S::LPE>(lsum, lane) - lsum;  // the earlier lanes'
+    int cnt = 0;
+    bool near = false;
+#pragma unroll
+    for (int k = 0; k < S::BPL; ++k) {
+      c += (double)p[k];
+      // the env's last boundary is 1.0: never below u
+      const bool last = li == S::LPE - 1 && k == S::BPL - 1;
+      cnt += !last && c < t;
+      near |= !last && fabs(c - t) < 1e-9 * sd;
+    }
+    choice = seg_sum_i<S::LPE>(cnt);
+    if ((__ballot(near) & segmask) != 0) {  // the reference's order, exactly
+      double s2 = 0.0;
+      for (int l = 0; l < S::LPE; ++l)
+#pragma unroll
+        for (int k = 0; k < S::BPL; ++k)
+          s2 += (double)wave_shfl(p[k], seg0 + l);
+      double acc = 0.0;
+      int c2 = B - 1;
+      for (int l = 0; l < S::LPE; ++l)
+#pragma unroll
+        for (int k = 0; k < S::BPL; ++k) {
+          const int j = l * S::BPL + k;
+          const double qj = (double)wave_shfl(p[k], seg0 + l) / s2;
+          acc = j == 0 ? qj : acc + qj;
+          const double cpj = j == B - 1 ? 1.0 : acc;
+          if (!(cpj < u) && j < c2) c2 = j;
+        }
+      choice = c2;
+    }
+  }
+  choice = refused ? 0 : choice & (B - 1);
+  float pmine = p[0];
+#pragma unroll
+  for (int k = 1; k < S::BPL; ++k) pmine = k == (choice % S::BPL) ? p[k] : pmine;
+  const float pc = wave_shfl(pmine, seg0 + choice / S::BPL);
+
+  int v[S::BPL][D];
+#pragma unroll
+  for (int k = 0; k < S::BPL; ++k)
+#pragma unroll
+    for (int d = 0; d < D; ++d) {
+      const int j = k * D + d;
+      v[k][d] = (int)(signed char)((wv[j >> 2] >> (8 * (j & 3))) & 0xff);
+    }
+  const bool live = in_range && !refused;
+  int item[D];
+#pragma unroll
+  for (int d = 0; d < D; ++d)
+    item[d] = live ? (int)(signed char)((itw >> (8 * d)) & 0xff) : 0;
+  int nb[S::BPL][D];
+  int neg_any = 0, neg_chosen = 0;
+#pragma unroll
+  for (int k = 0; k < S::BPL; ++k) {
+    const int bin = li * S::BPL + k;
+#pragma unroll
+    for (int d = 0; d < D; ++d) {
+      const int vv = live ? v[k][d] : 0;
+      nb[k][d] = bin == choice ? vv - item[d] : vv;
+      neg_any |= nb[k][d] < 0;
+      if (bin == choice) neg_chosen |= nb[k][d] < 0;
+    }
+  }
+  const bool over = (__ballot(neg_any) & segmask) != 0;
+  const bool chosen_over = (__ballot(neg_chosen) & segmask) != 0;
+  if (!in_range) return;
+
+  // the record's slot: the state before the step (also of a refused env)
+  const size_t ro = (size_t)a.slot * a.v.N + env;
+  if (a.rec_bins) {
+    uint32_t *rp = reinterpret_cast<uint32_t *>(__builtin_assume_aligned(
+        a.rec_bins + ro * S::BD + li * S::BPL * D, S::ALIGN));
+#pragma unroll
+    for (int q = 0; q < S::NW; ++q) rp[q] = wv[q];
+    if (li == 0) *reinterpret_cast<unsigned *>(a.rec_items + ro * 4) = itw;
+  }
+  if (refused) {
+    if (li == 0) {
+      atomicOr(a.v.err, 2);
+      a.v.done[env] = 0;
+      if (a.rec_action) {
+        a.rec_action[ro] = 0;
+        a.rec_pchoice[ro] = 0.0f;
+        a.rec_reward[ro] = 0.0f;
+        a.rec_done[ro] = 0;
+      }
+    }
+    return;
+  }
+  const bool reset = over;
+  {
+    uint32_t ow[S::NW];
+#pragma unroll
+    for (int q = 0; q < S::NW; ++q) ow[q] = 0u;
+#pragma unroll
+    for (int k = 0; k < S::BPL; ++k)
+#pragma unroll
+      for (int d = 0; d < D; ++d) {
+        const int j = k * D + d;
+        nb[k][d] = reset ? kCapacity : nb[k][d];
+        ow[j >> 2] |= (uint32_t)(nb[k][d] & 0xff) << (8 * (j & 3));
+      }
+    uint32_t *op = reinterpret_cast<uint32_t *>(
+        __builtin_assume_aligned(bp + li * S::BPL * D, S::ALIGN));
+#pragma unroll
+    for (int q = 0; q < S::NW; ++q) op[q] = ow[q];
+  }
+  // every lane of the env draws the same item (register-only), as in the
+  // step kernel; the bin-0 lane writes the record
+  int8_t nit[4];
+#pragma unroll
+  for (int d = 0; d < 4; ++d) nit[d] = d < D ? (int8_t)item[d] : 0;
+  if (!chosen_over) venv_item(a.v.env, x, nit);  // apply's get_item
+  if (reset) venv_item(a.v.env, x, nit);         // reset's get_item
+  x = mstd_mulmod(x, a.v.jump_mul);
+  if (li == 0) {
+    const float rew = over ? 0.0f : 1.0f;
+    *reinterpret_cast<unsigned *>(ip) = (unsigned)(uint8_t)nit[0] |
+                                        ((unsigned)(uint8_t)nit[1] << 8) |
+                                        ((unsigned)(uint8_t)nit[2] << 16) |
+                                        ((unsigned)(uint8_t)nit[3] << 24);
+    a.action[env] = choice;
+    a.pchoice[env] = pc;
+    a.v.reward[env] = rew;
+    a.v.done[env] = (uint8_t)over;
+    a.v.rng[env] = x;
+    if (a.rec_action) {
+      a.rec_action[ro] = choice;
+      a.rec_pchoice[ro] = pc;
+      a.rec_reward[ro] = rew;
+      a.rec_done[ro] = (uint8_t)over;
+    }
+  }
+  if (a.v.obs) {  // observation::to_vector of the resulting state
+#pragma unroll
+    for (int k = 0; k < S::BPL; ++k) {
+      float *o = a.v.obs + ((size_t)env * B + li * S::BPL + k) * 2 * D;
+#pragma unroll
+      for (int d = 0; d < D; ++d) {
+        o[d] = (float)nb[k][d] / (float)kCapacity;
+        o[D + d] = (float)nit[d] / (float)kCapacity;
+      }
+    }
+  }
+}
+
 // environment::reset for every (masked) env: bins at capacity, get_item.
 template <int B, int D>
 __global__ __launch_bounds__(256) void venv_reset_kernel(VenvArgs a) {
@@ -299,6 +588,20 @@ hipError_t launch_venv(const VenvArgs &a, int op, hipStream_t s) {
     else                                                                     \
       hipLaunchKernelGGL((venv_observe_kernel<XB, XD>), venv_grid(a.N, B),   \
                          dim3(256), 0, s, a);                                \
+    return hipGetLastError();                                                \
+  }
+  XH_VENV_SHAPES(X)
+#undef X
+  return hipErrorInvalidValue;
+}
+
+hipError_t launch_venv_act(const VenvActArgs &a, hipStream_t s) {
+  const int B = a.v.env.B, D = a.v.env.D;
+  if (a.v.N <= 0) return hipSuccess;
+#define X(XB, XD)                                                            \
+  if (B == XB && D == XD) {                                                  \
+    hipLaunchKernelGGL((venv_act_kernel<XB, XD>), venv_step_grid(a.v.N, B),       \
+                       dim3(256), 0, s, a);                                  \
     return hipGetLastError();                                                \
   }
   XH_VENV_SHAPES(X)

@@ -348,8 +348,26 @@ struct VenvArgs {
   uint32_t skip_mul;      // a^policy_draws (step)
   uint32_t jump_mul;      // a^(k (Nglobal - 1)) after a step (reference order)
 };
+// xh_venv_act: react's sampling + agent::step in one launch (venv_act_kernel).
+struct VenvActArgs {
+  VenvArgs v;             // mode 1; v.action unused (the kernel writes action)
+  const float *policy;    // [N][B] probabilities or logits
+  int32_t *action;        // [N] the chosen bin (out)
+  float *pchoice;         // [N] probability of the chosen bin (out)
+  int logits;             // the rows are logits: f32 softmax with a max shift
+  int argmax;             // first maximum instead of a sample (no draws)
+  // the trajectory record's slot (null: record off); slot = the cursor
+  int32_t *rec_action;    // [T][N]
+  float *rec_pchoice;     // [T][N]
+  float *rec_reward;      // [T][N]
+  uint8_t *rec_done;      // [T][N]
+  int8_t *rec_bins;       // [T][N][B][D] the state before the step, or null
+  int8_t *rec_items;      // [T][N][4]
+  int slot;
+};
 bool venv_shape_supported(int B, int D);
 hipError_t launch_venv(const VenvArgs &a, int op, hipStream_t s);
+hipError_t launch_venv_act(const VenvActArgs &a, hipStream_t s);
 hipError_t launch_venv_init(const VenvArgs &a, uint32_t x0, int env_offset,
                             int n_global, int k, hipStream_t s);
 

@@ -70,6 +70,10 @@ struct xh_venv {
   bool timing = false;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> events;  // recorded pairs
   std::vector<hipEvent_t> event_pool;  // recycled by set_timing
+  // xh_venv_set_record: the trajectory record xh_venv_act writes
+  int rec_steps = 0, rec_pos = 0;
+  void *rec[XH_VREC_COUNT] = {};
+  size_t rec_bytes[XH_VREC_COUNT] = {};
 
   xh::VenvArgs args() const {
     xh::VenvArgs a{};
@@ -2492,6 +2496,29 @@ int xh_trainer_set_env_state(xh_trainer *t, int first, int count,
 }  // extern "C"
 namespace {
 void venv_drop_events(xh_venv *v, bool destroy = false);
+// XH_VENV_POLICY / PCHOICE are allocated (zeroed on the stream) at their
+// first use, so a venv that never acts holds nothing for xh_venv_act
+int venv_ensure(xh_venv *v, int which) {
+  if (v->buf[which]) return XH_OK;
+  HIPCHK(hipSetDevice(v->ctx->device));
+  void *p = nullptr;
+  if (hipMalloc(&p, v->bytes[which]) != hipSuccess)
+    return fail(XH_ERR_HIP, "venv: allocating %zu bytes", v->bytes[which]);
+  if (hipMemsetAsync(p, 0, v->bytes[which], v->ctx->stream) != hipSuccess) {
+    (void)hipFree(p);
+    return fail(XH_ERR_HIP, "venv: zero fill");
+  }
+  v->buf[which] = p;
+  return XH_OK;
+}
+void venv_free_record(xh_venv *v) {
+  for (int w = 0; w < XH_VREC_COUNT; ++w) {
+    if (v->rec[w]) (void)hipFree(v->rec[w]);
+    v->rec[w] = nullptr;
+    v->rec_bytes[w] = 0;
+  }
+  v->rec_steps = v->rec_pos = 0;
+}
 }  // namespace
 extern "C" {
 
@@ -2522,10 +2549,13 @@ int xh_venv_create(xh_ctx *ctx, int num_envs, int bins, int dims,
     v->jump_mul = mstd_pow(k * (uint64_t)(num_envs_global - 1));
     const size_t N = (size_t)num_envs, BD = (size_t)bins * dims;
     const size_t sz[XH_VENV_BUF_COUNT] = {N * 4, N * 4, N, N * BD, N * 4, N * 4,
-                                          N * BD * 2 * 4, N};
+                                          N * BD * 2 * 4, N,
+                                          N * (size_t)bins * 4, N * 4};
     int st = XH_OK;
     for (int b = 0; b < XH_VENV_BUF_COUNT && st == XH_OK; ++b) {
       v->bytes[b] = sz[b];
+      // xh_venv_act's buffers at their first use (venv_ensure)
+      if (b == XH_VENV_POLICY || b == XH_VENV_PCHOICE) continue;
       if (hipMalloc(&v->buf[b], sz[b]) != hipSuccess ||
           hipMemsetAsync(v->buf[b], 0, sz[b], ctx->stream) != hipSuccess)
         st = fail(XH_ERR_HIP, "venv: allocating %zu bytes", sz[b]);
@@ -2563,6 +2593,7 @@ int xh_venv_destroy(xh_venv *v) {
     for (void *p : v->buf)
       if (p) (void)hipFree(p);
     if (v->err) (void)hipFree(v->err);
+    venv_free_record(v);
     xh_ctx *c = v->ctx;
     const bool counted = v->counted;
     delete v;
@@ -2576,7 +2607,14 @@ size_t xh_venv_bytes(const xh_venv *v, int which) {
 }
 
 void *xh_venv_device_ptr(xh_venv *v, int which) {
-  return v && which >= 0 && which < XH_VENV_BUF_COUNT ? v->buf[which] : nullptr;
+  if (!v || which < 0 || which >= XH_VENV_BUF_COUNT) return nullptr;
+  void *p = nullptr;
+  guard([&]() -> int {
+    const int st = venv_ensure(v, which);
+    if (st == XH_OK) p = v->buf[which];
+    return st;
+  });
+  return p;
 }
 
 namespace {
@@ -2587,19 +2625,19 @@ int venv_check_err(xh_venv *v) {
   if (err) {
     HIPCHK(hipMemsetAsync(v->err, 0, 4, v->ctx->stream));
     HIPCHK(hipStreamSynchronize(v->ctx->stream));
+    if (err & 2)
+      return fail(XH_ERR_INVALID, "venv: a policy row was refused (a NaN, a "
+                  "negative probability, or a sum that is zero or not finite)"
+                  "%s; those envs were left untouched",
+                  err & 1 ? ", and an action was out of range" : "");
     return fail(XH_ERR_INVALID, "venv: an action was outside [0, %d); those "
                 "envs were left untouched", v->env.B);
   }
   return XH_OK;
 }
-int venv_launch(xh_venv *v, int op, int mode, bool use_mask, bool obs) {
-  HIPCHK(hipSetDevice(v->ctx->device));
-  xh::VenvArgs a = v->args();
-  a.mode = mode;
-  a.mask = use_mask ? (const uint8_t *)v->buf[XH_VENV_MASK] : nullptr;
-  a.obs = obs ? (float *)v->buf[XH_VENV_OBS] : nullptr;
-  if (op == xh::kVenvObserve) a.obs = (float *)v->buf[XH_VENV_OBS];
-  if (mode == 0) a.reward = nullptr;
+// one launch on the context's stream, bracketed by HIP events when timing
+extern "C++" template <class F>
+int venv_timed(xh_venv *v, F &&launch) {
   // events from a pool (no creation per launch); a pair is kept only once
   // both of its records are on the stream, so a failed launch leaves no
   // half-recorded pair behind
@@ -2617,7 +2655,7 @@ int venv_launch(xh_venv *v, int op, int mode, bool use_mask, bool obs) {
     HIPCHK(pooled(&ev.second));
     HIPCHK(hipEventRecord(ev.first, v->ctx->stream));
   }
-  const hipError_t e = xh::launch_venv(a, op, v->ctx->stream);
+  const hipError_t e = launch();
   if (e != hipSuccess) {
     if (v->timing) {
       v->event_pool.push_back(ev.first);
@@ -2630,6 +2668,16 @@ int venv_launch(xh_venv *v, int op, int mode, bool use_mask, bool obs) {
     v->events.push_back(ev);
   }
   return XH_OK;
+}
+int venv_launch(xh_venv *v, int op, int mode, bool use_mask, bool obs) {
+  HIPCHK(hipSetDevice(v->ctx->device));
+  xh::VenvArgs a = v->args();
+  a.mode = mode;
+  a.mask = use_mask ? (const uint8_t *)v->buf[XH_VENV_MASK] : nullptr;
+  a.obs = obs ? (float *)v->buf[XH_VENV_OBS] : nullptr;
+  if (op == xh::kVenvObserve) a.obs = (float *)v->buf[XH_VENV_OBS];
+  if (mode == 0) a.reward = nullptr;
+  return venv_timed(v, [&] { return xh::launch_venv(a, op, v->ctx->stream); });
 }
 // the recorded pairs back into the pool (the stream is synchronised first);
 // destroy = true at xh_venv_destroy
@@ -2653,6 +2701,7 @@ int xh_venv_get(xh_venv *v, int which, void *host, size_t bytes) {
       return fail(XH_ERR_INVALID, "venv buffer %d: %zu bytes, expected %zu",
                   which, bytes, xh_venv_bytes(v, which));
     HIPCHK(hipSetDevice(v->ctx->device));
+    if (const int st = venv_ensure(v, which)) return st;
     HIPCHK(copy_to_host(host, v->buf[which], bytes, v->ctx->stream));
     return venv_check_err(v);
   });
@@ -2681,6 +2730,7 @@ int xh_venv_set(xh_venv *v, int which, const void *host, size_t bytes) {
                       b[i], kBinCapacity);
     }
     HIPCHK(hipSetDevice(v->ctx->device));
+    if (const int st = venv_ensure(v, which)) return st;
     HIPCHK(copy_to_device(v->buf[which], host, bytes, v->ctx->stream));
     HIPCHK(hipStreamSynchronize(v->ctx->stream));
     return XH_OK;
@@ -2691,6 +2741,120 @@ int xh_venv_step(xh_venv *v, int write_obs) {
   return guard([&]() -> int {
     if (!v) return fail(XH_ERR_INVALID, "null venv");
     return venv_launch(v, xh::kVenvStep, 1, false, write_obs != 0);
+  });
+}
+
+int xh_venv_act(xh_venv *v, const float *policy_dev, int kind, int mode,
+                int write_obs) {
+  return guard([&]() -> int {
+    if (!v) return fail(XH_ERR_INVALID, "null venv");
+    if (kind != XH_ACT_PROBS && kind != XH_ACT_LOGITS)
+      return fail(XH_ERR_INVALID, "venv act: kind %d (XH_ACT_PROBS / LOGITS)",
+                  kind);
+    if (mode != XH_ACT_SAMPLE && mode != XH_ACT_ARGMAX)
+      return fail(XH_ERR_INVALID, "venv act: mode %d (XH_ACT_SAMPLE / ARGMAX)",
+                  mode);
+    if (mode == XH_ACT_SAMPLE && v->policy_draws != 2)
+      return fail(XH_ERR_INVALID, "venv act: sampling takes two draws per env "
+                  "and step, the venv was created with policy_draws %d",
+                  v->policy_draws);
+    if (reinterpret_cast<uintptr_t>(policy_dev) & 15)
+      return fail(XH_ERR_INVALID, "venv act: the policy rows must be 16-byte "
+                  "aligned (the kernel reads them as 16-byte loads)");
+    if (v->rec_steps > 0 && v->rec_pos >= v->rec_steps)
+      return fail(XH_ERR_STATE, "venv act: the record's %d slots are full "
+                  "(xh_venv_record_rewind)", v->rec_steps);
+    HIPCHK(hipSetDevice(v->ctx->device));
+    if (!policy_dev)
+      if (const int st = venv_ensure(v, XH_VENV_POLICY)) return st;
+    if (const int st = venv_ensure(v, XH_VENV_PCHOICE)) return st;
+    xh::VenvActArgs a{};
+    a.v = v->args();
+    a.v.mode = 1;
+    a.v.obs = write_obs ? (float *)v->buf[XH_VENV_OBS] : nullptr;
+    a.policy = policy_dev ? policy_dev : (const float *)v->buf[XH_VENV_POLICY];
+    a.action = (int32_t *)v->buf[XH_VENV_ACTIONS];
+    a.pchoice = (float *)v->buf[XH_VENV_PCHOICE];
+    a.logits = kind == XH_ACT_LOGITS;
+    a.argmax = mode == XH_ACT_ARGMAX;
+    if (v->rec_steps > 0) {
+      a.rec_action = (int32_t *)v->rec[XH_VREC_ACTION];
+      a.rec_pchoice = (float *)v->rec[XH_VREC_PCHOICE];
+      a.rec_reward = (float *)v->rec[XH_VREC_REWARD];
+      a.rec_done = (uint8_t *)v->rec[XH_VREC_DONE];
+      a.rec_bins = (int8_t *)v->rec[XH_VREC_BINS];
+      a.rec_items = (int8_t *)v->rec[XH_VREC_ITEMS];
+      a.slot = v->rec_pos;
+    }
+    const int st = venv_timed(
+        v, [&] { return xh::launch_venv_act(a, v->ctx->stream); });
+    if (st == XH_OK && v->rec_steps > 0) ++v->rec_pos;
+    return st;
+  });
+}
+
+int xh_venv_set_record(xh_venv *v, int steps, int with_states) {
+  return guard([&]() -> int {
+    if (!v) return fail(XH_ERR_INVALID, "null venv");
+    if (steps < 0) return fail(XH_ERR_INVALID, "venv record: steps %d", steps);
+    HIPCHK(hipSetDevice(v->ctx->device));
+    HIPCHK(hipStreamSynchronize(v->ctx->stream));
+    venv_free_record(v);
+    if (steps == 0) return XH_OK;
+    const size_t TN = (size_t)steps * v->N;
+    const size_t BD = (size_t)v->env.B * v->env.D;
+    const size_t sz[XH_VREC_COUNT] = {TN * 4, TN * 4, TN * 4, TN,
+                                      with_states ? TN * BD : 0,
+                                      with_states ? TN * 4 : 0};
+    for (int w = 0; w < XH_VREC_COUNT; ++w) {
+      if (!sz[w]) continue;
+      if (hipMalloc(&v->rec[w], sz[w]) != hipSuccess ||
+          hipMemsetAsync(v->rec[w], 0, sz[w], v->ctx->stream) != hipSuccess) {
+        venv_free_record(v);
+        return fail(XH_ERR_HIP, "venv record: allocating %zu bytes", sz[w]);
+      }
+      v->rec_bytes[w] = sz[w];
+    }
+    v->rec_steps = steps;
+    return XH_OK;
+  });
+}
+
+int xh_venv_record_pos(xh_venv *v, int *pos) {
+  return guard([&]() -> int {
+    if (!v || !pos) return fail(XH_ERR_INVALID, "null arg");
+    *pos = v->rec_pos;
+    return XH_OK;
+  });
+}
+
+int xh_venv_record_rewind(xh_venv *v) {
+  return guard([&]() -> int {
+    if (!v) return fail(XH_ERR_INVALID, "null venv");
+    v->rec_pos = 0;
+    return XH_OK;
+  });
+}
+
+size_t xh_venv_record_bytes(const xh_venv *v, int which) {
+  return v && which >= 0 && which < XH_VREC_COUNT ? v->rec_bytes[which] : 0;
+}
+
+void *xh_venv_record_ptr(xh_venv *v, int which) {
+  return v && which >= 0 && which < XH_VREC_COUNT ? v->rec[which] : nullptr;
+}
+
+int xh_venv_get_record(xh_venv *v, int which, void *host, size_t bytes) {
+  return guard([&]() -> int {
+    if (!v || !host) return fail(XH_ERR_INVALID, "null arg");
+    if (which < 0 || which >= XH_VREC_COUNT || !v->rec[which] ||
+        bytes != v->rec_bytes[which])
+      return fail(XH_ERR_INVALID, "venv record %d: %zu bytes, expected %zu",
+                  which, bytes, xh_venv_record_bytes(v, which));
+    HIPCHK(hipSetDevice(v->ctx->device));
+    HIPCHK(copy_to_host(host, v->rec[which], bytes, v->ctx->stream));
+    HIPCHK(hipStreamSynchronize(v->ctx->stream));
+    return XH_OK;
   });
 }
 

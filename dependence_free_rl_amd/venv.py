@@ -6,6 +6,16 @@
     env.set_actions(actions)            # int32 [N]
     reward, done = env.step()           # agent::step minus react, all envs
 
+or, sampling the caller's policy rows on the device (react + agent::step in
+one launch, recording the trajectory):
+
+    env.set_record(steps=T)
+    for t in range(T):
+        rows = my_policy(env.observe())                 # [N][B] float32
+        actions, pchoice, reward, done = env.act(rows)  # or a device pointer
+    batch = env.record()                # action / pchoice / reward / done /
+                                        # bins / items, [T][N]...
+
 Mirrors xylo::environment<A,S>::apply / view / reset (rl.h:163-170) with the
 id ranging over the batch, bp::environment (bin_packing.h:46-85) and
 xylo::agent::step (rl.h:325-349).  State lives in HBM; numpy arrays here are
@@ -17,8 +27,14 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import (VENV_ACTIONS, VENV_BINS, VENV_DONE, VENV_ITEMS, VENV_MASK,
-                   VENV_OBS, VENV_REWARD, VENV_RNG, check)
+from ._lib import (ACT_ARGMAX, ACT_LOGITS, ACT_PROBS, ACT_SAMPLE, VENV_ACTIONS,
+                   VENV_BINS, VENV_DONE, VENV_ITEMS, VENV_MASK, VENV_OBS,
+                   VENV_PCHOICE, VENV_POLICY, VENV_REWARD, VENV_RNG,
+                   VREC_ACTION, VREC_BINS, VREC_DONE, VREC_ITEMS, VREC_PCHOICE,
+                   VREC_REWARD, check)
+
+_KINDS = {"probs": ACT_PROBS, "logits": ACT_LOGITS}
+_MODES = {"sample": ACT_SAMPLE, "argmax": ACT_ARGMAX}
 
 
 def _ptr(a):
@@ -43,7 +59,9 @@ class VecEnv:
                 VENV_DONE: (np.uint8, (N,)), VENV_BINS: (np.int8, (N, B, D)),
                 VENV_ITEMS: (np.int8, (N, 4)), VENV_RNG: (np.uint32, (N,)),
                 VENV_OBS: (np.float32, (N, B, 2 * D)),
-                VENV_MASK: (np.uint8, (N,))}[which]
+                VENV_MASK: (np.uint8, (N,)),
+                VENV_POLICY: (np.float32, (N, B)),
+                VENV_PCHOICE: (np.float32, (N,))}[which]
 
     def get(self, which):
         dt, shape = self._spec(which)
@@ -69,6 +87,66 @@ class VecEnv:
         if fetch:
             return self.get(VENV_REWARD), self.get(VENV_DONE)
         return None
+
+    def act(self, policy=None, kind="probs", mode="sample", write_obs=False,
+            fetch=True):
+        """react + agent::step for every env in one launch (xh_venv_act):
+        pick a bin from each env's policy row, then step with it.
+
+        policy: a host array [N][B] (uploaded into VENV_POLICY), an integer
+        device pointer to N * B floats, or None (VENV_POLICY as it stands).
+        kind "probs" | "logits"; mode "sample" (discrete_distribution, two
+        draws; needs policy_draws == 2) | "argmax" (first maximum, no draws).
+        Returns (actions, pchoice, reward, done) if fetch."""
+        ptr = None
+        if isinstance(policy, (int, np.integer)):
+            ptr = C.c_void_p(int(policy))
+        elif policy is not None:
+            self.set(VENV_POLICY, policy)
+        check(_lib.lib.xh_venv_act(self.h, ptr, _KINDS[kind], _MODES[mode],
+                                   1 if write_obs else 0))
+        if fetch:
+            return (self.get(VENV_ACTIONS), self.get(VENV_PCHOICE),
+                    self.get(VENV_REWARD), self.get(VENV_DONE))
+        return None
+
+    # ---- the trajectory record act() writes -----------------------------
+    def set_record(self, steps, states=True):
+        """Record the next `steps` act() calls (xh_venv_set_record); 0 turns
+        the record off and frees it."""
+        check(_lib.lib.xh_venv_set_record(self.h, int(steps),
+                                          1 if states else 0))
+
+    def record_pos(self):
+        pos = C.c_int()
+        check(_lib.lib.xh_venv_record_pos(self.h, C.byref(pos)))
+        return pos.value
+
+    def record(self):
+        """The recorded slots [0, cursor) as a dict: action int32 [t][N],
+        pchoice / reward float32 [t][N], done uint8 [t][N] and, if recorded,
+        the states before each step: bins int8 [t][N][B][D], items int8
+        [t][N][4]."""
+        N, B, D = self.N, self.B, self.D
+        spec = {"action": (VREC_ACTION, np.int32, (N,)),
+                "pchoice": (VREC_PCHOICE, np.float32, (N,)),
+                "reward": (VREC_REWARD, np.float32, (N,)),
+                "done": (VREC_DONE, np.uint8, (N,)),
+                "bins": (VREC_BINS, np.int8, (N, B, D)),
+                "items": (VREC_ITEMS, np.int8, (N, 4))}
+        pos, out = self.record_pos(), {}
+        for name, (which, dt, shape) in spec.items():
+            nbytes = _lib.lib.xh_venv_record_bytes(self.h, which)
+            if not nbytes:
+                continue
+            a = np.zeros(nbytes // np.dtype(dt).itemsize, dt)
+            check(_lib.lib.xh_venv_get_record(self.h, which, _ptr(a), nbytes))
+            out[name] = a.reshape((-1,) + shape)[:pos]
+        return out
+
+    def rewind(self):
+        """The next act() writes slot 0 again (xh_venv_record_rewind)."""
+        check(_lib.lib.xh_venv_record_rewind(self.h))
 
     def apply(self, mask=None):
         """environment::apply(actions[e], e) for the masked envs (no reset);

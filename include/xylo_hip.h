@@ -617,6 +617,12 @@ int xh_digest_host(const void *data, size_t bytes, uint64_t *out);
  *                                    31-40), written by xh_venv_observe and
  *                                    by xh_venv_step(write_obs = 1)
  *   XH_VENV_MASK    uint8 [N]        env selection for apply / reset
+ *   XH_VENV_POLICY  f32   [N][B]     the caller's policy output for the
+ *                                    current states (input of xh_venv_act)
+ *   XH_VENV_PCHOICE f32   [N]        probability of the bin xh_venv_act chose
+ * POLICY and PCHOICE are allocated (zero-filled) at their first use through
+ * xh_venv_set / get / device_ptr or xh_venv_act; xh_venv_bytes gives their
+ * sizes at any time.
  *
  * Engine draws: construction 2 per env, get_item 2, reset 2.
  * Env g of the job (env_offset + local index) starts on the global engine
@@ -636,7 +642,7 @@ typedef struct xh_venv xh_venv;
 enum {
   XH_VENV_ACTIONS = 0, XH_VENV_REWARD = 1, XH_VENV_DONE = 2,
   XH_VENV_BINS = 3, XH_VENV_ITEMS = 4, XH_VENV_RNG = 5, XH_VENV_OBS = 6,
-  XH_VENV_MASK = 7, XH_VENV_BUF_COUNT
+  XH_VENV_MASK = 7, XH_VENV_POLICY = 8, XH_VENV_PCHOICE = 9, XH_VENV_BUF_COUNT
 };
 int xh_venv_create(xh_ctx *ctx, int num_envs, int bins, int dims,
                    uint32_t rng_state, int env_offset, int num_envs_global,
@@ -650,6 +656,62 @@ int xh_venv_set(xh_venv *v, int which, const void *host, size_t bytes);
  * environment::apply(ACTIONS[e]), REWARD / DONE, reset on game over;
  * write_obs != 0 also writes OBS of the resulting states. */
 int xh_venv_step(xh_venv *v, int write_obs);
+/* The policy's react and agent::step in one launch: per env, pick a bin from
+ * the caller's policy row (policy_gradient_policy::react,
+ * policy_gradient.h:343-350), then do what xh_venv_step does with it.
+ *
+ * policy_dev: N*B floats on the context's device, 16-byte aligned (e.g. from
+ * xh_tensor_alloc), the caller's writes ordered before the call; NULL reads
+ * XH_VENV_POLICY.
+ * kind: XH_ACT_PROBS, the rows as given, or XH_ACT_LOGITS, an f32 softmax with
+ *   a max shift: e_j = expf(z_j - max z), p_j = e_j / se, where se adds each
+ *   run of 16 consecutive bins (all of them at 8 bins) in bin order and then
+ *   the runs' sums by an xor butterfly (partners 1, 2, 4).
+ * mode: XH_ACT_SAMPLE, std::discrete_distribution<size_t> over p[0..B) with
+ *   u = generate_canonical<double> (rl.h:27-30): p to double, divided by the
+ *   sequential double sum, sequential partial sums, the last entry 1.0, the
+ *   lower bound of u; two draws from the env's stream where it stands, so the
+ *   venv must have been created with policy_draws == 2 (XH_ERR_INVALID
+ *   otherwise).  XH_ACT_ARGMAX, the first maximum of the row's values as
+ *   given (ties to the lowest bin, tensor.cc:464-466); draws nothing and
+ *   skips the venv's policy_draws as xh_venv_step does.
+ * Out: ACTIONS[e] = the bin, PCHOICE[e] = p[bin] (for PROBS the bits of the
+ * input entry), then apply, REWARD / DONE, reset on game over, the jump over
+ * the other envs' draws, and OBS if write_obs != 0.
+ * A row with a NaN, a negative probability or a sum that is zero or not
+ * finite is refused: its env is left untouched (ACTIONS and PCHOICE too),
+ * DONE[e] = 0, and the next xh_venv_synchronize / get returns
+ * XH_ERR_INVALID.
+ * With a record (xh_venv_set_record) the call also writes the record's slot
+ * at the cursor and advances it; on a full record it returns XH_ERR_STATE. */
+enum { XH_ACT_PROBS = 0, XH_ACT_LOGITS = 1 };
+enum { XH_ACT_SAMPLE = 0, XH_ACT_ARGMAX = 1 };
+int xh_venv_act(xh_venv *v, const float *policy_dev, int kind, int mode,
+                int write_obs);
+/* The trajectory record, written by xh_venv_act's own launch (no further
+ * launch, no host synchronisation).  steps = T > 0 allocates T slots
+ * (zero-filled, cursor 0, replacing an earlier record); steps = 0 turns the
+ * record off and frees it.  The call at cursor t writes slot t of
+ *   XH_VREC_ACTION  int32 [T][N]        XH_VREC_PCHOICE f32 [T][N]
+ *   XH_VREC_REWARD  f32   [T][N]        XH_VREC_DONE    uint8 [T][N]
+ * and, with with_states != 0, the state before the step
+ *   XH_VREC_BINS    int8  [T][N][B][D]  XH_VREC_ITEMS   int8 [T][N][4]
+ * (the trainer's XH_BUF_ACTION / POLD / DONE / BINS / ITEMS layouts for slots
+ * 0..T-1; the state after the last step is XH_VENV_BINS / ITEMS).  A refused
+ * env's ACTION / PCHOICE / REWARD / DONE entries of the slot are zero; its
+ * state entries hold its (unchanged) state.  xh_venv_step / apply / reset do
+ * not record.  xh_venv_record_bytes is the whole array's size (0 with the
+ * record off, or for the states without with_states); xh_venv_get_record
+ * copies the whole array (slots from the cursor on hold what an earlier pass
+ * left there, zeros at first). */
+enum { XH_VREC_ACTION = 0, XH_VREC_PCHOICE, XH_VREC_REWARD, XH_VREC_DONE,
+       XH_VREC_BINS, XH_VREC_ITEMS, XH_VREC_COUNT };
+int xh_venv_set_record(xh_venv *v, int steps, int with_states);
+int xh_venv_record_pos(xh_venv *v, int *pos);
+int xh_venv_record_rewind(xh_venv *v);
+size_t xh_venv_record_bytes(const xh_venv *v, int which);
+void *xh_venv_record_ptr(xh_venv *v, int which);
+int xh_venv_get_record(xh_venv *v, int which, void *host, size_t bytes);
 /* environment::apply(ACTIONS[e], e) for the envs selected by MASK (all if
  * use_mask == 0), no reset; DONE[e] = game_over after the apply, 0 for the
  * envs this call did not apply (masked out, or an out-of-range action). */
@@ -658,9 +720,10 @@ int xh_venv_apply(xh_venv *v, int use_mask);
 int xh_venv_reset(xh_venv *v, int use_mask);
 /* observation::to_vector of every env into OBS. */
 int xh_venv_observe(xh_venv *v);
-/* Waits for the venv's work; XH_ERR_INVALID if an action was out of range. */
+/* Waits for the venv's work; XH_ERR_INVALID if an action was out of range or
+ * xh_venv_act refused a policy row. */
 int xh_venv_synchronize(xh_venv *v);
-/* Kernel timing: on != 0 brackets every later step / apply / reset /
+/* Kernel timing: on != 0 brackets every later step / act / apply / reset /
  * observe launch with HIP events on the context's stream (and drops the
  * events recorded so far); xh_venv_kernel_time returns their accumulated
  * milliseconds and the launch count. */

@@ -211,6 +211,7 @@ variant: $(OBJS)
 # KL-PPO, epoch 0) with XH_SP8_* switches turned, for the same A/B runs
 # (`variant` with VSRC=policy_spec8_kernels would rebuild the plain one only):
 #   make variant_spec8 V=l1pk0 VFLAGS="-DXH_SP8_L1PK=0"
+#   make variant_spec8 V=dhb0 VFLAGS="-DXH_SP8_DHB=0"   (dH1 back in phase A)
 #   make variant_spec8 V=ghf_e0 VFLAGS="" VFLAGS_E0="-DXH_SP8_GHF=1"
 #     (VFLAGS_E0 / VFLAGS_KL: the epoch-0 / KL-PPO object's, default VFLAGS)
 VFLAGS_E0 ?= $(VFLAGS)

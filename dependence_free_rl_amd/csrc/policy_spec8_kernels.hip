@@ -35,25 +35,48 @@
 // MFMAs per K slice.
 //
 // Per 64-row group g (one transition's 64 bins), the work by role:
-//   vector  L1(g)   layer 1 -> H1 image (f16 pair, [i][r]), H1 kept in registers
+//   vector  L1(g)   layer 1 on the matrix cores (one bf16 MFMA per r-tile)
+//                   -> the H1 image (f16 pair, [r][i]); nothing of it is kept
 //   matrix  L2(g)   layer 2 (48 MFMAs per wave: its 32 outputs o x 64 rows)
 //                   -> partial logits over its o
 //   matrix  SM(g)   softmax + loss gradient g of the 64 rows (every matrix
 //                   wave, from the four partial logits), dW3 / db2 sums,
 //                   relu masks -> the mask image ([r][o], 0 / 2.0: bf16 and
 //                   f16 alike)
-//   vector  DH(g)   dH1 = M (S_D W2') (32 MFMAs: its 32 features i), dW1 /
-//                   db1 / item sums; g (x) H1 -> the split image ([i][r])
+//   vector  GH(g)   the group's layer-1 values from the exact f32 chain (hk,
+//                   in registers until dW1) and g (x) H1 -> the split image
+//                   ([i][r])
+//   vector  DH(g)   dH1 = M (S_D W2') (32 MFMAs: its 32 features i, 16 steps
+//                   of one mask fragment and two MFMAs, r-tile 0's eight
+//                   first), then dW1 / db1 / item sums from hk and dH1
 //   matrix  DW(g)   dW2 += M^T (g (x) H1) (32 MFMAs: its 32 features i; 48
 //                   in the three-part form)
 // pipelined two phases per group, each closed by a barrier:
-//   A(j): matrix L2(j+1) + partial logits    vector DH(j) + g (x) H1(j)
-//   B(j): matrix SM(j+1) + DW(j)             vector dW1(j) + L1(j+2)
-// (the phases carry 80 / 32 MFMAs per SIMD beside the vector wave's VALU).
+//   A(j): matrix L2(j+1) + partial logits    vector GH(j)
+//   B(j): matrix SM(j+1) + DW(j)             vector DH(j) with L1(j+2) in
+//                                            r-tile 0's MFMA slots and dW1(j)'s
+//                                            blocks 0-3 in r-tile 1's, then
+//                                            dW1(j)'s blocks 4-7
+// (the phases carry 48 / 66 MFMAs per SIMD: a nearly MFMA-only wave beside a
+// VALU-only one in A, the regime the probe above measured).  XH_SP8_DHB = 0
+// is the earlier schedule, dH1 in A with g (x) H1 in its MFMA slots, B dW1(j)
+// + L1(j+2): 80 / 34 MFMAs, A bound by the matrix pipe and B by issue; 8
+// leaves r-tile 0 in A.  The epoch-0 build keeps dH1 beside g (x) H1 in its
+// one phase.
+// Hazards of dH1 in B (none new): in B(j) SM(j+1) writes mask slot (j+1) & 1
+// and g slot (j+1) & 1 while dH1(j) and DW(j) read mask slot j & 1 and dW1(j)
+// g slot j & 1; SM(j+2) overwrites slot j & 1 only in B(j+1), behind B(j)'s
+// barrier.  L1(j+2) writes the single H1 image in B(j), as before, after
+// L2(j+1) read it in A(j) and before L2(j+2) reads it in A(j+1).  The F_G /
+// F_X / F_REC slots are read in the phases they were read in (GH(j): X slot
+// j & 3 and g slot j & 1 in A(j); dW1(j): g slot j & 1, L1(j+2): X / REC slot
+// (j+2) & 3 in B(j)): no lifetime lengthens.  LDS size and layout are
+// unchanged.
 // The two roles run separate code paths with the same barrier sequence, so
 // the compiler allocates each path's registers alone (matrix: W2 pair 64,
 // dW2 accumulators 64, layer-2 accumulators 32, dW3 / db2 sums 32; vector:
-// W2' pair 64, dH1 accumulators 32, two groups' H1 64).
+// W2' pair 64, dH1 accumulators 32, hk 32, layer 1's pre-activations 32
+// while r-tile 0 runs).
 //
 // LDS (dynamic, base 0): the f32 vectors first (8 KB; 9 KB in the KL-PPO
 // build: their offsets are the ds instructions' immediates), then g (x) H1
@@ -203,8 +226,34 @@
 #endif
 // XH_SP8_VAF (A/B builds): 0 lets the compiler schedule the vector waves'
 // phase-A slots (g (x) H1) across the dH1 MFMAs
+// (with XH_SP8_DHB the same fences hold phase B's layer-1 / dW1 pieces in
+// their dH1 MFMA slots)
 #ifndef XH_SP8_VAF
 #define XH_SP8_VAF 1
+#endif
+// XH_SP8_DHB: how many of dH1's 16 steps (one mask fragment and two f16 MFMAs
+// each) the vector waves issue in phase B instead of phase A: 0 (all of dH1 in
+// A, beside layer 2's MFMAs on the same SIMD), 8 (r-tile 1 in B) or 16 (all of
+// dH1 in B, in the matrix pipe's idle time beside dW2); the schedule in the
+// header's phase table.  Every accumulator keeps the order of its products:
+// the gradients are bit for bit the same at every value.  Measured (DESIGN.md
+// §8, three paired rounds on one box): 0 6.582, 8 6.507, 16 6.480 ms per
+// iteration, so 16 ships; 0 is the earlier code line for line, kept for A/B
+// runs.  (The epoch-0 build has one phase per group and takes no part in
+// this.)
+#ifndef XH_SP8_DHB
+#define XH_SP8_DHB 16
+#endif
+#if XH_SP8_E0_TU
+#define SP8_DHB 0
+#else
+#define SP8_DHB XH_SP8_DHB
+#endif
+#if SP8_DHB != 0 && SP8_DHB != 8 && SP8_DHB != 16
+#error "XH_SP8_DHB: 0, 8 (dH1's r-tile 1 in phase B) or 16 (all of dH1)"
+#endif
+#if SP8_DHB && XH_SP8_DHI
+#error "XH_SP8_DHB moves whole r-tiles: not with XH_SP8_DHI's alternating order"
 #endif
 #define VAFENCE()                                 \
   do {                                            \
@@ -1603,12 +1652,16 @@ __global__ __launch_bounds__(kThreads, 2) void policy_train_spec8_kernel(PolicyT
 #endif
         }
       };
-      ldA(0);
+      // (XH_SP8_DHB: the last kStB steps are phase B's, dh_b below; their
+      // blocks' slots follow the loop with no MFMA between them, the
+      // scheduler's to order, the ring still two blocks ahead)
+      constexpr int kStA = 16 - SP8_DHB;
+      if (kStA > 0) ldA(0);
 #pragma unroll
-      for (int st = 0; st < 16; ++st) {
+      for (int st = 0; st < kStA; ++st) {
         const int t = XH_SP8_DHI ? st & 1 : st >> 3, ks = XH_SP8_DHI ? st >> 1 : st & 7,
                   ca = st & 1;
-        if (st + 1 < 16) ldA(st + 1);
+        if (st + 1 < kStA) ldA(st + 1);
         VAFENCE();
         if (ks == 0)
           dh[t] = mfma_f16(A[ca], wd[ks][1], f32x16s{});
@@ -1622,6 +1675,8 @@ __global__ __launch_bounds__(kThreads, 2) void policy_train_spec8_kernel(PolicyT
         gh_slot(2 * st + 1);
         VAFENCE();
       }
+#pragma unroll
+      for (int k = 2 * kStA; k < 32; ++k) gh_slot(k);
     };
     // B(gi): dW1 / db1 / item sums of group gi: d = relu'(H1) dH1 g; sums
     // d x0, d x1, d (g, g x0, g x1 staged by matrix wave 0), two partial
@@ -1662,6 +1717,108 @@ __global__ __launch_bounds__(kThreads, 2) void policy_train_spec8_kernel(PolicyT
       else
         sb += sg;
     };
+#if SP8_DHB
+    // B(gi) with XH_SP8_DHB: dH1's last SP8_DHB steps (dh_gh's, in its order:
+    // r-tile 0's K steps, then r-tile 1's; the mask fragment one step ahead),
+    // then dW1(gi) and layer1(gi + 2) as above, cut into pieces that sit in the
+    // MFMA slots, two slots per step, so that one in-order stream never waits
+    // for a complete dH1:
+    //   16: r-tile 0's 16 slots hold layer 1 (l1_mfma first, then one f16-pair
+    //       split of two columns per slot, a block's two stores with its
+    //       last), r-tile 1's hold dW1's blocks 0-3 (r-tile 0's dh), a row per
+    //       slot; dW1's blocks 4-7 follow
+    //    8: r-tile 1's 16 slots hold a layer-1 piece and a dW1 row each;
+    //       dW1's blocks 4-7 follow
+    // dW1's two partial sums run over the blocks' rows in dw1's order.
+    (void)dw1;
+    auto dh_b = [&](int gi, int gpar, const f32x16s (&hk)[2], f32x16s (&dh)[2]) {
+      constexpr bool run_dh = SP8_RUN(2 | 4), run_dw = SP8_RUN(2 | 64), run_l1 = SP8_RUN(2 | 8);
+      constexpr int kStA = 16 - SP8_DHB;
+      const int mb = kMaskSlot * gpar;
+      f16x8 A[2];
+      auto ldA = [&](int st) {
+        A[st & 1] = ld8h(((st & 1) ? rbm1 : rbm0) + mb + 8192 * (st >> 3) + 1024 * ((st & 7) >> 1));
+      };
+      const float *gv = lf + F_G + 192 * gpar;
+      float a0[2] = {0.0f, 0.0f}, a1[2] = {0.0f, 0.0f}, ag[2] = {0.0f, 0.0f};
+      f32x4 gb[2][3];
+      auto ld3 = [&](int b) {
+        const int r0 = 32 * (b >> 2) + 8 * (b & 3) + 4 * h;
+        gb[b & 1][0] = lds4v(gv + r0);
+        gb[b & 1][1] = lds4v(gv + 64 + r0);
+        gb[b & 1][2] = lds4v(gv + 128 + r0);
+      };
+      // row u of dW1's block b (block b + 1's vectors loaded with its first)
+      auto dw1_row = [&](int b, int u) {
+        if (!run_dw) return;
+        const int t = b >> 2, q = b & 3;
+        if (u == 0 && b + 1 < 8) ld3(b + 1);
+        const f32x4(&cur)[3] = gb[b & 1];
+        const float m = hk[t][4 * q + u] > 0.0f ? dh[t][4 * q + u] : 0.0f;
+        a0[u & 1] = fmaf(m, cur[1][u], a0[u & 1]);
+        a1[u & 1] = fmaf(m, cur[2][u], a1[u & 1]);
+        ag[u & 1] = fmaf(m, cur[0][u], ag[u & 1]);
+      };
+      // piece k of layer1(gi + 2): pair p = k & 3 of its block b = k >> 2
+      f32x16s pre[2];
+      typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+      u32x4 hi, lo;
+      auto l1_piece = [&](int k) {
+        if (!run_l1) return;
+        const int b = k >> 2, p = k & 3, t = b >> 1, j = b & 1;
+        const int q = 2 * j + (p >> 1), u = 2 * (p & 1);
+        unsigned h2, l2;
+        split2h_x2(relu(pre[t][4 * q + u]), relu(pre[t][4 * q + u + 1]), h2, l2);
+        hi[p] = h2;
+        lo[p] = l2;
+        if (p == 3) {
+          st8h(vwH[j] + 8192 * t, __builtin_bit_cast(f16x8, hi));
+          st8h(vwH[j] + kImg + 8192 * t, __builtin_bit_cast(f16x8, lo));
+        }
+      };
+      auto slot = [&](int n) {
+        if (SP8_DHB == 16 && n >= 16) {
+          dw1_row((n - 16) >> 2, n & 3);
+        } else {
+          l1_piece(n);
+          if (SP8_DHB == 8) dw1_row(n >> 2, n & 3);
+        }
+      };
+      if (run_dh) ldA(kStA);
+      if (run_l1) l1_mfma(gi + 2, pre);
+      if (run_dw) ld3(0);
+#pragma unroll
+      for (int st = kStA; st < 16; ++st) {
+        const int t = st >> 3, ks = st & 7, ca = st & 1;
+        if (run_dh && st + 1 < 16) ldA(st + 1);
+        VAFENCE();
+        if (run_dh) {
+          if (ks == 0)
+            dh[t] = mfma_f16(A[ca], wd[ks][1], f32x16s{});
+          else
+            dh[t] = mfma_f16(A[ca], wd[ks][1], dh[t]);
+        }
+        VAFENCE();
+        slot(2 * (st - kStA));
+        VAFENCE();
+        if (run_dh) dh[t] = mfma_f16(A[ca], wd[ks][0], dh[t]);
+        VAFENCE();
+        slot(2 * (st - kStA) + 1);
+        VAFENCE();
+      }
+#pragma unroll
+      for (int n = 16; n < 32; ++n) dw1_row(n >> 2, n & 3);
+      w0 += a0[0] + a0[1];
+      w1 += a1[0] + a1[1];
+      const float sg = ag[0] + ag[1];
+      const bool ia =
+          __builtin_amdgcn_readfirstlane(__float_as_int(lf[F_REC + 4 * (gi & 3) + 3])) != 0;
+      if (ia)
+        sa += sg;
+      else
+        sb += sg;
+    };
+#endif
 
     f32x16s hk[2], dh[2];
     if (XH_SP8_PRIO >> 2) __builtin_amdgcn_s_setprio(XH_SP8_PRIO >> 2);
@@ -1699,8 +1856,12 @@ __global__ __launch_bounds__(kThreads, 2) void policy_train_spec8_kernel(PolicyT
       constexpr int par = decltype(P)::value;
       if (SP8_RUN(2 | 4)) dh_gh(j, par, hk, dh);
       __syncthreads();  // A(j)
+#if SP8_DHB
+      if (SP8_RUN(2)) dh_b(j, par, hk, dh);
+#else
       if (SP8_RUN(2 | 64)) dw1(j, par, hk, dh);
       if (SP8_RUN(2 | 8)) layer1(j + 2);
+#endif
       __syncthreads();  // B(j)
     };
     for (int j = 0; j < J; j += 2) {

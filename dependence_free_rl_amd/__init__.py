@@ -25,7 +25,7 @@ from .trainer import (ALGOS, POLICY, VALUE, Context, Trainer,  # noqa: F401
                       init_policy, init_value,
                       policy_param_count, value_param_count)
 from ._lib import (ACT_ARGMAX, ACT_LOGITS, ACT_PROBS, ACT_SAMPLE,  # noqa: F401
-                   VENV_PCHOICE, VENV_POLICY, VREC_ACTION, VREC_BINS,
+                   VENV_PCHOICE, VENV_POLICY, VOBS_NEXT, VOBS_STATE, VREC_ACTION, VREC_BINS,
                    VREC_COUNT, VREC_DONE, VREC_ITEMS, VREC_PCHOICE,
                    VREC_REWARD)
 from .venv import VecEnv  # noqa: F401

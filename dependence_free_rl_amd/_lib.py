@@ -25,6 +25,9 @@ ACT_SAMPLE, ACT_ARGMAX = 0, 1
 # the trajectory record's arrays (xh_venv_set_record)
 (VREC_ACTION, VREC_PCHOICE, VREC_REWARD, VREC_DONE, VREC_BINS, VREC_ITEMS,
  VREC_COUNT) = range(7)
+# xh_venv_record_obs: the state S_t, or the successor row of transition t
+VOBS_STATE, VOBS_NEXT = 0, 1
+COPY_H2D, COPY_D2H, COPY_D2D = 0, 1, 2
 (BUF_BINS, BUF_ITEMS, BUF_ACTION, BUF_POLD, BUF_DONE, BUF_RNG, BUF_V_STATE,
  BUF_V_TERM, BUF_TARGETS, BUF_ADV, BUF_VALUE_GRAD, BUF_POLICY_GRADS,
  BUF_LOGITS, BUF_PROBS, BUF_V_STATE0, BUF_QOLD, BUF_KL, BUF_LEN) = range(18)
@@ -78,6 +81,16 @@ class Eval(C.Structure):
         ("final_items", C.c_void_p), ("rng_out", C.c_void_p),
         ("totals", C.c_void_p), ("steps", C.c_void_p), ("trace", C.c_void_p),
         ("trace_cap", C.c_long), ("elapsed_ms", C.c_double)]
+
+
+class VenvAdv(C.Structure):
+    """Mirror of xh_venv_adv."""
+    _fields_ = [
+        ("steps", C.c_int), ("values", C.c_void_p), ("v_term", C.c_void_p),
+        ("reward", C.c_void_p), ("done", C.c_void_p), ("gamma", C.c_float),
+        ("lambda_", C.c_float), ("normalize", C.c_int), ("adv", C.c_void_p),
+        ("td_target", C.c_void_p), ("lambda_return", C.c_void_p),
+        ("stats", C.c_void_p)]
 
 
 def _load():
@@ -140,6 +153,9 @@ def _load():
         "xh_venv_record_bytes": (sz, [vp, i]),
         "xh_venv_record_ptr": (vp, [vp, i]),
         "xh_venv_get_record": (i, [vp, i, vp, sz]),
+        "xh_venv_record_obs": (i, [vp, i, vp, C.c_long, C.c_long, vp]),
+        "xh_venv_record_ends": (i, [vp, vp, vp]),
+        "xh_venv_advantages": (i, [vp, C.POINTER(VenvAdv)]),
         "xh_venv_apply": (i, [vp, i]),
         "xh_venv_reset": (i, [vp, i]),
         "xh_venv_observe": (i, [vp]),
@@ -201,8 +217,16 @@ LAYER_FULL, LAYER_CONV1D_1, LAYER_RELU, LAYER_SOFTMAX, LAYER_SOFTMAX_XENT = rang
  LOSS_KL_REGULATED) = range(4)
 
 lib = _load()
+# device scratch of the VecEnv (venv.py): prototypes of their own, so a caller
+# that sets argtypes on lib.xh_tensor_* for its own use does not change them
+tensor_alloc = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_size_t,
+                           C.POINTER(C.c_void_p))(("xh_tensor_alloc", lib))
+tensor_free = C.CFUNCTYPE(C.c_int, C.c_void_p,
+                          C.c_void_p)(("xh_tensor_free", lib))
+tensor_copy = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                          C.c_size_t, C.c_int)(("xh_tensor_copy", lib))
 for _name, _mirror in (("xh_config", Config), ("xh_eval", Eval),
-                       ("xh_layer", Layer)):
+                       ("xh_layer", Layer), ("xh_venv_adv", VenvAdv)):
     if lib.xh_struct_size(_name.encode()) != C.sizeof(_mirror):
         raise ImportError("ctypes mirror of %s is out of date (%d vs %d bytes)"
                           % (_name, C.sizeof(_mirror),

@@ -371,6 +371,48 @@ hipError_t launch_venv_act(const VenvActArgs &a, hipStream_t s);
 hipError_t launch_venv_init(const VenvArgs &a, uint32_t x0, int env_offset,
                             int n_global, int k, hipStream_t s);
 
+// The learner's side of a recorded window (xh_venv_record_obs /
+// xh_venv_advantages, venv_learn_kernels.hip).
+// observation::to_vector of `count` rows of the record: row q = t N + e is
+// slot t of env e (slot P = the present state); next != 0 gives the successor
+// row of transition q (S_t+1, or the terminal view E_t where done[q]).
+struct VenvObsArgs {
+  int B, D, N;
+  int P;                      // the record's cursor
+  int next;                   // XH_VOBS_NEXT
+  const int8_t *rec_bins;     // [P][N][B][D]
+  const int8_t *rec_items;    // [P][N][4]
+  const int8_t *cur_bins;     // [N][B][D] the state after slot P - 1's step
+  const int8_t *cur_items;    // [N][4]
+  const int32_t *rec_action;  // [P][N] (next)
+  const uint8_t *rec_done;    // [P][N] (next)
+  const int32_t *rows;        // index list or nullptr (rows first ..)
+  long first, count;
+  float *obs;                 // [count][B][2D], 16-byte aligned
+  int *err;                   // bit 4: an index outside the view's rows
+};
+hipError_t launch_venv_record_obs(const VenvObsArgs &a, hipStream_t s);
+// GAE, TD(0) targets and lambda returns of a window with explicit rewards:
+// gae_kernel's and value_targets_kernel's arithmetic, one env per lane.
+struct VenvGaeArgs {
+  int N, T;
+  const float *values;    // [T+1][N]
+  const float *v_term;    // [T][N] or nullptr (0)
+  const float *reward;    // [T][N]
+  const uint8_t *done;    // [T][N]
+  float gamma, lambda;
+  float *adv;             // [T][N]
+  float *td_target;       // [T][N] or nullptr
+  float *lambda_return;   // [T][N] or nullptr
+  double *part;           // [venv_gae_grid(N)][2] sum A, sum A^2, or nullptr
+  int *end_part;          // [venv_gae_grid(N)] ended rows (with part)
+};
+int venv_gae_grid(int N);
+hipError_t launch_venv_gae(const VenvGaeArgs &a, hipStream_t s);
+// stats[2] = rows, stats[3] = the sum of end_part (one wave, fixed order)
+hipError_t launch_venv_adv_counts(const int *end_part, int nparts, double rows,
+                                  double *stats, hipStream_t s);
+
 // 1 when the kernels were built with the phase-ablation switches
 // (make diag, -DXH_DIAG_ABLATE=1), 0 in the product library.
 int diag_build();

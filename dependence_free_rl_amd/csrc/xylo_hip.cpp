@@ -74,6 +74,12 @@ struct xh_venv {
   int rec_steps = 0, rec_pos = 0;
   void *rec[XH_VREC_COUNT] = {};
   size_t rec_bytes[XH_VREC_COUNT] = {};
+  // scratch of xh_venv_record_ends / xh_venv_advantages, allocated at their
+  // first use: launch_end_list's block totals and n_open; the scan's block
+  // partials [venv_gae_grid(N)][2], their ended-row counts, and stats [4]
+  int *end_scratch = nullptr;
+  double *adv_part = nullptr, *adv_stats = nullptr;
+  int *adv_end_part = nullptr;
 
   xh::VenvArgs args() const {
     xh::VenvArgs a{};
@@ -1404,6 +1410,7 @@ size_t xh_struct_size(const char *name) {
   if (!std::strcmp(name, "xh_upd_row")) return XH_UPD_COUNT * sizeof(double);
   if (!std::strcmp(name, "xh_state_header")) return sizeof(xh_state_header);
   if (!std::strcmp(name, "xh_state_section")) return sizeof(xh_state_section);
+  if (!std::strcmp(name, "xh_venv_adv")) return sizeof(xh_venv_adv);
   return 0;
 }
 
@@ -2593,6 +2600,8 @@ int xh_venv_destroy(xh_venv *v) {
     for (void *p : v->buf)
       if (p) (void)hipFree(p);
     if (v->err) (void)hipFree(v->err);
+    if (v->end_scratch) (void)hipFree(v->end_scratch);
+    if (v->adv_part) (void)hipFree(v->adv_part);  // adv_stats, adv_end_part too
     venv_free_record(v);
     xh_ctx *c = v->ctx;
     const bool counted = v->counted;
@@ -2625,6 +2634,11 @@ int venv_check_err(xh_venv *v) {
   if (err) {
     HIPCHK(hipMemsetAsync(v->err, 0, 4, v->ctx->stream));
     HIPCHK(hipStreamSynchronize(v->ctx->stream));
+    if (err & 4)
+      return fail(XH_ERR_INVALID, "venv: xh_venv_record_obs met a row index "
+                  "outside its view's rows; those output rows were left "
+                  "untouched%s%s", err & 2 ? ", and a policy row was refused" : "",
+                  err & 1 ? ", and an action was out of range" : "");
     if (err & 2)
       return fail(XH_ERR_INVALID, "venv: a policy row was refused (a NaN, a "
                   "negative probability, or a sum that is zero or not finite)"
@@ -2854,6 +2868,143 @@ int xh_venv_get_record(xh_venv *v, int which, void *host, size_t bytes) {
     HIPCHK(hipSetDevice(v->ctx->device));
     HIPCHK(copy_to_host(host, v->rec[which], bytes, v->ctx->stream));
     HIPCHK(hipStreamSynchronize(v->ctx->stream));
+    return XH_OK;
+  });
+}
+
+// ---- the learner's side of a recorded window (venv_learn_kernels.hip) ----
+int xh_venv_record_obs(xh_venv *v, int view, const int32_t *rows_dev,
+                       long first, long count, float *obs_dev) {
+  return guard([&]() -> int {
+    if (!v) return fail(XH_ERR_INVALID, "null venv");
+    if (view != XH_VOBS_STATE && view != XH_VOBS_NEXT)
+      return fail(XH_ERR_INVALID, "venv record obs: view %d (XH_VOBS_STATE / "
+                  "NEXT)", view);
+    if (!v->rec[XH_VREC_BINS])
+      return fail(XH_ERR_STATE, "venv record obs: %s",
+                  v->rec_steps > 0 ? "the record was made without states "
+                                     "(xh_venv_set_record's with_states)"
+                                   : "no record (xh_venv_set_record)");
+    if (first < 0 || count < 0)
+      return fail(XH_ERR_INVALID, "venv record obs: first %ld, count %ld",
+                  first, count);
+    if (count == 0) return XH_OK;
+    if (!obs_dev || (reinterpret_cast<uintptr_t>(obs_dev) & 15))
+      return fail(XH_ERR_INVALID, "venv record obs: obs_dev must be 16-byte "
+                  "aligned (the kernel writes 16-byte stores)");
+    const long P = v->rec_pos;
+    const long total = (view == XH_VOBS_NEXT ? P : P + 1) * (long)v->N;
+    if (total == 0 || (!rows_dev && first + count > total))
+      return fail(XH_ERR_INVALID, "venv record obs: rows %ld .. %ld of %ld "
+                  "(cursor %ld, %d envs)", first, first + count - 1, total, P,
+                  v->N);
+    HIPCHK(hipSetDevice(v->ctx->device));
+    xh::VenvObsArgs a{};
+    a.B = v->env.B;
+    a.D = v->env.D;
+    a.N = v->N;
+    a.P = (int)P;
+    a.next = view == XH_VOBS_NEXT;
+    a.rec_bins = (const int8_t *)v->rec[XH_VREC_BINS];
+    a.rec_items = (const int8_t *)v->rec[XH_VREC_ITEMS];
+    a.cur_bins = (const int8_t *)v->buf[XH_VENV_BINS];
+    a.cur_items = (const int8_t *)v->buf[XH_VENV_ITEMS];
+    a.rec_action = (const int32_t *)v->rec[XH_VREC_ACTION];
+    a.rec_done = (const uint8_t *)v->rec[XH_VREC_DONE];
+    a.rows = rows_dev;
+    a.first = first;
+    a.count = count;
+    a.obs = obs_dev;
+    a.err = v->err;
+    return venv_timed(
+        v, [&] { return xh::launch_venv_record_obs(a, v->ctx->stream); });
+  });
+}
+
+int xh_venv_record_ends(xh_venv *v, int32_t *list_dev, int32_t *n_dev) {
+  return guard([&]() -> int {
+    if (!v || !list_dev || !n_dev) return fail(XH_ERR_INVALID, "null arg");
+    if (v->rec_steps <= 0)
+      return fail(XH_ERR_STATE, "venv record ends: no record "
+                  "(xh_venv_set_record)");
+    HIPCHK(hipSetDevice(v->ctx->device));
+    hipStream_t s = v->ctx->stream;
+    if (v->rec_pos == 0) {  // nothing recorded: an empty list
+      HIPCHK(hipMemsetAsync(n_dev, 0, 4, s));
+      return XH_OK;
+    }
+    const int ns = xh::end_list_scratch_ints(v->N);
+    if (!v->end_scratch)
+      HIPCHK(hipMalloc((void **)&v->end_scratch, (size_t)(ns + 1) * 4));
+    xh::EndListArgs ea{(const uint8_t *)v->rec[XH_VREC_DONE], v->N, v->rec_pos,
+                       list_dev, n_dev, v->end_scratch + ns, nullptr, 0};
+    return venv_timed(
+        v, [&] { return xh::launch_end_list(ea, v->end_scratch, s); });
+  });
+}
+
+int xh_venv_advantages(xh_venv *v, const xh_venv_adv *p) {
+  return guard([&]() -> int {
+    if (!v || !p) return fail(XH_ERR_INVALID, "null arg");
+    if (p->steps < 0)
+      return fail(XH_ERR_INVALID, "venv advantages: steps %d", p->steps);
+    if (!p->values || !p->adv)
+      return fail(XH_ERR_INVALID, "venv advantages: null values / adv");
+    xh::VenvGaeArgs a{};
+    a.N = v->N;
+    a.T = p->steps;
+    a.reward = p->reward;
+    a.done = p->done;
+    if (p->steps == 0) {  // the record's window
+      if (v->rec_steps <= 0)
+        return fail(XH_ERR_STATE, "venv advantages: steps 0 takes the "
+                    "record's window and there is no record "
+                    "(xh_venv_set_record)");
+      a.T = v->rec_pos;
+      if (!a.reward) a.reward = (const float *)v->rec[XH_VREC_REWARD];
+      if (!a.done) a.done = (const uint8_t *)v->rec[XH_VREC_DONE];
+    } else if (!a.reward || !a.done) {
+      return fail(XH_ERR_INVALID, "venv advantages: a window of %d steps of "
+                  "the caller's own needs reward and done", p->steps);
+    }
+    if (a.T == 0)
+      return fail(XH_ERR_STATE, "venv advantages: the record is empty");
+    a.values = p->values;
+    a.v_term = p->v_term;
+    a.gamma = p->gamma;
+    a.lambda = p->lambda;
+    a.adv = p->adv;
+    a.td_target = p->td_target;
+    a.lambda_return = p->lambda_return;
+    HIPCHK(hipSetDevice(v->ctx->device));
+    hipStream_t s = v->ctx->stream;
+    const int grid = xh::venv_gae_grid(v->N);
+    const bool sums = p->normalize || p->stats;
+    if (sums && !v->adv_part) {  // partials, stats [4], ended-row counts
+      HIPCHK(hipMalloc((void **)&v->adv_part,
+                       (size_t)grid * 16 + 32 + (size_t)grid * 4));
+      v->adv_stats = v->adv_part + 2 * (size_t)grid;
+      v->adv_end_part = reinterpret_cast<int *>(v->adv_stats + 4);
+    }
+    if (sums) {
+      a.part = v->adv_part;
+      a.end_part = v->adv_end_part;
+    }
+    CHK(venv_timed(v, [&] { return xh::launch_venv_gae(a, s); }));
+    if (!sums) return XH_OK;
+    const double rows = (double)a.T * (double)v->N;
+    hipError_t e = xh::launch_adv_stats(v->adv_part, grid, v->adv_stats, s);
+    if (e == hipSuccess)
+      e = xh::launch_venv_adv_counts(v->adv_end_part, grid, rows, v->adv_stats,
+                                     s);
+    if (e == hipSuccess && p->normalize)
+      e = xh::launch_adv_normalize(p->adv, (long)a.T * v->N, v->adv_stats, rows,
+                                   s);
+    if (e != hipSuccess)
+      return fail(XH_ERR_HIP, "venv advantages: %s", hipGetErrorString(e));
+    if (p->stats)
+      HIPCHK(hipMemcpyAsync(p->stats, v->adv_stats, 32,
+                            hipMemcpyDeviceToDevice, s));
     return XH_OK;
   });
 }

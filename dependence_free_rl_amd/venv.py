@@ -30,8 +30,8 @@ from . import _lib
 from ._lib import (ACT_ARGMAX, ACT_LOGITS, ACT_PROBS, ACT_SAMPLE, VENV_ACTIONS,
                    VENV_BINS, VENV_DONE, VENV_ITEMS, VENV_MASK, VENV_OBS,
                    VENV_PCHOICE, VENV_POLICY, VENV_REWARD, VENV_RNG,
-                   VREC_ACTION, VREC_BINS, VREC_DONE, VREC_ITEMS, VREC_PCHOICE,
-                   VREC_REWARD, check)
+                   VOBS_NEXT, VOBS_STATE, VREC_ACTION, VREC_BINS, VREC_DONE,
+                   VREC_ITEMS, VREC_PCHOICE, VREC_REWARD, check)
 
 _KINDS = {"probs": ACT_PROBS, "logits": ACT_LOGITS}
 _MODES = {"sample": ACT_SAMPLE, "argmax": ACT_ARGMAX}
@@ -49,6 +49,7 @@ class VecEnv:
         self.ctx = ctx
         self.N, self.B, self.D = num_envs, bins, dims
         self.h = C.c_void_p()
+        self._dev = {}  # device scratch: name -> (address, bytes)
         check(_lib.lib.xh_venv_create(ctx.h, num_envs, bins, dims, rng_state,
                                       env_offset, num_envs_global or num_envs,
                                       policy_draws, C.byref(self.h)))
@@ -148,6 +149,155 @@ class VecEnv:
         """The next act() writes slot 0 again (xh_venv_record_rewind)."""
         check(_lib.lib.xh_venv_record_rewind(self.h))
 
+    # ---- from the record to the learner's minibatches, on the device ------
+    def _scratch(self, name, nbytes):
+        """A device block of at least nbytes (xh_tensor_alloc) kept under
+        `name` until close(); grown by reallocation."""
+        have = self._dev.get(name)
+        if have and have[1] >= nbytes:
+            return have[0]
+        if have:
+            check(_lib.tensor_free(self.ctx.h, have[0]))
+            del self._dev[name]
+        p = C.c_void_p()
+        n = (max(nbytes, 16) + 3) // 4
+        check(_lib.tensor_alloc(self.ctx.h, n, C.byref(p)))
+        self._dev[name] = (p.value, 4 * n)
+        return p.value
+
+    def _upload(self, ptr, a):
+        raw = np.zeros((a.nbytes + 3) // 4 * 4, np.uint8)
+        raw[:a.nbytes] = a.reshape(-1).view(np.uint8)
+        check(_lib.tensor_copy(self.ctx.h, ptr, _ptr(raw), raw.size // 4,
+                               _lib.COPY_H2D))
+
+    def _download(self, ptr, dtype, shape):
+        out = np.zeros(shape, dtype)
+        raw = np.zeros((out.nbytes + 3) // 4 * 4, np.uint8)
+        if raw.size:
+            check(_lib.tensor_copy(self.ctx.h, _ptr(raw), ptr, raw.size // 4,
+                                   _lib.COPY_D2H))
+        out.reshape(-1).view(np.uint8)[:] = raw[:out.nbytes]
+        return out
+
+    def _staged(self, name, arr, dtype, shape):
+        """The device address of `arr`: an integer is one already, a host
+        array is uploaded into the scratch block `name`."""
+        if arr is None:
+            return None
+        if isinstance(arr, (int, np.integer)):
+            return int(arr)
+        a = np.ascontiguousarray(arr, dtype)
+        if a.shape != shape:
+            raise ValueError("%s: shape %s, expected %s" % (name, a.shape,
+                                                            shape))
+        ptr = self._scratch(name, a.nbytes)
+        self._upload(ptr, a)
+        return ptr
+
+    def record_obs(self, view="state", rows=None, first=0, count=None,
+                   out=None):
+        """observation::to_vector of recorded rows (xh_venv_record_obs), row
+        index q = t * N + e.  view "state": S_t of slot t in [0, P], slot P the
+        present state; "next": the successor row of transition q -- S_t+1, or
+        the terminal view E_t where the row ended.  rows: None (the rows
+        first .. first + count - 1), a host int array (uploaded) or an integer
+        device pointer to int32 indices, of which first .. first + count - 1
+        are taken.  out: an integer device pointer (16-byte aligned; nothing
+        is returned), or None for a host array [count][B][2D] float32."""
+        view_id = {"state": VOBS_STATE, "next": VOBS_NEXT}[view]
+        N, B, D = self.N, self.B, self.D
+        rows_ptr = None
+        if rows is None:
+            if count is None:
+                P = self.record_pos()
+                count = (P + 1 if view_id == VOBS_STATE else P) * N - first
+        elif isinstance(rows, (int, np.integer)):
+            if count is None:
+                raise ValueError("record_obs: count is needed with a device "
+                                 "pointer to the rows")
+            rows_ptr = int(rows)
+        else:
+            r = np.ascontiguousarray(rows, np.int32).reshape(-1)
+            if count is None:
+                count = r.size - first
+            if first < 0 or count < 0 or first + count > r.size:
+                raise ValueError("record_obs: rows %d .. %d of a list of %d"
+                                 % (first, first + count - 1, r.size))
+            rows_ptr = self._scratch("rows", r.nbytes)
+            self._upload(rows_ptr, r)
+        dst = out if out is not None else self._scratch(
+            "obs", count * B * 2 * D * 4)
+        check(_lib.lib.xh_venv_record_obs(self.h, view_id, rows_ptr, first,
+                                          count, dst))
+        if out is not None:
+            return None
+        return self._download(dst, np.float32, (count, B, 2 * D))
+
+    def record_ends(self):
+        """The ended transitions of the recorded slots (xh_venv_record_ends):
+        int32 indices t * N + e, env-major (e ascending, then t)."""
+        cap = max(self.record_pos() * self.N, 1)
+        p = self._scratch("ends", (cap + 1) * 4)
+        check(_lib.lib.xh_venv_record_ends(self.h, p + 4, p))
+        got = self._download(p, np.int32, (cap + 1,))
+        return got[1:1 + got[0]].copy()
+
+    def advantages(self, values, v_term=None, reward=None, done=None,
+                   gamma=0.99, lam=0.95, normalize=False,
+                   returns=("adv", "td_target"), steps=None):
+        """GAE, TD(0) targets and lambda returns on the device
+        (xh_venv_advantages).  Without reward and done the window is the
+        record's P slots; with both it is the caller's own, [steps][N].
+        values [steps+1][N] and v_term [steps][N] (None: 0) are host arrays or
+        integer device pointers, as reward (float32) and done (uint8) are;
+        the window's length is `steps`, or the first dimension of the first
+        host array among reward, done and values.  normalize covers this
+        venv's rows only.  Returns a
+        dict of host arrays [steps][N] for the names in `returns` ("adv",
+        "td_target", "lambda_return") plus "stats": float64 [4] = sum A, sum
+        A^2 (before normalisation), rows, ended rows."""
+        N = self.N
+        own = reward is not None or done is not None
+        if own and (reward is None or done is None):
+            raise ValueError("advantages: reward and done go together")
+        if own and steps is not None:
+            T = int(steps)
+        elif own:
+            for a in (reward, done, values):
+                if not isinstance(a, (int, np.integer)):
+                    n = np.asarray(a).shape[0]
+                    T = n - 1 if a is values else n
+                    break
+            else:
+                raise ValueError("advantages: with device pointers only, "
+                                 "pass steps")
+        else:
+            T = self.record_pos()
+        names = ("adv", "td_target", "lambda_return")
+        bad = set(returns) - set(names)
+        if bad:
+            raise ValueError("advantages: returns %s" % sorted(bad))
+        a = _lib.VenvAdv()
+        a.steps = T if own else 0
+        a.values = self._staged("values", values, np.float32, (T + 1, N))
+        a.v_term = self._staged("v_term", v_term, np.float32, (T, N))
+        a.reward = self._staged("reward", reward, np.float32, (T, N))
+        a.done = self._staged("done", done, np.uint8, (T, N))
+        a.gamma, a.lambda_, a.normalize = gamma, lam, 1 if normalize else 0
+        # one block: [adv | td_target | lambda_return | stats], 16-byte parts
+        part = (T * N * 4 + 15) // 16 * 16
+        base = self._scratch("adv", 3 * part + 32)
+        a.adv = base
+        a.td_target = base + part if "td_target" in returns else None
+        a.lambda_return = base + 2 * part if "lambda_return" in returns else None
+        a.stats = base + 3 * part
+        check(_lib.lib.xh_venv_advantages(self.h, C.byref(a)))
+        out = {n: self._download(base + k * part, np.float32, (T, N))
+               for k, n in enumerate(names) if n in returns}
+        out["stats"] = self._download(base + 3 * part, np.float64, (4,))
+        return out
+
     def apply(self, mask=None):
         """environment::apply(actions[e], e) for the masked envs (no reset);
         returns game_over per env ([N] uint8; 0 for the envs not applied)."""
@@ -189,6 +339,9 @@ class VecEnv:
         if self.h:
             check(_lib.lib.xh_venv_destroy(self.h))
             self.h = C.c_void_p()
+            for ptr, _ in self._dev.values():
+                check(_lib.tensor_free(self.ctx.h, ptr))
+            self._dev = {}
 
     def __del__(self):
         try:

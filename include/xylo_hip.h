@@ -712,6 +712,73 @@ int xh_venv_record_rewind(xh_venv *v);
 size_t xh_venv_record_bytes(const xh_venv *v, int which);
 void *xh_venv_record_ptr(xh_venv *v, int which);
 int xh_venv_get_record(xh_venv *v, int which, void *host, size_t bytes);
+/* From a recorded window to the learner's minibatches, on the device.  P is
+ * the record's cursor (xh_venv_record_pos), a row index is q = t N + e.  The
+ * three calls are asynchronous on the context's stream; their pointer
+ * arguments are device memory on the context's device, the caller's writes to
+ * them ordered before the call.  They read the record and the venv's present
+ * state and change neither.
+ *
+ * xh_venv_record_obs writes obs_dev[count][B][2D] f32, observation::to_vector
+ * (eighths: exact) of the rows first .. first + count - 1 (rows_dev == NULL)
+ * or of the rows rows_dev[first .. first + count - 1] (a shuffled minibatch).
+ *   XH_VOBS_STATE: S_t from the record's slot t, t in [0, P]; slot P is the
+ *     venv's present state (XH_VENV_BINS / ITEMS), the state after the last
+ *     recorded step.
+ *   XH_VOBS_NEXT: the successor row replay_buffer::sample_td gives transition
+ *     q, t in [0, P): S_t+1 where DONE[q] == 0; where the row ended the
+ *     terminal view E_t, slot t's bins with bins[ACTION[q]] -= item, shown
+ *     with slot t's item (the state the value net must see for it).
+ * XH_ERR_STATE without a record that holds the states (with_states == 0),
+ * XH_ERR_INVALID if obs_dev is not 16-byte aligned (the kernel writes 16-byte
+ * stores).  An index in rows_dev outside the view's rows leaves its output
+ * row untouched and is reported by the next xh_venv_synchronize / get as
+ * XH_ERR_INVALID, as an out-of-range action is.
+ *
+ * xh_venv_record_ends writes the ended transitions of slots [0, P): list_dev
+ * [j] = t N + e, env-major (e ascending, then t), and *n_dev = their count.
+ * list_dev holds P N ints.  Its scratch is allocated at the first call and
+ * freed with the venv.
+ *
+ * xh_venv_advantages: generalised advantage estimates, TD(0) targets and
+ * lambda returns of a window, all in f32, one rounding per operation:
+ *     lg    = lambda * gamma
+ *     vn    = done ? 0 : V(S_t+1)
+ *     delta = (r + gamma * vn) - V(S_t)
+ *     A_t   = done ? delta : delta + lg * A_t+1        (A_steps = 0)
+ *     td_target_t     = r + gamma * (done ? v_term : V(S_t+1))
+ *     lambda_return_t = A_t + V(S_t)                   (A_t un-normalised)
+ * With the venv's own rewards (1, or 0 on the step that ended) these are the
+ * trainer's advantages and value targets bit for bit.  normalize: A <- (A -
+ * mean) / (std + 1e-8), population mean and std over the window's steps * N
+ * rows, in double and rounded once.  It covers THIS venv's rows only: a job
+ * sharded over several venvs (env_offset) normalises each shard by its own
+ * moments; nothing is all-reduced.  stats' sums are in double in a fixed
+ * order (no floating-point atomics): the same inputs give the same bits.
+ * A row xh_venv_act refused has reward 0 and done 0 in the record and is
+ * treated as any other row.
+ * XH_ERR_INVALID: steps < 0, steps > 0 without reward and done, a null
+ * values / adv; XH_ERR_STATE: steps == 0 without a record. */
+enum { XH_VOBS_STATE = 0, XH_VOBS_NEXT = 1 };
+typedef struct {
+  int steps;               /* 0: the record's P slots; > 0: a window of the
+                              caller's own, reward and done both required */
+  const float   *values;   /* [steps+1][N]  V(S_0 .. S_steps)               */
+  const float   *v_term;   /* [steps][N] V(E_t), read only where done; NULL: 0 */
+  const float   *reward;   /* [steps][N] or NULL: the record's              */
+  const uint8_t *done;     /* [steps][N] or NULL: the record's              */
+  float gamma, lambda;
+  int normalize;           /* 1: A <- (A - mean)/(std + 1e-8) over steps*N rows */
+  float *adv;              /* [steps][N] out                                */
+  float *td_target;        /* out or NULL: r + gamma*(done ? v_term : V(S_t+1)) */
+  float *lambda_return;    /* out or NULL: A_t (un-normalised) + V(S_t)     */
+  double *stats;           /* out or NULL, device [4]: sum A, sum A^2 (both
+                              before normalisation), rows, ended rows       */
+} xh_venv_adv;             /* xh_struct_size("xh_venv_adv") */
+int xh_venv_record_obs(xh_venv *v, int view, const int32_t *rows_dev,
+                       long first, long count, float *obs_dev);
+int xh_venv_record_ends(xh_venv *v, int32_t *list_dev, int32_t *n_dev);
+int xh_venv_advantages(xh_venv *v, const xh_venv_adv *a);
 /* environment::apply(ACTIONS[e], e) for the envs selected by MASK (all if
  * use_mask == 0), no reset; DONE[e] = game_over after the apply, 0 for the
  * envs this call did not apply (masked out, or an out-of-range action). */
@@ -720,13 +787,17 @@ int xh_venv_apply(xh_venv *v, int use_mask);
 int xh_venv_reset(xh_venv *v, int use_mask);
 /* observation::to_vector of every env into OBS. */
 int xh_venv_observe(xh_venv *v);
-/* Waits for the venv's work; XH_ERR_INVALID if an action was out of range or
- * xh_venv_act refused a policy row. */
+/* Waits for the venv's work; XH_ERR_INVALID if an action was out of range,
+ * xh_venv_act refused a policy row or xh_venv_record_obs met an index outside
+ * its view's rows. */
 int xh_venv_synchronize(xh_venv *v);
 /* Kernel timing: on != 0 brackets every later step / act / apply / reset /
  * observe launch with HIP events on the context's stream (and drops the
  * events recorded so far); xh_venv_kernel_time returns their accumulated
- * milliseconds and the launch count. */
+ * milliseconds and the launch count.  xh_venv_record_obs and
+ * xh_venv_record_ends are one bracket each; xh_venv_advantages is one
+ * bracket around the scan (venv_gae_kernel) alone -- its statistics and
+ * normalisation launches are not timed. */
 int xh_venv_set_timing(xh_venv *v, int on);
 int xh_venv_kernel_time(xh_venv *v, double *ms, long *launches);
 

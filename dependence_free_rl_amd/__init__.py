@@ -28,6 +28,10 @@ from ._lib import (ACT_ARGMAX, ACT_LOGITS, ACT_PROBS, ACT_SAMPLE,  # noqa: F401
                    VENV_PCHOICE, VENV_POLICY, VOBS_NEXT, VOBS_STATE, VREC_ACTION, VREC_BINS,
                    VREC_COUNT, VREC_DONE, VREC_ITEMS, VREC_PCHOICE,
                    VREC_REWARD)
+from ._lib import (VLOSS_CLIPPED, VLOSS_COUNT, VLOSS_ENTROPY_SUM,  # noqa: F401
+                   VLOSS_K3_SUM, VLOSS_LOGR_SQSUM, VLOSS_LOGR_SUM, VLOSS_ROWS,
+                   VLOSS_SKIPPED, VLOSS_SURR_SUM, VLOSS_VERR_SQSUM,
+                   VLOSS_VERR_SUM)
 from .venv import VecEnv  # noqa: F401
 
 __all__ = ["Context", "Trainer", "POLICY", "VALUE", "init_policy", "init_value",

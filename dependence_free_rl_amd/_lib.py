@@ -27,6 +27,10 @@ ACT_SAMPLE, ACT_ARGMAX = 0, 1
  VREC_COUNT) = range(7)
 # xh_venv_record_obs: the state S_t, or the successor row of transition t
 VOBS_STATE, VOBS_NEXT = 0, 1
+# the statistics of xh_venv_policy_loss (the XH_VLOSS_* enum)
+(VLOSS_ROWS, VLOSS_SKIPPED, VLOSS_LOGR_SUM, VLOSS_LOGR_SQSUM, VLOSS_K3_SUM,
+ VLOSS_CLIPPED, VLOSS_SURR_SUM, VLOSS_ENTROPY_SUM, VLOSS_VERR_SUM,
+ VLOSS_VERR_SQSUM, VLOSS_COUNT) = range(11)
 COPY_H2D, COPY_D2H, COPY_D2D = 0, 1, 2
 (BUF_BINS, BUF_ITEMS, BUF_ACTION, BUF_POLD, BUF_DONE, BUF_RNG, BUF_V_STATE,
  BUF_V_TERM, BUF_TARGETS, BUF_ADV, BUF_VALUE_GRAD, BUF_POLICY_GRADS,
@@ -93,6 +97,19 @@ class VenvAdv(C.Structure):
         ("stats", C.c_void_p)]
 
 
+class VenvLoss(C.Structure):
+    """Mirror of xh_venv_loss."""
+    _fields_ = [
+        ("policy", C.c_void_p), ("kind", C.c_int), ("loss", C.c_int),
+        ("rows_dev", C.c_void_p), ("first", C.c_long), ("count", C.c_long),
+        ("adv", C.c_void_p), ("action", C.c_void_p), ("p_old", C.c_void_p),
+        ("total", C.c_long), ("eps", C.c_float), ("scale", C.c_float),
+        ("values_new", C.c_void_p), ("target", C.c_void_p),
+        ("value_scale", C.c_float), ("grad", C.c_void_p),
+        ("dvalue", C.c_void_p), ("probs_out", C.c_void_p),
+        ("stats", C.c_void_p), ("accumulate", C.c_int)]
+
+
 def _load():
     if not os.path.exists(LIB_PATH):
         raise ImportError(
@@ -156,6 +173,7 @@ def _load():
         "xh_venv_record_obs": (i, [vp, i, vp, C.c_long, C.c_long, vp]),
         "xh_venv_record_ends": (i, [vp, vp, vp]),
         "xh_venv_advantages": (i, [vp, C.POINTER(VenvAdv)]),
+        "xh_venv_policy_loss": (i, [vp, C.POINTER(VenvLoss)]),
         "xh_venv_apply": (i, [vp, i]),
         "xh_venv_reset": (i, [vp, i]),
         "xh_venv_observe": (i, [vp]),
@@ -226,7 +244,8 @@ tensor_free = C.CFUNCTYPE(C.c_int, C.c_void_p,
 tensor_copy = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                           C.c_size_t, C.c_int)(("xh_tensor_copy", lib))
 for _name, _mirror in (("xh_config", Config), ("xh_eval", Eval),
-                       ("xh_layer", Layer), ("xh_venv_adv", VenvAdv)):
+                       ("xh_layer", Layer), ("xh_venv_adv", VenvAdv),
+                       ("xh_venv_loss", VenvLoss)):
     if lib.xh_struct_size(_name.encode()) != C.sizeof(_mirror):
         raise ImportError("ctypes mirror of %s is out of date (%d vs %d bytes)"
                           % (_name, C.sizeof(_mirror),

@@ -16,6 +16,7 @@
 // row first -- react's sampling -- and writes the trajectory record.
 #include "xh_device.h"
 #include "xh_kernels.h"
+#include "xh_seg.h"
 
 namespace xh {
 
@@ -237,23 +238,11 @@ __global__ __launch_bounds__(256) void venv_step_kernel(VenvArgs a) {
 //
 // Logits: p_j = e_j / se with e_j = expf(z_j - m), m the row's maximum, all
 // f32; se adds the lane's e_j in bin order, then the env's lanes' sums by
-// seg_sum's xor butterfly (partners 1, 2, 4).
+// seg_sum's xor butterfly (partners 1, 2, 4): seg_softmax (xh_seg.h), the
+// text venv_policy_loss_kernel compiles too.
 //
 // A row is refused (env untouched, DONE 0, error bit 2) when a probability is
 // NaN or negative or the double-precision sum is zero or not finite.
-template <int S>
-__device__ __forceinline__ float seg_max(float v) {
-#pragma unroll
-  for (int o = 1; o < S; o <<= 1) v = fmaxf(v, __shfl_xor(v, o, kWave));
-  return v;
-}
-template <int S>
-__device__ __forceinline__ int seg_sum_i(int v) {
-#pragma unroll
-  for (int o = 1; o < S; o <<= 1) v += __shfl_xor(v, o, kWave);
-  return v;
-}
-
 template <int B, int D>
 __global__ __launch_bounds__(256) void venv_act_kernel(VenvActArgs a) {
   using S = VStepShape<B, D>;
@@ -292,19 +281,7 @@ __global__ __launch_bounds__(256) void venv_act_kernel(VenvActArgs a) {
   // the row's probabilities
   float p[S::BPL];
   if (a.logits) {
-    float m = z[0];
-#pragma unroll
-    for (int k = 1; k < S::BPL; ++k) m = fmaxf(m, z[k]);
-    m = seg_max<S::LPE>(m);
-    float se = 0.0f;
-#pragma unroll
-    for (int k = 0; k < S::BPL; ++k) {
-      p[k] = expf(z[k] - m);
-      se += p[k];
-    }
-    se = seg_sum<S::LPE>(se);
-#pragma unroll
-    for (int k = 0; k < S::BPL; ++k) p[k] = p[k] / se;
+    seg_softmax<S::LPE, S::BPL>(z, p);  // xh_seg.h
   } else {
 #pragma unroll
     for (int k = 0; k < S::BPL; ++k) p[k] = z[k];

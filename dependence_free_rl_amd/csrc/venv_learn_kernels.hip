@@ -17,6 +17,7 @@
 // + 4 T read (+ 4 T with v_term), 4 T written per output.
 #include "xh_device.h"
 #include "xh_kernels.h"
+#include "xh_sums.h"
 
 namespace xh {
 
@@ -137,24 +138,14 @@ __global__ __launch_bounds__(256) void venv_record_obs_kernel(VenvObsArgs a) {
   }
 }
 
-// s += x in double with the rounding error kept (Knuth's two-sum): c collects
-// what the additions lose, so a lane's sum over any number of steps carries
-// one rounding, not one per step
-__device__ __forceinline__ void sum2(double &s, double &c, double x) {
-  const double t = s + x;
-  const double bb = t - s;
-  c += (s - (t - bb)) + (x - bb);
-  s = t;
-}
-
 // One env per lane, a reverse scan over T in chunks of 8 steps, latest first:
 // every load of a chunk (done, reward, v_term and the 9 values V(S_hi+1) ..
 // V(S_hi-7)) is issued before the chunk's arithmetic and unconditionally, as
 // gae_kernel does, so a chunk costs one HBM round trip.  adv, td_target and
 // lambda_return are written in the same pass.  part != nullptr: the block's
-// sum and sum of squares of its advantages in double (lane sums compensated,
-// then the wave by shuffles and the block's four waves in LDS, fixed order),
-// and the block's count of ended rows.
+// sum and sum of squares of its advantages in double (lane sums compensated
+// by xh_sums.h's sum2, then the wave by shuffles and the block's four waves in
+// LDS, fixed order), and the block's count of ended rows.
 __global__ __launch_bounds__(256) void venv_gae_kernel(VenvGaeArgs a) {
 #pragma clang fp contract(off)
   const int N = a.N, T = a.T;

@@ -1,0 +1,304 @@
+// venv_loss_kernels.hip -- the PPO / actor-critic loss head of a caller's own
+// network on a window xh_venv_act recorded (xh_venv_policy_loss, include/
+// xylo_hip.h): from the network's output rows of a minibatch to dL/d(output)
+// in one launch, without leaving HBM:
+//   venv_policy_loss_kernel  per output row j: the index q (a shuffle list's
+//                            entry or first + j), the gather of action[q],
+//                            p_old[q], adv[q] (and target[q]), venv_act_kernel's
+//                            softmax of a row of logits (seg_softmax, xh_seg.h:
+//                            one text, so p[choice] has the record's bits while
+//                            the parameters have not moved), policy_loss
+//                            (rl.h:44-52) or clipped_gradient (rl.h:54-74) in
+//                            action_loss_kernel's expressions, softmax_layer::
+//                            backward (nn.h:393-416) on the one-hot backprop for
+//                            logits, square_loss_grad (nn.h:548-550) for the
+//                            value head, and the row's diagnostics (diag_terms,
+//                            xh_diag.h) in double;
+//   venv_loss_reduce_kernel  the call's totals from the block partials, one
+//                            wave, fixed order; no floating-point atomics.
+// HBM-bound.  Bytes per row: 4 B read (the output row), 4 B written (the
+// gradient), another 4 B with probs_out, and about 20 gathered (the index,
+// action, p_old, adv, target; + 8 with the value head's values_new / dvalue).
+#include "xh_device.h"
+#include "xh_diag.h"
+#include "xh_kernels.h"
+#include "xh_seg.h"
+#include "xh_sums.h"
+#include "../../include/xylo_hip.h"
+
+namespace xh {
+
+// venv_act_kernel's layout (VStepShape): a lane owns 16 consecutive bins of a
+// row (all 8 at 8 bins) -- their floats as 16-byte loads in and 16-byte stores
+// out -- so B / 16 lanes share a row and a wave covers 64 / (B / 16) rows.
+// The stores are venv_record_obs_kernel's: a lane's 16 floats are one 64-byte
+// run, and stored from the lane that made them every instruction would touch
+// 64 lines; the wave's rows are consecutive, so its output is one contiguous
+// block, exchanged through LDS and stored as whole lines, nontemporal (the
+// gradient is read once, by the caller's backward).  -DXH_VLOSS_OWNER_STORES=1
+// (make variant VSRC=venv_loss_kernels) stores from the owning lanes instead;
+// the two times are in DESIGN.md 3.2.
+#ifndef XH_VLOSS_OWNER_STORES
+#define XH_VLOSS_OWNER_STORES 0
+#endif
+typedef float vl_f4 __attribute__((ext_vector_type(4)));
+
+template <int B>
+struct VLossShape {
+  static constexpr int BPL = 16 < B ? 16 : B;  // bins per lane
+  static constexpr int LPE = B / BPL;          // lanes per row
+  static constexpr int RPW = 64 / LPE;         // rows per wave
+  static constexpr int F4 = BPL / 4;           // 16-byte pieces per lane
+};
+
+// The wave's [RPW][B] block at `ob` from the lanes' f[BPL]: lane l holds the
+// pieces l F4 .. l F4 + F4 - 1 of the block; instruction i stores piece 64 i +
+// l from lane l.  rows_live bit l: lane l's row is stored.  Every lane of the
+// workgroup reaches the barriers.
+template <int B>
+__device__ __forceinline__ void vloss_store(const float *f, vl_f4 *stage,
+                                            int lane,
+                                            unsigned long long rows_live,
+                                            vl_f4 *ob) {
+  constexpr int G = VLossShape<B>::F4;
+#if XH_VLOSS_OWNER_STORES
+  if ((rows_live >> lane) & 1)
+#pragma unroll
+    for (int g = 0; g < G; ++g) {
+      const vl_f4 x = {f[4 * g], f[4 * g + 1], f[4 * g + 2], f[4 * g + 3]};
+      ob[lane * G + g] = x;
+    }
+#else
+  __syncthreads();  // the previous block's pieces have been read
+#pragma unroll
+  for (int g = 0; g < G; ++g) {
+    const vl_f4 x = {f[4 * g], f[4 * g + 1], f[4 * g + 2], f[4 * g + 3]};
+    stage[lane * G + (g + lane) % G] = x;  // rotated: LDS banks
+  }
+  __syncthreads();
+#pragma unroll
+  for (int i = 0; i < G; ++i) {
+    const int p = i * 64 + lane, lp = p / G, gg = p % G;
+    if ((rows_live >> lp) & 1) {
+      const vl_f4 x = stage[lp * G + (gg + lp) % G];
+      __builtin_nontemporal_store(x, ob + p);
+    }
+  }
+#endif
+}
+
+// A tile is the 4 RPW consecutive rows of a workgroup's four waves; the
+// workgroups stride over the tiles, so a wave reads all RPW rows of its block
+// before it stores any of them and no other wave touches them: grad may be
+// policy itself.  Lanes past the last row load nothing and store nothing.
+// STATS: the instantiation that forms the statistics (a.part != nullptr); the
+// other one carries neither the double-precision logarithms nor the sums'
+// registers.
+template <int B, bool STATS>
+__global__ __launch_bounds__(256) void venv_policy_loss_kernel(VenvLossArgs a) {
+#pragma clang fp contract(off)
+  using S = VLossShape<B>;
+  const int lane = threadIdx.x & 63, wib = threadIdx.x >> 6;
+  const int el = lane / S::LPE, li = lane % S::LPE;
+  const int seg0 = el * S::LPE;
+  __shared__ vl_f4 stage[4][64 * S::F4];
+  // the lane's sums and what their additions lost (sum2)
+  double st[XH_VLOSS_COUNT], sc[XH_VLOSS_COUNT];
+#pragma unroll
+  for (int k = 0; k < XH_VLOSS_COUNT; ++k) st[k] = sc[k] = 0.0;
+
+  for (long tile = blockIdx.x; tile < a.tiles; tile += gridDim.x) {
+    const long wbase = (tile * 4 + wib) * S::RPW;
+    const long j = wbase + el;
+    const bool in_range = j < a.count;
+    float z[S::BPL];
+#pragma unroll
+    for (int k = 0; k < S::BPL; ++k) z[k] = 0.0f;
+    int ch = 0, ok = 0;
+    float q_old = 0.0f, A = 0.0f, tg = 0.0f, vn = 0.0f;
+    if (in_range) {
+      const vl_f4 *zp = reinterpret_cast<const vl_f4 *>(
+          __builtin_assume_aligned(a.policy + (size_t)j * B + li * S::BPL, 16));
+#pragma unroll
+      for (int w = 0; w < S::F4; ++w) {
+        const vl_f4 t = zp[w];
+        z[4 * w] = t.x;
+        z[4 * w + 1] = t.y;
+        z[4 * w + 2] = t.z;
+        z[4 * w + 3] = t.w;
+      }
+      if (li == 0) {  // the row's gathers: one lane, 4-byte loads
+        const long qr = a.rows ? (long)a.rows[a.first + j] : a.first + j;
+        const bool qok = qr >= 0 && qr < a.total;
+        const long q = qok ? qr : 0;
+        ch = a.action[q];
+        q_old = a.p_old[q];
+        A = a.adv[q];
+        if (a.values_new) {
+          tg = a.target[q];
+          vn = a.values_new[j];
+        }
+        ok = qok && ch >= 0 && ch < B;
+        if (!ok) atomicOr(a.err, 4);  // row j of every output stays untouched
+      }
+    }
+    if constexpr (S::LPE > 1) {  // to the row's other lanes
+      ch = __shfl(ch, seg0, kWave);
+      ok = __shfl(ok, seg0, kWave);
+      q_old = wave_shfl(q_old, seg0);
+      A = wave_shfl(A, seg0);
+    }
+    const bool valid = in_range && ok;
+    const int chc = valid ? ch : 0;
+
+    float p[S::BPL];
+    if (a.logits) {
+      seg_softmax<S::LPE, S::BPL>(z, p);
+    } else {
+#pragma unroll
+      for (int k = 0; k < S::BPL; ++k) p[k] = z[k];
+    }
+    float pmine = p[0];
+#pragma unroll
+    for (int k = 1; k < S::BPL; ++k) pmine = k == (chc % S::BPL) ? p[k] : pmine;
+    const float p_ch = wave_shfl(pmine, seg0 + chc / S::BPL);
+    // a row xh_venv_act refused: its record entries are zero
+    const bool skipped = !(q_old > 0.0f);
+
+    float g[S::BPL];
+    if (a.loss == kLossSoftmaxGradientLog) {
+      // output = input * advantage; output[choice] -= advantage (rl.h:44-52);
+      // through softmax_cross_entropy the same row is the logits' gradient
+#pragma unroll
+      for (int k = 0; k < S::BPL; ++k) {
+        float v = p[k] * A;
+        if (li * S::BPL + k == chc) v = v - A;
+        g[k] = v;
+      }
+    } else {  // rl.h:54-74 in action_loss_kernel's expressions
+      const float ratio = p_ch / q_old;
+      float clipped = ratio;
+      if (ratio > 1.0f + a.eps)
+        clipped = 1.0f + a.eps;
+      else if (ratio < 1.0f - a.eps)
+        clipped = 1.0f - a.eps;
+      const float x = clipped * A, y = ratio * A;
+      const float imp = (y < x ? y : x) * -1.0f;
+      const float d = imp / p_ch;
+#pragma unroll
+      for (int k = 0; k < S::BPL; ++k) {
+        const bool mine = li * S::BPL + k == chc;
+        if (a.logits) {  // softmax_layer::backward's column `choice` times d
+          const float quad = p[k] * p_ch;
+          const float pd = (mine ? p[k] : 0.0f) - quad;
+          g[k] = pd * d;
+        } else {
+          g[k] = mine ? d : 0.0f;
+        }
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < S::BPL; ++k) g[k] = skipped ? 0.0f : g[k] * a.scale;
+    const float dv = vn - tg;  // square_loss_grad (nn.h:548-550)
+    if (valid && li == 0 && a.values_new)
+      a.dvalue[j] = skipped ? 0.0f : dv * a.value_scale;
+
+    if (STATS && valid) {
+      if (skipped) {
+        if (li == 0) st[XH_VLOSS_SKIPPED] += 1.0;
+      } else {
+        double h = 0.0;  // the lane's bins of sum p log p, in bin order
+#pragma unroll
+        for (int k = 0; k < S::BPL; ++k)
+          if (p[k] > 0.0f) h += (double)p[k] * log((double)p[k]);
+        sum2(st[XH_VLOSS_ENTROPY_SUM], sc[XH_VLOSS_ENTROPY_SUM], -h);
+        if (li == 0) {
+          const DiagTerms t = diag_terms(p_ch, q_old, A, a.eps);
+          st[XH_VLOSS_ROWS] += 1.0;
+          st[XH_VLOSS_CLIPPED] += t.clipped;
+          sum2(st[XH_VLOSS_LOGR_SUM], sc[XH_VLOSS_LOGR_SUM], t.logr);
+          sum2(st[XH_VLOSS_LOGR_SQSUM], sc[XH_VLOSS_LOGR_SQSUM], t.logr2);
+          sum2(st[XH_VLOSS_K3_SUM], sc[XH_VLOSS_K3_SUM], t.k3);
+          sum2(st[XH_VLOSS_SURR_SUM], sc[XH_VLOSS_SURR_SUM], t.surr);
+          if (a.values_new) {
+            sum2(st[XH_VLOSS_VERR_SUM], sc[XH_VLOSS_VERR_SUM], (double)dv);
+            sum2(st[XH_VLOSS_VERR_SQSUM], sc[XH_VLOSS_VERR_SQSUM],
+                 (double)dv * (double)dv);
+          }
+        }
+      }
+    }
+
+    const unsigned long long rows_live = __ballot(valid);
+    const size_t wo = (size_t)wbase * (B / 4);  // the wave's block, in pieces
+    vloss_store<B>(g, stage[wib], lane, rows_live,
+                   reinterpret_cast<vl_f4 *>(
+                       __builtin_assume_aligned(a.grad, 16)) + wo);
+    if (a.probs_out)
+      vloss_store<B>(p, stage[wib], lane, rows_live,
+                     reinterpret_cast<vl_f4 *>(
+                         __builtin_assume_aligned(a.probs_out, 16)) + wo);
+  }
+  if constexpr (STATS) {
+#pragma unroll
+    for (int k = 0; k < XH_VLOSS_COUNT; ++k) st[k] += sc[k];
+    block_sums<XH_VLOSS_COUNT>(st,
+                               a.part + (size_t)blockIdx.x * XH_VLOSS_COUNT);
+  }
+}
+
+// stats[k] = (accumulate ? stats[k] : 0) + the column sums of part[nparts]
+// [XH_VLOSS_COUNT]: lane l adds partials l, l + 64, ... in order, then the
+// shuffle tree (wave_column_sums) -- the same bits for the same inputs.
+__global__ __launch_bounds__(64) void venv_loss_reduce_kernel(
+    const double *part, int nparts, int accumulate, double *stats) {
+#pragma clang fp contract(off)
+  double v[XH_VLOSS_COUNT];
+  wave_column_sums<XH_VLOSS_COUNT>(part, nparts, v);
+  if (threadIdx.x != 0) return;
+#pragma unroll
+  for (int k = 0; k < XH_VLOSS_COUNT; ++k)
+    stats[k] = accumulate ? stats[k] + v[k] : v[k];
+}
+
+// ------------------------------------------------------------- launchers --
+#define XH_VLOSS_BINS(X) X(8) X(16) X(32) X(64) X(128)
+
+int venv_loss_grid(int B, long count) {
+  const int bpl = 16 < B ? 16 : B;
+  const long tile = 4l * (64 / (B / bpl));  // rows per workgroup and pass
+  const long tiles = (count + tile - 1) / tile;
+  return (int)(tiles < 1 ? 1 : (tiles > kVenvLossMaxBlocks ? kVenvLossMaxBlocks
+                                                           : tiles));
+}
+
+hipError_t launch_venv_policy_loss(VenvLossArgs a, hipStream_t s) {
+  if (a.count <= 0) return hipSuccess;
+  if (a.total <= 0) return hipErrorInvalidValue;  // a bad index reads row 0's
+#define X(XB)                                                                \
+  if (a.B == XB) {                                                           \
+    const long tile = 4l * VLossShape<XB>::RPW;                              \
+    a.tiles = (a.count + tile - 1) / tile;                                   \
+    const dim3 grid((unsigned)venv_loss_grid(XB, a.count));                  \
+    if (a.part)                                                              \
+      hipLaunchKernelGGL((venv_policy_loss_kernel<XB, true>), grid,          \
+                         dim3(256), 0, s, a);                                \
+    else                                                                     \
+      hipLaunchKernelGGL((venv_policy_loss_kernel<XB, false>), grid,         \
+                         dim3(256), 0, s, a);                                \
+    return hipGetLastError();                                                \
+  }
+  XH_VLOSS_BINS(X)
+#undef X
+  return hipErrorInvalidValue;
+}
+
+hipError_t launch_venv_loss_reduce(const double *part, int nparts,
+                                   int accumulate, double *stats,
+                                   hipStream_t s) {
+  hipLaunchKernelGGL(venv_loss_reduce_kernel, dim3(1), dim3(64), 0, s, part,
+                     nparts, accumulate, stats);
+  return hipGetLastError();
+}
+
+}  // namespace xh

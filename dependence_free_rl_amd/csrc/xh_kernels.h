@@ -412,6 +412,37 @@ hipError_t launch_venv_gae(const VenvGaeArgs &a, hipStream_t s);
 // stats[2] = rows, stats[3] = the sum of end_part (one wave, fixed order)
 hipError_t launch_venv_adv_counts(const int *end_part, int nparts, double rows,
                                   double *stats, hipStream_t s);
+// xh_venv_policy_loss (venv_loss_kernels.hip): the loss head of the caller's
+// network on `count` rows of a recorded window, row j's index q = rows[first
+// + j] or first + j.
+constexpr int kVenvLossMaxBlocks = 4096;
+struct VenvLossArgs {
+  int B;
+  int logits;                 // XH_ACT_LOGITS: venv_act_kernel's softmax first
+  int loss;                   // kLossSoftmaxGradientLog / kLossClipped
+  const float *policy;        // [count][B], 16-byte aligned; may equal grad
+  const int32_t *rows;        // index list or nullptr
+  long first, count, total;   // q in [0, total)
+  long tiles;                 // set by the launcher
+  const float *adv;           // [total]
+  const int32_t *action;      // [total]
+  const float *p_old;         // [total]
+  float eps, scale;
+  const float *values_new;    // [count] or nullptr (no value head)
+  const float *target;        // [total] (with values_new)
+  float value_scale;
+  float *grad;                // [count][B], 16-byte aligned
+  float *dvalue;              // [count] (with values_new)
+  float *probs_out;           // [count][B], 16-byte aligned, or nullptr
+  double *part;               // [venv_loss_grid][XH_VLOSS_COUNT] or nullptr
+  int *err;                   // bit 4: an index or an action out of range
+};
+int venv_loss_grid(int B, long count);
+hipError_t launch_venv_policy_loss(VenvLossArgs a, hipStream_t s);
+// stats[k] = (accumulate ? stats[k] : 0) + the sum of part[nparts][k]
+hipError_t launch_venv_loss_reduce(const double *part, int nparts,
+                                   int accumulate, double *stats,
+                                   hipStream_t s);
 
 // 1 when the kernels were built with the phase-ablation switches
 // (make diag, -DXH_DIAG_ABLATE=1), 0 in the product library.

@@ -9,6 +9,17 @@
 namespace xh {
 namespace {
 
+// s += x in double with the rounding error kept (Knuth's two-sum): c collects
+// what the additions lose, so a lane's sum over any number of steps carries
+// one rounding, not one per step (venv_gae_kernel, venv_policy_loss_kernel)
+__device__ __forceinline__ void sum2(double &s, double &c, double x) {
+#pragma clang fp contract(off)
+  const double t = s + x;
+  const double bb = t - s;
+  c += (s - (t - bb)) + (x - bb);
+  s = t;
+}
+
 // Sums of S values over a 256-thread workgroup -> part[0..S) (thread 0).
 template <int S>
 __device__ __forceinline__ void block_sums(double (&v)[S], double *part) {

@@ -80,6 +80,9 @@ struct xh_venv {
   int *end_scratch = nullptr;
   double *adv_part = nullptr, *adv_stats = nullptr;
   int *adv_end_part = nullptr;
+  // xh_venv_policy_loss's block partials [kVenvLossMaxBlocks][XH_VLOSS_COUNT],
+  // allocated at the first call that asks for stats
+  double *loss_part = nullptr;
 
   xh::VenvArgs args() const {
     xh::VenvArgs a{};
@@ -1411,6 +1414,7 @@ size_t xh_struct_size(const char *name) {
   if (!std::strcmp(name, "xh_state_header")) return sizeof(xh_state_header);
   if (!std::strcmp(name, "xh_state_section")) return sizeof(xh_state_section);
   if (!std::strcmp(name, "xh_venv_adv")) return sizeof(xh_venv_adv);
+  if (!std::strcmp(name, "xh_venv_loss")) return sizeof(xh_venv_loss);
   return 0;
 }
 
@@ -2602,6 +2606,7 @@ int xh_venv_destroy(xh_venv *v) {
     if (v->err) (void)hipFree(v->err);
     if (v->end_scratch) (void)hipFree(v->end_scratch);
     if (v->adv_part) (void)hipFree(v->adv_part);  // adv_stats, adv_end_part too
+    if (v->loss_part) (void)hipFree(v->loss_part);
     venv_free_record(v);
     xh_ctx *c = v->ctx;
     const bool counted = v->counted;
@@ -2635,9 +2640,10 @@ int venv_check_err(xh_venv *v) {
     HIPCHK(hipMemsetAsync(v->err, 0, 4, v->ctx->stream));
     HIPCHK(hipStreamSynchronize(v->ctx->stream));
     if (err & 4)
-      return fail(XH_ERR_INVALID, "venv: xh_venv_record_obs met a row index "
-                  "outside its view's rows; those output rows were left "
-                  "untouched%s%s", err & 2 ? ", and a policy row was refused" : "",
+      return fail(XH_ERR_INVALID, "venv: xh_venv_record_obs or "
+                  "xh_venv_policy_loss met a row index outside its rows (the "
+                  "loss: or an action outside its range); those output rows "
+                  "were left untouched%s%s", err & 2 ? ", and a policy row was refused" : "",
                   err & 1 ? ", and an action was out of range" : "");
     if (err & 2)
       return fail(XH_ERR_INVALID, "venv: a policy row was refused (a NaN, a "
@@ -3005,6 +3011,101 @@ int xh_venv_advantages(xh_venv *v, const xh_venv_adv *p) {
     if (p->stats)
       HIPCHK(hipMemcpyAsync(p->stats, v->adv_stats, 32,
                             hipMemcpyDeviceToDevice, s));
+    return XH_OK;
+  });
+}
+
+int xh_venv_policy_loss(xh_venv *v, const xh_venv_loss *p) {
+  return guard([&]() -> int {
+    if (!v) return fail(XH_ERR_INVALID, "null venv");
+    if (!p) return fail(XH_ERR_INVALID, "venv policy loss: null args");
+    if (!p->policy || !p->adv || !p->grad)
+      return fail(XH_ERR_INVALID, "venv policy loss: null policy / adv / grad");
+    if (p->kind != XH_ACT_PROBS && p->kind != XH_ACT_LOGITS)
+      return fail(XH_ERR_INVALID, "venv policy loss: kind %d (XH_ACT_PROBS / "
+                  "LOGITS)", p->kind);
+    if (p->loss != XH_LOSS_SOFTMAX_GRADIENT_LOG && p->loss != XH_LOSS_CLIPPED)
+      return fail(XH_ERR_INVALID, "venv policy loss: loss %d "
+                  "(XH_LOSS_SOFTMAX_GRADIENT_LOG / XH_LOSS_CLIPPED; "
+                  "KL-regulated needs the full sampling distribution, which "
+                  "the record does not hold)", p->loss);
+    if (p->first < 0 || p->count < 0 || p->total < 0)
+      return fail(XH_ERR_INVALID, "venv policy loss: first %ld, count %ld, "
+                  "total %ld", p->first, p->count, p->total);
+    if (p->loss == XH_LOSS_CLIPPED && !(p->eps > 0.0f && std::isfinite(p->eps)))
+      return fail(XH_ERR_INVALID, "venv policy loss: eps %g", (double)p->eps);
+    if (p->values_new && (!p->target || !p->dvalue))
+      return fail(XH_ERR_INVALID, "venv policy loss: values_new needs target "
+                  "and dvalue");
+    long total = p->total;
+    if (!p->action || !p->p_old) {
+      if (v->rec_steps <= 0)
+        return fail(XH_ERR_STATE, "venv policy loss: action / p_old NULL take "
+                    "the record's and there is no record (xh_venv_set_record)");
+      const long recorded = (long)v->rec_pos * v->N;
+      if (total == 0) total = recorded;
+      if (total > recorded)
+        return fail(XH_ERR_INVALID, "venv policy loss: total %ld, the record "
+                    "holds %ld rows", total, recorded);
+    }
+    if (!p->rows_dev && p->first + p->count > total)
+      return fail(XH_ERR_INVALID, "venv policy loss: rows %ld .. %ld of %ld",
+                  p->first, p->first + p->count - 1, total);
+    if (p->count == 0) return XH_OK;
+    if (total == 0)
+      return fail(XH_ERR_INVALID, "venv policy loss: %ld rows of none",
+                  p->count);
+    const int B = v->env.B;
+    const uintptr_t bytes = (uintptr_t)p->count * B * 4;
+    const uintptr_t pol = reinterpret_cast<uintptr_t>(p->policy);
+    const uintptr_t grd = reinterpret_cast<uintptr_t>(p->grad);
+    const uintptr_t prb = reinterpret_cast<uintptr_t>(p->probs_out);
+    if ((pol | grd | prb) & 15)
+      return fail(XH_ERR_INVALID, "venv policy loss: policy, grad and "
+                  "probs_out must be 16-byte aligned (the kernel moves "
+                  "16-byte pieces)");
+    auto overlap = [&](uintptr_t x, uintptr_t y) {
+      return x < y + bytes && y < x + bytes;
+    };
+    if ((grd != pol && overlap(grd, pol)) ||
+        (prb && (overlap(prb, pol) || overlap(prb, grd))))
+      return fail(XH_ERR_INVALID, "venv policy loss: grad may be policy "
+                  "itself; any other overlap of policy, grad and probs_out "
+                  "is refused");
+    HIPCHK(hipSetDevice(v->ctx->device));
+    hipStream_t s = v->ctx->stream;
+    if (p->stats && !v->loss_part)
+      HIPCHK(hipMalloc((void **)&v->loss_part,
+                       (size_t)xh::kVenvLossMaxBlocks * XH_VLOSS_COUNT * 8));
+    xh::VenvLossArgs a{};
+    a.B = B;
+    a.logits = p->kind == XH_ACT_LOGITS;
+    a.loss = p->loss;
+    a.policy = p->policy;
+    a.rows = p->rows_dev;
+    a.first = p->first;
+    a.count = p->count;
+    a.total = total;
+    a.adv = p->adv;
+    a.action = p->action ? p->action : (const int32_t *)v->rec[XH_VREC_ACTION];
+    a.p_old = p->p_old ? p->p_old : (const float *)v->rec[XH_VREC_PCHOICE];
+    a.eps = p->eps;
+    a.scale = p->scale;
+    a.values_new = p->values_new;
+    a.target = p->target;
+    a.value_scale = p->value_scale;
+    a.grad = p->grad;
+    a.dvalue = p->dvalue;
+    a.probs_out = p->probs_out;
+    a.part = p->stats ? v->loss_part : nullptr;
+    a.err = v->err;
+    CHK(venv_timed(v, [&] { return xh::launch_venv_policy_loss(a, s); }));
+    if (!p->stats) return XH_OK;
+    const hipError_t e = xh::launch_venv_loss_reduce(
+        v->loss_part, xh::venv_loss_grid(B, p->count), p->accumulate != 0,
+        p->stats, s);
+    if (e != hipSuccess)
+      return fail(XH_ERR_HIP, "venv policy loss: %s", hipGetErrorString(e));
     return XH_OK;
   });
 }

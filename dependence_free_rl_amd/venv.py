@@ -298,6 +298,92 @@ class VecEnv:
         out["stats"] = self._download(base + 3 * part, np.float64, (4,))
         return out
 
+    def policy_loss(self, policy, adv, kind="logits", loss="clipped",
+                    rows=None, first=0, count=None, eps=0.2, scale=1.0,
+                    action=None, p_old=None, values=None, target=None,
+                    value_scale=1.0, want_probs=False, want_stats=False,
+                    accumulate=False):
+        """The loss head of the caller's network on a minibatch of the
+        recorded window (xh_venv_policy_loss): from the network's output rows
+        policy [count][B] ("logits": xh_venv_act's softmax first, or "probs")
+        to dL/d(output) under loss "clipped" (PPO, eps) or "log" (policy_loss
+        / actor-critic), times scale.  Output row j has the index q = rows[first
+        + j] (rows: a host int array or an integer device pointer) or first +
+        j into adv, action, p_old and target, all [total]; action / p_old None
+        are the record's, with total = P * N.  values [count] with target
+        turns the value head on: dvalue = (values - target[q]) * value_scale.
+        Every array is a host array or an integer device pointer; count is
+        needed where neither policy nor rows is a host array.  Returns a dict
+        of host arrays: "grad" [count][B], and where asked "dvalue" [count],
+        "probs" [count][B] and "stats" float64 [VLOSS_COUNT]; accumulate adds
+        this call's statistics to the previous call's (the epoch's first
+        minibatch passes False)."""
+        B = self.B
+        losses = {"clipped": _lib.LOSS_CLIPPED,
+                  "log": _lib.LOSS_SOFTMAX_GRADIENT_LOG}
+        host = lambda x: x is not None and not isinstance(  # noqa: E731
+            x, (int, np.integer))
+        rows_ptr = None
+        if host(rows):
+            r = np.ascontiguousarray(rows, np.int32).reshape(-1)
+            if count is None:
+                count = r.size - first
+            if first < 0 or count < 0 or first + count > r.size:
+                raise ValueError("policy_loss: rows %d .. %d of a list of %d"
+                                 % (first, first + count - 1, r.size))
+            rows_ptr = self._staged("vl_rows", r, np.int32, r.shape)
+        elif rows is not None:
+            rows_ptr = int(rows)
+        if count is None:
+            if not host(policy):
+                raise ValueError("policy_loss: count is needed with device "
+                                 "pointers only")
+            count = np.asarray(policy).reshape(-1, B).shape[0]
+        total = 0
+        for x in (adv, action, p_old, target):
+            if host(x):
+                total = np.asarray(x).size
+                break
+        else:
+            if action is not None or p_old is not None:
+                total = self.record_pos() * self.N
+        a = _lib.VenvLoss()
+        if host(policy):
+            policy = np.asarray(policy, np.float32).reshape(-1, B)
+        a.policy = self._staged("vl_policy", policy, np.float32, (count, B))
+        a.kind, a.loss = _KINDS[kind], losses[loss]
+        a.rows_dev, a.first, a.count, a.total = rows_ptr, first, count, total
+
+        def flat(name, x, dtype, n):
+            if host(x):
+                x = np.asarray(x, dtype).reshape(-1)
+            return self._staged(name, x, dtype, (n,))
+        a.adv = flat("vl_adv", adv, np.float32, total)
+        a.action = flat("vl_action", action, np.int32, total)
+        a.p_old = flat("vl_pold", p_old, np.float32, total)
+        a.eps, a.scale, a.value_scale = eps, scale, value_scale
+        a.values_new = flat("vl_values", values, np.float32, count)
+        a.target = flat("vl_target", target, np.float32, total)
+        n = max(count, 1)
+        a.grad = self._scratch("vl_grad", n * B * 4)
+        if values is not None:
+            a.dvalue = self._scratch("vl_dvalue", n * 4)
+        if want_probs:
+            a.probs_out = self._scratch("vl_probs", n * B * 4)
+        if want_stats:
+            a.stats = self._scratch("vl_stats", _lib.VLOSS_COUNT * 8)
+            a.accumulate = 1 if accumulate else 0
+        check(_lib.lib.xh_venv_policy_loss(self.h, C.byref(a)))
+        out = {"grad": self._download(a.grad, np.float32, (count, B))}
+        if values is not None:
+            out["dvalue"] = self._download(a.dvalue, np.float32, (count,))
+        if want_probs:
+            out["probs"] = self._download(a.probs_out, np.float32, (count, B))
+        if want_stats:
+            out["stats"] = self._download(a.stats, np.float64,
+                                          (_lib.VLOSS_COUNT,))
+        return out
+
     def apply(self, mask=None):
         """environment::apply(actions[e], e) for the masked envs (no reset);
         returns game_over per env ([N] uint8; 0 for the envs not applied)."""

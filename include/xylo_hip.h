@@ -779,6 +779,96 @@ int xh_venv_record_obs(xh_venv *v, int view, const int32_t *rows_dev,
                        long first, long count, float *obs_dev);
 int xh_venv_record_ends(xh_venv *v, int32_t *list_dev, int32_t *n_dev);
 int xh_venv_advantages(xh_venv *v, const xh_venv_adv *a);
+/* The loss head of the caller's own network on a minibatch of the recorded
+ * window: from the network's output rows to dL/d(output), one asynchronous
+ * launch on the context's stream (plus a one-wave launch with stats).  It
+ * reads the record and changes nothing of the venv's.  Every pointer is device
+ * memory on the context's device.
+ *
+ * Output row j in [0, count) has the index q = rows_dev[first + j], or first +
+ * j with rows_dev == NULL, into the [total] arrays adv, action, p_old and
+ * target.  action / p_old == NULL take the record's XH_VREC_ACTION /
+ * XH_VREC_PCHOICE, and total == 0 with both NULL is P * N.  A q outside [0,
+ * total) or an action[q] outside [0, B) leaves row j of every output untouched
+ * and is reported by the next xh_venv_synchronize / get as XH_ERR_INVALID, as
+ * xh_venv_record_obs reports a bad index.
+ *
+ * Per row, with ch = action[q], q_old = p_old[q], A = adv[q], every f32
+ * operation rounded once, in this order (no fused multiply-add):
+ *   p: XH_ACT_PROBS the row as given; XH_ACT_LOGITS xh_venv_act's softmax,
+ *     restated bit for bit: m = the row's maximum, e_k = expf(z_k - m), se =
+ *     the sums of 16 consecutive e_k in bin order (all 8 at 8 bins), those
+ *     sums added by an xor butterfly (partners 1, 2, 4), p_k = e_k / se.  So
+ *     while the parameters have not moved (the first epoch) p_ch is the
+ *     record's PCHOICE and the ratio below is exactly 1.0f.  probs_out, where
+ *     not NULL, receives p.
+ *   a skipped row: q_old <= 0 or NaN marks a row xh_venv_act refused (its
+ *     record entries are zero).  grad[j] and dvalue[j] are zeros, the row adds
+ *     1 to XH_VLOSS_SKIPPED and nothing else to the statistics; it is not an
+ *     error (the refusal was reported when it happened).
+ *   XH_LOSS_SOFTMAX_GRADIENT_LOG (policy_loss, rl.h:44-52): g_k = p_k * A,
+ *     then g_ch = g_ch - A.  Through softmax_cross_entropy the same row is the
+ *     logits' gradient, so both kinds give these bits from their p.
+ *   XH_LOSS_CLIPPED (clipped_gradient, rl.h:54-74): ratio = p_ch / q_old;
+ *     clipped = ratio > 1.0f + eps ? 1.0f + eps : ratio < 1.0f - eps ? 1.0f -
+ *     eps : ratio; imp = min(clipped * A, ratio * A) * -1.0f; d = imp / p_ch.
+ *     XH_ACT_PROBS: g_ch = d, every other entry 0.  XH_ACT_LOGITS:
+ *     softmax_layer::backward (nn.h:393-416) on that one-hot backprop: quad =
+ *     p_k * p_ch; pd = (k == ch ? p_k : 0.0f) - quad; g_k = pd * d.
+ *   The other loss kinds are XH_ERR_INVALID: XH_LOSS_KL_REGULATED needs each
+ *     row's full sampling distribution, which the venv's record does not
+ *     hold (use xh_action_loss_grad with a distribution of the caller's own).
+ *   grad[j][k] = g_k * scale.  scale = 1.0f is the reference's row-sum loss; a
+ *     caller who wants the mean passes 1 / count.
+ *   the value head, where values_new != NULL (square_loss_grad, nn.h:548-550):
+ *     dv = values_new[j] - target[q], dvalue[j] = dv * value_scale.
+ * grad may be policy itself (in place); any other overlap among policy, grad
+ * and probs_out is XH_ERR_INVALID, as is one of them not 16-byte aligned (the
+ * kernel moves 16-byte pieces).
+ *
+ * stats, where not NULL, receives the call's XH_VLOSS_* sums over the rows
+ * that are neither skipped nor out of range: ROWS, SKIPPED, the sums of the
+ * PPO update diagnostics' terms (xh_trainer_set_update_diag: log ratio, its
+ * square, k3, clipped rows and the surrogate, from p_ch, q_old, A and eps;
+ * eps is read for them under either loss), the entropy -sum_k p_k log p_k in
+ * double (terms with p_k == 0 are 0), and dv and dv^2 in double (0 without
+ * the value head).  All in double in a fixed order, no floating-point
+ * atomics: the same inputs give the same bits.  accumulate != 0 writes old +
+ * total instead, so an epoch's minibatches add up to one row in call order.
+ * The block partials (4096 x XH_VLOSS_COUNT doubles) are allocated at the
+ * first call with stats and freed with the venv.
+ *
+ * XH_ERR_STATE: action or p_old NULL without a record.  XH_ERR_INVALID: a
+ * null venv, args, policy, adv or grad; a kind or loss other than the above;
+ * first < 0, count < 0, total < 0, or first + count > total without an index
+ * list; eps not finite or not positive with XH_LOSS_CLIPPED; values_new
+ * without target and dvalue; a misaligned pointer; a partial overlap.  count
+ * == 0 returns XH_OK and launches nothing. */
+enum { XH_VLOSS_ROWS = 0, XH_VLOSS_SKIPPED, XH_VLOSS_LOGR_SUM,
+       XH_VLOSS_LOGR_SQSUM, XH_VLOSS_K3_SUM, XH_VLOSS_CLIPPED,
+       XH_VLOSS_SURR_SUM, XH_VLOSS_ENTROPY_SUM, XH_VLOSS_VERR_SUM,
+       XH_VLOSS_VERR_SQSUM, XH_VLOSS_COUNT };
+typedef struct {
+  const float   *policy;     /* [count][B] the network's output for the rows  */
+  int kind;                  /* XH_ACT_PROBS / XH_ACT_LOGITS                  */
+  int loss;                  /* XH_LOSS_SOFTMAX_GRADIENT_LOG / XH_LOSS_CLIPPED */
+  const int32_t *rows_dev;   /* index list or NULL: rows first .. first+count-1 */
+  long first, count;
+  const float   *adv;        /* [total] indexed by q                          */
+  const int32_t *action;     /* [total] or NULL: the record's XH_VREC_ACTION  */
+  const float   *p_old;      /* [total] or NULL: the record's XH_VREC_PCHOICE */
+  long total;                /* 0 with action == p_old == NULL: P * N         */
+  float eps, scale;
+  const float *values_new;   /* [count] or NULL: no value head                */
+  const float *target;       /* [total], required with values_new             */
+  float value_scale;
+  float *grad;               /* [count][B] out; may equal policy              */
+  float *dvalue;             /* [count] out, required with values_new         */
+  float *probs_out;          /* [count][B] out or NULL                        */
+  double *stats;             /* device [XH_VLOSS_COUNT] out or NULL           */
+  int accumulate;
+} xh_venv_loss;              /* xh_struct_size("xh_venv_loss") */
+int xh_venv_policy_loss(xh_venv *v, const xh_venv_loss *a);
 /* environment::apply(ACTIONS[e], e) for the envs selected by MASK (all if
  * use_mask == 0), no reset; DONE[e] = game_over after the apply, 0 for the
  * envs this call did not apply (masked out, or an out-of-range action). */
@@ -788,8 +878,9 @@ int xh_venv_reset(xh_venv *v, int use_mask);
 /* observation::to_vector of every env into OBS. */
 int xh_venv_observe(xh_venv *v);
 /* Waits for the venv's work; XH_ERR_INVALID if an action was out of range,
- * xh_venv_act refused a policy row or xh_venv_record_obs met an index outside
- * its view's rows. */
+ * xh_venv_act refused a policy row or xh_venv_record_obs /
+ * xh_venv_policy_loss met an index (the loss: or an action) outside its
+ * range. */
 int xh_venv_synchronize(xh_venv *v);
 /* Kernel timing: on != 0 brackets every later step / act / apply / reset /
  * observe launch with HIP events on the context's stream (and drops the
@@ -797,7 +888,9 @@ int xh_venv_synchronize(xh_venv *v);
  * milliseconds and the launch count.  xh_venv_record_obs and
  * xh_venv_record_ends are one bracket each; xh_venv_advantages is one
  * bracket around the scan (venv_gae_kernel) alone -- its statistics and
- * normalisation launches are not timed. */
+ * normalisation launches are not timed; xh_venv_policy_loss is one bracket
+ * around the loss launch (venv_policy_loss_kernel) -- the one-wave launch
+ * that reduces its statistics is not timed. */
 int xh_venv_set_timing(xh_venv *v, int on);
 int xh_venv_kernel_time(xh_venv *v, double *ms, long *launches);
 

@@ -33,7 +33,7 @@ VARIANT_KERNELS := policy_split_kernels policy_split128_kernels \
 HDRS     := $(SRC)/xh_device.h $(SRC)/xh_kernels.h $(SRC)/xh_split.h \
             $(SRC)/spec8_layout.h $(SRC)/spec8_e0_layout.h $(SRC)/spec8_l1_layout.h \
             $(SRC)/xh_opt.h $(SRC)/xh_clip.h \
-            $(SRC)/xh_diag.h $(SRC)/xh_sums.h $(SRC)/xh_seg.h \
+            $(SRC)/xh_diag.h $(SRC)/xh_sums.h $(SRC)/xh_seg.h $(SRC)/xh_vstore.h \
             $(SRC)/xh_digest.h $(SRC)/xh_state_blob.h $(SRC)/xh_trainer.h \
             $(SRC)/xh_host.h include/xylo_hip.h
 

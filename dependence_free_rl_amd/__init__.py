@@ -32,6 +32,8 @@ from ._lib import (VLOSS_CLIPPED, VLOSS_COUNT, VLOSS_ENTROPY_SUM,  # noqa: F401
                    VLOSS_K3_SUM, VLOSS_LOGR_SQSUM, VLOSS_LOGR_SUM, VLOSS_ROWS,
                    VLOSS_SKIPPED, VLOSS_SURR_SUM, VLOSS_VERR_SQSUM,
                    VLOSS_VERR_SUM)
+from ._lib import (VKL_COUNT, VKL_KL_SQSUM, VKL_KL_SUM,  # noqa: F401
+                   VKL_ROWS)
 from .venv import VecEnv  # noqa: F401
 
 __all__ = ["Context", "Trainer", "POLICY", "VALUE", "init_policy", "init_value",

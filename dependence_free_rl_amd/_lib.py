@@ -31,6 +31,8 @@ VOBS_STATE, VOBS_NEXT = 0, 1
 (VLOSS_ROWS, VLOSS_SKIPPED, VLOSS_LOGR_SUM, VLOSS_LOGR_SQSUM, VLOSS_K3_SUM,
  VLOSS_CLIPPED, VLOSS_SURR_SUM, VLOSS_ENTROPY_SUM, VLOSS_VERR_SUM,
  VLOSS_VERR_SQSUM, VLOSS_COUNT) = range(11)
+# the exact-KL sums of xh_venv_policy_loss's kl_stats (the XH_VKL_* enum)
+VKL_KL_SUM, VKL_ROWS, VKL_KL_SQSUM, VKL_COUNT = range(4)
 COPY_H2D, COPY_D2H, COPY_D2D = 0, 1, 2
 (BUF_BINS, BUF_ITEMS, BUF_ACTION, BUF_POLD, BUF_DONE, BUF_RNG, BUF_V_STATE,
  BUF_V_TERM, BUF_TARGETS, BUF_ADV, BUF_VALUE_GRAD, BUF_POLICY_GRADS,
@@ -107,7 +109,9 @@ class VenvLoss(C.Structure):
         ("values_new", C.c_void_p), ("target", C.c_void_p),
         ("value_scale", C.c_float), ("grad", C.c_void_p),
         ("dvalue", C.c_void_p), ("probs_out", C.c_void_p),
-        ("stats", C.c_void_p), ("accumulate", C.c_int)]
+        ("stats", C.c_void_p), ("accumulate", C.c_int),
+        ("distrib", C.c_void_p), ("beta", C.c_float),
+        ("beta_dev", C.c_void_p), ("kl_stats", C.c_void_p)]
 
 
 def _load():
@@ -170,6 +174,11 @@ def _load():
         "xh_venv_record_bytes": (sz, [vp, i]),
         "xh_venv_record_ptr": (vp, [vp, i]),
         "xh_venv_get_record": (i, [vp, i, vp, sz]),
+        "xh_venv_set_record_distrib": (i, [vp, i]),
+        "xh_venv_record_distrib_bytes": (sz, [vp]),
+        "xh_venv_record_distrib_ptr": (vp, [vp]),
+        "xh_venv_get_record_distrib": (i, [vp, vp, sz]),
+        "xh_venv_kl_beta": (i, [vp, vp, C.c_float, vp, vp]),
         "xh_venv_record_obs": (i, [vp, i, vp, C.c_long, C.c_long, vp]),
         "xh_venv_record_ends": (i, [vp, vp, vp]),
         "xh_venv_advantages": (i, [vp, C.POINTER(VenvAdv)]),

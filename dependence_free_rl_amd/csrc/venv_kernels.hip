@@ -17,6 +17,7 @@
 #include "xh_device.h"
 #include "xh_kernels.h"
 #include "xh_seg.h"
+#include "xh_vstore.h"
 
 namespace xh {
 
@@ -243,10 +244,29 @@ __global__ __launch_bounds__(256) void venv_step_kernel(VenvArgs a) {
 //
 // A row is refused (env untouched, DONE 0, error bit 2) when a probability is
 // NaN or negative or the double-precision sum is zero or not finite.
-template <int B, int D>
+//
+// RD: the instantiation that also records the distribution (a.rec_distrib,
+// xh_venv_set_record_distrib): row slot N + env of [T][N][B] receives the p[]
+// the pick was made from, zeros for a refused env.  A lane's 16 floats are one
+// 64-byte run and the wave's envs are consecutive, so the wave's block is
+// contiguous: vloss_store (xh_vstore.h), the LDS exchange into whole-line
+// nontemporal stores.  Its barriers stand BEFORE the kernel's first early
+// return, where every lane of the workgroup still runs; lanes past N store
+// nothing.  -DXH_VACT_OWNER_STORES=1 (make variant VSRC=venv_kernels) stores
+// 16-byte pieces from the owning lanes instead; the two times are in
+// DESIGN.md 3.2.  The other instantiation holds none of this.
+#ifndef XH_VACT_OWNER_STORES
+#define XH_VACT_OWNER_STORES 0
+#endif
+constexpr bool kVActOwner = XH_VACT_OWNER_STORES != 0;
+
+template <int B, int D, bool RD>
 __global__ __launch_bounds__(256) void venv_act_kernel(VenvActArgs a) {
   using S = VStepShape<B, D>;
   static_assert(S::BPL % 4 == 0, "the lane's floats as 16-byte loads");
+  static_assert(!RD || (S::BPL == VLossShape<B>::BPL && S::EPW ==
+                                                          VLossShape<B>::RPW),
+                "the distribution record is stored in vloss_store's layout");
   const int lane = threadIdx.x & 63;
   const int wave = (xcd_block() * (int)blockDim.x + (int)threadIdx.x) >> 6;
   const int el = lane / S::LPE, li = lane % S::LPE;
@@ -361,6 +381,19 @@ __global__ __launch_bounds__(256) void venv_act_kernel(VenvActArgs a) {
 #pragma unroll
   for (int k = 1; k < S::BPL; ++k) pmine = k == (choice % S::BPL) ? p[k] : pmine;
   const float pc = wave_shfl(pmine, seg0 + choice / S::BPL);
+  if constexpr (RD) {
+    // every lane of the workgroup is still here (the first return is below)
+    __shared__ vl_f4 stage[4][64 * VLossShape<B>::F4];
+    float pr[S::BPL];
+#pragma unroll
+    for (int k = 0; k < S::BPL; ++k) pr[k] = refused ? 0.0f : p[k];
+    const size_t wo =
+        ((size_t)a.slot * a.v.N + (size_t)wave * S::EPW) * (B / 4);
+    vloss_store<B, kVActOwner>(
+        pr, stage[threadIdx.x >> 6], lane, __ballot(in_range),
+        reinterpret_cast<vl_f4 *>(__builtin_assume_aligned(a.rec_distrib, 16)) +
+            wo);
+  }
 
   int v[S::BPL][D];
 #pragma unroll
@@ -577,8 +610,12 @@ hipError_t launch_venv_act(const VenvActArgs &a, hipStream_t s) {
   if (a.v.N <= 0) return hipSuccess;
 #define X(XB, XD)                                                            \
   if (B == XB && D == XD) {                                                  \
-    hipLaunchKernelGGL((venv_act_kernel<XB, XD>), venv_step_grid(a.v.N, B),       \
-                       dim3(256), 0, s, a);                                  \
+    if (a.rec_distrib)                                                       \
+      hipLaunchKernelGGL((venv_act_kernel<XB, XD, true>),                    \
+                         venv_step_grid(a.v.N, B), dim3(256), 0, s, a);      \
+    else                                                                     \
+      hipLaunchKernelGGL((venv_act_kernel<XB, XD, false>),                   \
+                         venv_step_grid(a.v.N, B), dim3(256), 0, s, a);      \
     return hipGetLastError();                                                \
   }
   XH_VENV_SHAPES(X)

@@ -18,12 +18,15 @@
 //                            wave, fixed order; no floating-point atomics.
 // HBM-bound.  Bytes per row: 4 B read (the output row), 4 B written (the
 // gradient), another 4 B with probs_out, and about 20 gathered (the index,
-// action, p_old, adv, target; + 8 with the value head's values_new / dvalue).
+// action, p_old, adv, target; + 8 with the value head's values_new / dvalue);
+// with XH_LOSS_KL_REGULATED or kl_stats another 4 B gathered (the row's
+// sampling distribution).
 #include "xh_device.h"
 #include "xh_diag.h"
 #include "xh_kernels.h"
 #include "xh_seg.h"
 #include "xh_sums.h"
+#include "xh_vstore.h"
 #include "../../include/xylo_hip.h"
 
 namespace xh {
@@ -31,61 +34,15 @@ namespace xh {
 // venv_act_kernel's layout (VStepShape): a lane owns 16 consecutive bins of a
 // row (all 8 at 8 bins) -- their floats as 16-byte loads in and 16-byte stores
 // out -- so B / 16 lanes share a row and a wave covers 64 / (B / 16) rows.
-// The stores are venv_record_obs_kernel's: a lane's 16 floats are one 64-byte
-// run, and stored from the lane that made them every instruction would touch
-// 64 lines; the wave's rows are consecutive, so its output is one contiguous
-// block, exchanged through LDS and stored as whole lines, nontemporal (the
-// gradient is read once, by the caller's backward).  -DXH_VLOSS_OWNER_STORES=1
-// (make variant VSRC=venv_loss_kernels) stores from the owning lanes instead;
-// the two times are in DESIGN.md 3.2.
+// The stores are vloss_store's (xh_vstore.h): the wave's block exchanged
+// through LDS and stored as whole lines, nontemporal (the gradient is read
+// once, by the caller's backward).  -DXH_VLOSS_OWNER_STORES=1 (make variant
+// VSRC=venv_loss_kernels) stores from the owning lanes instead; the two times
+// are in DESIGN.md 3.2.
 #ifndef XH_VLOSS_OWNER_STORES
 #define XH_VLOSS_OWNER_STORES 0
 #endif
-typedef float vl_f4 __attribute__((ext_vector_type(4)));
-
-template <int B>
-struct VLossShape {
-  static constexpr int BPL = 16 < B ? 16 : B;  // bins per lane
-  static constexpr int LPE = B / BPL;          // lanes per row
-  static constexpr int RPW = 64 / LPE;         // rows per wave
-  static constexpr int F4 = BPL / 4;           // 16-byte pieces per lane
-};
-
-// The wave's [RPW][B] block at `ob` from the lanes' f[BPL]: lane l holds the
-// pieces l F4 .. l F4 + F4 - 1 of the block; instruction i stores piece 64 i +
-// l from lane l.  rows_live bit l: lane l's row is stored.  Every lane of the
-// workgroup reaches the barriers.
-template <int B>
-__device__ __forceinline__ void vloss_store(const float *f, vl_f4 *stage,
-                                            int lane,
-                                            unsigned long long rows_live,
-                                            vl_f4 *ob) {
-  constexpr int G = VLossShape<B>::F4;
-#if XH_VLOSS_OWNER_STORES
-  if ((rows_live >> lane) & 1)
-#pragma unroll
-    for (int g = 0; g < G; ++g) {
-      const vl_f4 x = {f[4 * g], f[4 * g + 1], f[4 * g + 2], f[4 * g + 3]};
-      ob[lane * G + g] = x;
-    }
-#else
-  __syncthreads();  // the previous block's pieces have been read
-#pragma unroll
-  for (int g = 0; g < G; ++g) {
-    const vl_f4 x = {f[4 * g], f[4 * g + 1], f[4 * g + 2], f[4 * g + 3]};
-    stage[lane * G + (g + lane) % G] = x;  // rotated: LDS banks
-  }
-  __syncthreads();
-#pragma unroll
-  for (int i = 0; i < G; ++i) {
-    const int p = i * 64 + lane, lp = p / G, gg = p % G;
-    if ((rows_live >> lp) & 1) {
-      const vl_f4 x = stage[lp * G + (gg + lp) % G];
-      __builtin_nontemporal_store(x, ob + p);
-    }
-  }
-#endif
-}
+constexpr bool kVLossOwner = XH_VLOSS_OWNER_STORES != 0;
 
 // A tile is the 4 RPW consecutive rows of a workgroup's four waves; the
 // workgroups stride over the tiles, so a wave reads all RPW rows of its block
@@ -94,7 +51,13 @@ __device__ __forceinline__ void vloss_store(const float *f, vl_f4 *stage,
 // STATS: the instantiation that forms the statistics (a.part != nullptr); the
 // other one carries neither the double-precision logarithms nor the sums'
 // registers.
-template <int B, bool STATS>
+// KL: 0 the code without a sampling distribution; 1 each row's distribution
+// q = distrib[q] is gathered too (16 more floats per lane) for XH_LOSS_
+// KL_REGULATED's gradient (kl_regulated_loss, policy_gradient.h:56-75, in
+// action_loss_kernel's expressions); 2 also the row's exact KL(q || p) in
+// double for kl_stats (a.kl_part != nullptr; diag_bin_terms' form: a term
+// with q_k == 0 is 0, nothing else is masked), under any loss kind.
+template <int B, bool STATS, int KL>
 __global__ __launch_bounds__(256) void venv_policy_loss_kernel(VenvLossArgs a) {
 #pragma clang fp contract(off)
   using S = VLossShape<B>;
@@ -106,6 +69,11 @@ __global__ __launch_bounds__(256) void venv_policy_loss_kernel(VenvLossArgs a) {
   double st[XH_VLOSS_COUNT], sc[XH_VLOSS_COUNT];
 #pragma unroll
   for (int k = 0; k < XH_VLOSS_COUNT; ++k) st[k] = sc[k] = 0.0;
+  double kt[XH_VKL_COUNT], kc[XH_VKL_COUNT];
+#pragma unroll
+  for (int k = 0; k < XH_VKL_COUNT; ++k) kt[k] = kc[k] = 0.0;
+  float beta = 0.0f;  // the regulation's weight, before this epoch's update
+  if constexpr (KL > 0) beta = a.beta_dev ? *a.beta_dev : a.beta;
 
   for (long tile = blockIdx.x; tile < a.tiles; tile += gridDim.x) {
     const long wbase = (tile * 4 + wib) * S::RPW;
@@ -115,6 +83,7 @@ __global__ __launch_bounds__(256) void venv_policy_loss_kernel(VenvLossArgs a) {
 #pragma unroll
     for (int k = 0; k < S::BPL; ++k) z[k] = 0.0f;
     int ch = 0, ok = 0;
+    long long qrow = 0;
     float q_old = 0.0f, A = 0.0f, tg = 0.0f, vn = 0.0f;
     if (in_range) {
       const vl_f4 *zp = reinterpret_cast<const vl_f4 *>(
@@ -139,6 +108,7 @@ __global__ __launch_bounds__(256) void venv_policy_loss_kernel(VenvLossArgs a) {
           vn = a.values_new[j];
         }
         ok = qok && ch >= 0 && ch < B;
+        qrow = q;
         if (!ok) atomicOr(a.err, 4);  // row j of every output stays untouched
       }
     }
@@ -150,6 +120,25 @@ __global__ __launch_bounds__(256) void venv_policy_loss_kernel(VenvLossArgs a) {
     }
     const bool valid = in_range && ok;
     const int chc = valid ? ch : 0;
+    float qd[S::BPL];  // the row's sampling distribution (KL > 0)
+    if constexpr (KL > 0) {
+      if constexpr (S::LPE > 1) qrow = __shfl(qrow, seg0, kWave);
+#pragma unroll
+      for (int k = 0; k < S::BPL; ++k) qd[k] = 0.0f;
+      if (in_range) {  // a bad index reads row 0's, as the other gathers do
+        const vl_f4 *dp = reinterpret_cast<const vl_f4 *>(
+            __builtin_assume_aligned(
+                a.distrib + (size_t)qrow * B + li * S::BPL, 16));
+#pragma unroll
+        for (int w = 0; w < S::F4; ++w) {
+          const vl_f4 t = dp[w];
+          qd[4 * w] = t.x;
+          qd[4 * w + 1] = t.y;
+          qd[4 * w + 2] = t.z;
+          qd[4 * w + 3] = t.w;
+        }
+      }
+    }
 
     float p[S::BPL];
     if (a.logits) {
@@ -173,6 +162,16 @@ __global__ __launch_bounds__(256) void venv_policy_loss_kernel(VenvLossArgs a) {
       for (int k = 0; k < S::BPL; ++k) {
         float v = p[k] * A;
         if (li * S::BPL + k == chc) v = v - A;
+        g[k] = v;
+      }
+    } else if (KL > 0 && a.loss == kLossKlRegulated) {
+      // softmax_gradient_log + (p - q) * beta (policy_gradient.h:69-73)
+#pragma unroll
+      for (int k = 0; k < S::BPL; ++k) {
+        float v = p[k] * A;
+        if (li * S::BPL + k == chc) v = v - A;
+        const float reg = (p[k] - qd[k]) * beta;
+        v = v + reg;
         g[k] = v;
       }
     } else {  // rl.h:54-74 in action_loss_kernel's expressions
@@ -229,13 +228,31 @@ __global__ __launch_bounds__(256) void venv_policy_loss_kernel(VenvLossArgs a) {
       }
     }
 
+    if constexpr (KL > 1) {
+      // KL(q || p) of the row: the lane's bins in bin order, then the row's
+      // lanes by the xor butterfly; every lane takes part in the shuffles
+      double kl = 0.0;
+#pragma unroll
+      for (int k = 0; k < S::BPL; ++k) {
+        const double qk = (double)qd[k];
+        const double term = qk * (log(qk) - log((double)p[k]));
+        kl += qd[k] == 0.0f ? 0.0 : term;
+      }
+      kl = seg_sum_d<S::LPE>(kl);
+      if (valid && !skipped && li == 0) {
+        sum2(kt[XH_VKL_KL_SUM], kc[XH_VKL_KL_SUM], kl);
+        kt[XH_VKL_ROWS] += 1.0;
+        sum2(kt[XH_VKL_KL_SQSUM], kc[XH_VKL_KL_SQSUM], kl * kl);
+      }
+    }
+
     const unsigned long long rows_live = __ballot(valid);
     const size_t wo = (size_t)wbase * (B / 4);  // the wave's block, in pieces
-    vloss_store<B>(g, stage[wib], lane, rows_live,
+    vloss_store<B, kVLossOwner>(g, stage[wib], lane, rows_live,
                    reinterpret_cast<vl_f4 *>(
                        __builtin_assume_aligned(a.grad, 16)) + wo);
     if (a.probs_out)
-      vloss_store<B>(p, stage[wib], lane, rows_live,
+      vloss_store<B, kVLossOwner>(p, stage[wib], lane, rows_live,
                      reinterpret_cast<vl_f4 *>(
                          __builtin_assume_aligned(a.probs_out, 16)) + wo);
   }
@@ -245,20 +262,27 @@ __global__ __launch_bounds__(256) void venv_policy_loss_kernel(VenvLossArgs a) {
     block_sums<XH_VLOSS_COUNT>(st,
                                a.part + (size_t)blockIdx.x * XH_VLOSS_COUNT);
   }
+  if constexpr (KL > 1) {
+#pragma unroll
+    for (int k = 0; k < XH_VKL_COUNT; ++k) kt[k] += kc[k];
+    block_sums<XH_VKL_COUNT>(kt,
+                             a.kl_part + (size_t)blockIdx.x * XH_VKL_COUNT);
+  }
 }
 
 // stats[k] = (accumulate ? stats[k] : 0) + the column sums of part[nparts]
-// [XH_VLOSS_COUNT]: lane l adds partials l, l + 64, ... in order, then the
-// shuffle tree (wave_column_sums) -- the same bits for the same inputs.
+// [S] (S = XH_VLOSS_COUNT for stats, XH_VKL_COUNT for kl_stats): lane l adds
+// partials l, l + 64, ... in order, then the shuffle tree (wave_column_sums)
+// -- the same bits for the same inputs.
+template <int S>
 __global__ __launch_bounds__(64) void venv_loss_reduce_kernel(
     const double *part, int nparts, int accumulate, double *stats) {
 #pragma clang fp contract(off)
-  double v[XH_VLOSS_COUNT];
-  wave_column_sums<XH_VLOSS_COUNT>(part, nparts, v);
+  double v[S];
+  wave_column_sums<S>(part, nparts, v);
   if (threadIdx.x != 0) return;
 #pragma unroll
-  for (int k = 0; k < XH_VLOSS_COUNT; ++k)
-    stats[k] = accumulate ? stats[k] + v[k] : v[k];
+  for (int k = 0; k < S; ++k) stats[k] = accumulate ? stats[k] + v[k] : v[k];
 }
 
 // ------------------------------------------------------------- launchers --
@@ -272,20 +296,34 @@ int venv_loss_grid(int B, long count) {
                                                            : tiles));
 }
 
+// the STATS instantiation where the call asks for stats (a.part)
+template <int B, int KL>
+static void vloss_launch(const VenvLossArgs &a, dim3 grid, hipStream_t s) {
+  if (a.part)
+    hipLaunchKernelGGL((venv_policy_loss_kernel<B, true, KL>), grid, dim3(256),
+                       0, s, a);
+  else
+    hipLaunchKernelGGL((venv_policy_loss_kernel<B, false, KL>), grid, dim3(256),
+                       0, s, a);
+}
+
 hipError_t launch_venv_policy_loss(VenvLossArgs a, hipStream_t s) {
   if (a.count <= 0) return hipSuccess;
   if (a.total <= 0) return hipErrorInvalidValue;  // a bad index reads row 0's
+  // the distribution is gathered for the KL-regulated loss and for kl_stats
+  const int kl = a.kl_part ? 2 : a.loss == kLossKlRegulated ? 1 : 0;
+  if (kl && !a.distrib) return hipErrorInvalidValue;
 #define X(XB)                                                                \
   if (a.B == XB) {                                                           \
     const long tile = 4l * VLossShape<XB>::RPW;                              \
     a.tiles = (a.count + tile - 1) / tile;                                   \
     const dim3 grid((unsigned)venv_loss_grid(XB, a.count));                  \
-    if (a.part)                                                              \
-      hipLaunchKernelGGL((venv_policy_loss_kernel<XB, true>), grid,          \
-                         dim3(256), 0, s, a);                                \
+    if (kl == 2)                                                             \
+      vloss_launch<XB, 2>(a, grid, s);                                       \
+    else if (kl == 1)                                                        \
+      vloss_launch<XB, 1>(a, grid, s);                                       \
     else                                                                     \
-      hipLaunchKernelGGL((venv_policy_loss_kernel<XB, false>), grid,         \
-                         dim3(256), 0, s, a);                                \
+      vloss_launch<XB, 0>(a, grid, s);                                       \
     return hipGetLastError();                                                \
   }
   XH_VLOSS_BINS(X)
@@ -296,8 +334,15 @@ hipError_t launch_venv_policy_loss(VenvLossArgs a, hipStream_t s) {
 hipError_t launch_venv_loss_reduce(const double *part, int nparts,
                                    int accumulate, double *stats,
                                    hipStream_t s) {
-  hipLaunchKernelGGL(venv_loss_reduce_kernel, dim3(1), dim3(64), 0, s, part,
-                     nparts, accumulate, stats);
+  hipLaunchKernelGGL(venv_loss_reduce_kernel<XH_VLOSS_COUNT>, dim3(1), dim3(64),
+                     0, s, part, nparts, accumulate, stats);
+  return hipGetLastError();
+}
+
+hipError_t launch_venv_kl_reduce(const double *part, int nparts, int accumulate,
+                                 double *kl_stats, hipStream_t s) {
+  hipLaunchKernelGGL(venv_loss_reduce_kernel<XH_VKL_COUNT>, dim3(1), dim3(64),
+                     0, s, part, nparts, accumulate, kl_stats);
   return hipGetLastError();
 }
 

@@ -364,6 +364,8 @@ struct VenvActArgs {
   int8_t *rec_bins;       // [T][N][B][D] the state before the step, or null
   int8_t *rec_items;      // [T][N][4]
   int slot;
+  float *rec_distrib;     // [T][N][B] the p[] sampled from, or null
+                          // (xh_venv_set_record_distrib)
 };
 bool venv_shape_supported(int B, int D);
 hipError_t launch_venv(const VenvArgs &a, int op, hipStream_t s);
@@ -419,7 +421,8 @@ constexpr int kVenvLossMaxBlocks = 4096;
 struct VenvLossArgs {
   int B;
   int logits;                 // XH_ACT_LOGITS: venv_act_kernel's softmax first
-  int loss;                   // kLossSoftmaxGradientLog / kLossClipped
+  int loss;                   // kLossSoftmaxGradientLog / kLossClipped /
+                              // kLossKlRegulated (with distrib)
   const float *policy;        // [count][B], 16-byte aligned; may equal grad
   const int32_t *rows;        // index list or nullptr
   long first, count, total;   // q in [0, total)
@@ -436,6 +439,11 @@ struct VenvLossArgs {
   float *probs_out;           // [count][B], 16-byte aligned, or nullptr
   double *part;               // [venv_loss_grid][XH_VLOSS_COUNT] or nullptr
   int *err;                   // bit 4: an index or an action out of range
+  const float *distrib;       // [total][B] sampling distributions, 16-byte
+                              // aligned, or nullptr (no KL code)
+  float beta;                 // kLossKlRegulated: the regulation's weight ...
+  const float *beta_dev;      // ... or, where not null, one device float
+  double *kl_part;            // [venv_loss_grid][XH_VKL_COUNT] or nullptr
 };
 int venv_loss_grid(int B, long count);
 hipError_t launch_venv_policy_loss(VenvLossArgs a, hipStream_t s);
@@ -443,6 +451,9 @@ hipError_t launch_venv_policy_loss(VenvLossArgs a, hipStream_t s);
 hipError_t launch_venv_loss_reduce(const double *part, int nparts,
                                    int accumulate, double *stats,
                                    hipStream_t s);
+// the same for kl_part[nparts][XH_VKL_COUNT] -> kl_stats
+hipError_t launch_venv_kl_reduce(const double *part, int nparts, int accumulate,
+                                 double *kl_stats, hipStream_t s);
 
 // 1 when the kernels were built with the phase-ablation switches
 // (make diag, -DXH_DIAG_ABLATE=1), 0 in the product library.

@@ -74,6 +74,10 @@ struct xh_venv {
   int rec_steps = 0, rec_pos = 0;
   void *rec[XH_VREC_COUNT] = {};
   size_t rec_bytes[XH_VREC_COUNT] = {};
+  // xh_venv_set_record_distrib: f32 [rec_steps][N][B], the p[] each recorded
+  // xh_venv_act sampled from; dropped with the record
+  float *rec_distrib = nullptr;
+  size_t rec_distrib_bytes = 0;
   // scratch of xh_venv_record_ends / xh_venv_advantages, allocated at their
   // first use: launch_end_list's block totals and n_open; the scan's block
   // partials [venv_gae_grid(N)][2], their ended-row counts, and stats [4]
@@ -83,6 +87,9 @@ struct xh_venv {
   // xh_venv_policy_loss's block partials [kVenvLossMaxBlocks][XH_VLOSS_COUNT],
   // allocated at the first call that asks for stats
   double *loss_part = nullptr;
+  // ... and its kl_stats partials [kVenvLossMaxBlocks][XH_VKL_COUNT], at the
+  // first call that asks for kl_stats
+  double *kl_part = nullptr;
 
   xh::VenvArgs args() const {
     xh::VenvArgs a{};
@@ -2528,6 +2535,9 @@ void venv_free_record(xh_venv *v) {
     v->rec[w] = nullptr;
     v->rec_bytes[w] = 0;
   }
+  if (v->rec_distrib) (void)hipFree(v->rec_distrib);
+  v->rec_distrib = nullptr;
+  v->rec_distrib_bytes = 0;
   v->rec_steps = v->rec_pos = 0;
 }
 }  // namespace
@@ -2607,6 +2617,7 @@ int xh_venv_destroy(xh_venv *v) {
     if (v->end_scratch) (void)hipFree(v->end_scratch);
     if (v->adv_part) (void)hipFree(v->adv_part);  // adv_stats, adv_end_part too
     if (v->loss_part) (void)hipFree(v->loss_part);
+    if (v->kl_part) (void)hipFree(v->kl_part);
     venv_free_record(v);
     xh_ctx *c = v->ctx;
     const bool counted = v->counted;
@@ -2805,6 +2816,7 @@ int xh_venv_act(xh_venv *v, const float *policy_dev, int kind, int mode,
       a.rec_bins = (int8_t *)v->rec[XH_VREC_BINS];
       a.rec_items = (int8_t *)v->rec[XH_VREC_ITEMS];
       a.slot = v->rec_pos;
+      a.rec_distrib = v->rec_distrib;
     }
     const int st = venv_timed(
         v, [&] { return xh::launch_venv_act(a, v->ctx->stream); });
@@ -2873,6 +2885,63 @@ int xh_venv_get_record(xh_venv *v, int which, void *host, size_t bytes) {
                   which, bytes, xh_venv_record_bytes(v, which));
     HIPCHK(hipSetDevice(v->ctx->device));
     HIPCHK(copy_to_host(host, v->rec[which], bytes, v->ctx->stream));
+    HIPCHK(hipStreamSynchronize(v->ctx->stream));
+    return XH_OK;
+  });
+}
+
+int xh_venv_set_record_distrib(xh_venv *v, int on) {
+  return guard([&]() -> int {
+    if (!v) return fail(XH_ERR_INVALID, "null venv");
+    HIPCHK(hipSetDevice(v->ctx->device));
+    if (!on) {
+      if (v->rec_distrib) {
+        HIPCHK(hipStreamSynchronize(v->ctx->stream));
+        (void)hipFree(v->rec_distrib);
+        v->rec_distrib = nullptr;
+        v->rec_distrib_bytes = 0;
+      }
+      return XH_OK;
+    }
+    if (v->rec_steps <= 0)
+      return fail(XH_ERR_STATE, "venv record distrib: no record "
+                  "(xh_venv_set_record)");
+    if (v->rec_pos != 0)
+      return fail(XH_ERR_STATE, "venv record distrib: the cursor is at %d; "
+                  "turn it on at cursor 0 (xh_venv_record_rewind), so every "
+                  "recorded slot has its distribution", v->rec_pos);
+    if (v->rec_distrib) return XH_OK;
+    const size_t bytes = (size_t)v->rec_steps * v->N * v->env.B * 4;
+    void *p = nullptr;
+    if (hipMalloc(&p, bytes) != hipSuccess)
+      return fail(XH_ERR_HIP, "venv record distrib: allocating %zu bytes",
+                  bytes);
+    if (hipMemsetAsync(p, 0, bytes, v->ctx->stream) != hipSuccess) {
+      (void)hipFree(p);
+      return fail(XH_ERR_HIP, "venv record distrib: zero fill");
+    }
+    v->rec_distrib = (float *)p;
+    v->rec_distrib_bytes = bytes;
+    return XH_OK;
+  });
+}
+
+size_t xh_venv_record_distrib_bytes(const xh_venv *v) {
+  return v ? v->rec_distrib_bytes : 0;
+}
+
+float *xh_venv_record_distrib_ptr(xh_venv *v) {
+  return v ? v->rec_distrib : nullptr;
+}
+
+int xh_venv_get_record_distrib(xh_venv *v, float *host, size_t bytes) {
+  return guard([&]() -> int {
+    if (!v || !host) return fail(XH_ERR_INVALID, "null arg");
+    if (!v->rec_distrib || bytes != v->rec_distrib_bytes)
+      return fail(XH_ERR_INVALID, "venv record distrib: %zu bytes, expected "
+                  "%zu", bytes, v->rec_distrib_bytes);
+    HIPCHK(hipSetDevice(v->ctx->device));
+    HIPCHK(copy_to_host(host, v->rec_distrib, bytes, v->ctx->stream));
     HIPCHK(hipStreamSynchronize(v->ctx->stream));
     return XH_OK;
   });
@@ -3024,11 +3093,22 @@ int xh_venv_policy_loss(xh_venv *v, const xh_venv_loss *p) {
     if (p->kind != XH_ACT_PROBS && p->kind != XH_ACT_LOGITS)
       return fail(XH_ERR_INVALID, "venv policy loss: kind %d (XH_ACT_PROBS / "
                   "LOGITS)", p->kind);
-    if (p->loss != XH_LOSS_SOFTMAX_GRADIENT_LOG && p->loss != XH_LOSS_CLIPPED)
+    const bool kl_loss = p->loss == XH_LOSS_KL_REGULATED;
+    if (p->loss != XH_LOSS_SOFTMAX_GRADIENT_LOG && p->loss != XH_LOSS_CLIPPED &&
+        !kl_loss)
       return fail(XH_ERR_INVALID, "venv policy loss: loss %d "
-                  "(XH_LOSS_SOFTMAX_GRADIENT_LOG / XH_LOSS_CLIPPED; "
-                  "KL-regulated needs the full sampling distribution, which "
-                  "the record does not hold)", p->loss);
+                  "(XH_LOSS_SOFTMAX_GRADIENT_LOG / XH_LOSS_CLIPPED / "
+                  "XH_LOSS_KL_REGULATED)", p->loss);
+    // the rows' sampling distributions: the caller's, or the record's
+    const bool want_q = kl_loss || p->kl_stats;
+    const float *distrib = p->distrib ? p->distrib : v->rec_distrib;
+    if (want_q && !distrib)
+      return fail(XH_ERR_INVALID, "venv policy loss: %s needs each row's "
+                  "sampling distribution: pass distrib, or record it "
+                  "(xh_venv_set_record_distrib)",
+                  kl_loss ? "XH_LOSS_KL_REGULATED" : "kl_stats");
+    if (kl_loss && !p->beta_dev && !(p->beta >= 0.0f && std::isfinite(p->beta)))
+      return fail(XH_ERR_INVALID, "venv policy loss: beta %g", (double)p->beta);
     if (p->first < 0 || p->count < 0 || p->total < 0)
       return fail(XH_ERR_INVALID, "venv policy loss: first %ld, count %ld, "
                   "total %ld", p->first, p->count, p->total);
@@ -3047,6 +3127,13 @@ int xh_venv_policy_loss(xh_venv *v, const xh_venv_loss *p) {
       if (total > recorded)
         return fail(XH_ERR_INVALID, "venv policy loss: total %ld, the record "
                     "holds %ld rows", total, recorded);
+    }
+    if (want_q && !p->distrib) {  // the record's: as many rows as it holds
+      const long recorded = (long)v->rec_pos * v->N;
+      if (total == 0) total = recorded;
+      if (total > recorded)
+        return fail(XH_ERR_INVALID, "venv policy loss: total %ld, the record "
+                    "holds the distributions of %ld rows", total, recorded);
     }
     if (!p->rows_dev && p->first + p->count > total)
       return fail(XH_ERR_INVALID, "venv policy loss: rows %ld .. %ld of %ld",
@@ -3072,13 +3159,35 @@ int xh_venv_policy_loss(xh_venv *v, const xh_venv_loss *p) {
       return fail(XH_ERR_INVALID, "venv policy loss: grad may be policy "
                   "itself; any other overlap of policy, grad and probs_out "
                   "is refused");
+    if (want_q) {
+      const uintptr_t dst = reinterpret_cast<uintptr_t>(distrib);
+      const uintptr_t dbytes = (uintptr_t)total * B * 4;
+      if (dst & 15)
+        return fail(XH_ERR_INVALID, "venv policy loss: distrib must be 16-byte "
+                    "aligned (the kernel reads 16-byte pieces)");
+      auto hits = [&](uintptr_t x) {
+        return x && x < dst + dbytes && dst < x + bytes;
+      };
+      if (hits(grd) || hits(prb))
+        return fail(XH_ERR_INVALID, "venv policy loss: distrib overlaps grad "
+                    "or probs_out");
+    }
     HIPCHK(hipSetDevice(v->ctx->device));
     hipStream_t s = v->ctx->stream;
     if (p->stats && !v->loss_part)
       HIPCHK(hipMalloc((void **)&v->loss_part,
                        (size_t)xh::kVenvLossMaxBlocks * XH_VLOSS_COUNT * 8));
+    if (p->kl_stats && !v->kl_part)
+      HIPCHK(hipMalloc((void **)&v->kl_part,
+                       (size_t)xh::kVenvLossMaxBlocks * XH_VKL_COUNT * 8));
     xh::VenvLossArgs a{};
     a.B = B;
+    if (want_q) {
+      a.distrib = distrib;
+      a.beta = p->beta;
+      a.beta_dev = p->beta_dev;
+      a.kl_part = p->kl_stats ? v->kl_part : nullptr;
+    }
     a.logits = p->kind == XH_ACT_LOGITS;
     a.loss = p->loss;
     a.policy = p->policy;
@@ -3100,12 +3209,36 @@ int xh_venv_policy_loss(xh_venv *v, const xh_venv_loss *p) {
     a.part = p->stats ? v->loss_part : nullptr;
     a.err = v->err;
     CHK(venv_timed(v, [&] { return xh::launch_venv_policy_loss(a, s); }));
-    if (!p->stats) return XH_OK;
-    const hipError_t e = xh::launch_venv_loss_reduce(
-        v->loss_part, xh::venv_loss_grid(B, p->count), p->accumulate != 0,
-        p->stats, s);
+    hipError_t e = hipSuccess;
+    if (p->stats)
+      e = xh::launch_venv_loss_reduce(v->loss_part,
+                                      xh::venv_loss_grid(B, p->count),
+                                      p->accumulate != 0, p->stats, s);
+    if (e == hipSuccess && p->kl_stats)
+      e = xh::launch_venv_kl_reduce(v->kl_part, xh::venv_loss_grid(B, p->count),
+                                    p->accumulate != 0, p->kl_stats, s);
     if (e != hipSuccess)
       return fail(XH_ERR_HIP, "venv policy loss: %s", hipGetErrorString(e));
+    return XH_OK;
+  });
+}
+
+int xh_venv_kl_beta(xh_venv *v, const double *kl_stats_dev, float d_targ,
+                    float *beta_dev, float *log_dev) {
+  return guard([&]() -> int {
+    if (!v || !kl_stats_dev || !beta_dev)
+      return fail(XH_ERR_INVALID, "venv kl beta: null venv / kl_stats_dev / "
+                  "beta_dev");
+    if (!(d_targ > 0.0f && std::isfinite(d_targ)))
+      return fail(XH_ERR_INVALID, "venv kl beta: d_targ %g", (double)d_targ);
+    HIPCHK(hipSetDevice(v->ctx->device));
+    // kl_stats' first two entries are KL_SUM and ROWS: kl_beta_kernel's input
+    static_assert(XH_VKL_KL_SUM == 0 && XH_VKL_ROWS == 1, "kl_beta_kernel");
+    const hipError_t e = xh::launch_kl_beta_update(kl_stats_dev, beta_dev,
+                                                   d_targ, log_dev,
+                                                   v->ctx->stream);
+    if (e != hipSuccess)
+      return fail(XH_ERR_HIP, "venv kl beta: %s", hipGetErrorString(e));
     return XH_OK;
   });
 }

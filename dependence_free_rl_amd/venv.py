@@ -41,6 +41,18 @@ def _ptr(a):
     return a.ctypes.data_as(C.c_void_p)
 
 
+def _beta_ptr(beta):
+    """The device address in `beta`, or None where it is a value.  An integer
+    is an address (as everywhere in this class), so a small one is a mistake:
+    beta = 1 is written 1.0."""
+    if isinstance(beta, bool) or not isinstance(beta, (int, np.integer)):
+        return None
+    if int(beta) < 4096:
+        raise ValueError("beta: a float, or an integer device pointer to one "
+                         "(got the integer %d; write it as a float)" % beta)
+    return int(beta)
+
+
 class VecEnv:
     """xh_venv: N envs of B bins x D dims stepped by one kernel per call."""
 
@@ -112,11 +124,15 @@ class VecEnv:
         return None
 
     # ---- the trajectory record act() writes -----------------------------
-    def set_record(self, steps, states=True):
+    def set_record(self, steps, states=True, distrib=False):
         """Record the next `steps` act() calls (xh_venv_set_record); 0 turns
-        the record off and frees it."""
+        the record off and frees it.  distrib: also record the distribution
+        every pick is made from (xh_venv_set_record_distrib), which the "kl"
+        loss and want_kl of policy_loss() read."""
         check(_lib.lib.xh_venv_set_record(self.h, int(steps),
                                           1 if states else 0))
+        if distrib and steps:
+            check(_lib.lib.xh_venv_set_record_distrib(self.h, 1))
 
     def record_pos(self):
         pos = C.c_int()
@@ -127,7 +143,8 @@ class VecEnv:
         """The recorded slots [0, cursor) as a dict: action int32 [t][N],
         pchoice / reward float32 [t][N], done uint8 [t][N] and, if recorded,
         the states before each step: bins int8 [t][N][B][D], items int8
-        [t][N][4]."""
+        [t][N][4]; and, only while the distribution record is on, distrib
+        float32 [t][N][B]."""
         N, B, D = self.N, self.B, self.D
         spec = {"action": (VREC_ACTION, np.int32, (N,)),
                 "pchoice": (VREC_PCHOICE, np.float32, (N,)),
@@ -143,6 +160,11 @@ class VecEnv:
             a = np.zeros(nbytes // np.dtype(dt).itemsize, dt)
             check(_lib.lib.xh_venv_get_record(self.h, which, _ptr(a), nbytes))
             out[name] = a.reshape((-1,) + shape)[:pos]
+        nbytes = _lib.lib.xh_venv_record_distrib_bytes(self.h)
+        if nbytes:
+            a = np.zeros(nbytes // 4, np.float32)
+            check(_lib.lib.xh_venv_get_record_distrib(self.h, _ptr(a), nbytes))
+            out["distrib"] = a.reshape(-1, N, B)[:pos]
         return out
 
     def rewind(self):
@@ -302,12 +324,18 @@ class VecEnv:
                     rows=None, first=0, count=None, eps=0.2, scale=1.0,
                     action=None, p_old=None, values=None, target=None,
                     value_scale=1.0, want_probs=False, want_stats=False,
-                    accumulate=False):
+                    accumulate=False, beta=0.0, distrib=None, want_kl=False):
         """The loss head of the caller's network on a minibatch of the
         recorded window (xh_venv_policy_loss): from the network's output rows
         policy [count][B] ("logits": xh_venv_act's softmax first, or "probs")
-        to dL/d(output) under loss "clipped" (PPO, eps) or "log" (policy_loss
-        / actor-critic), times scale.  Output row j has the index q = rows[first
+        to dL/d(output) under loss "clipped" (PPO, eps), "log" (policy_loss /
+        actor-critic) or "kl" (KL-PPO: "log" + beta * (p - q), q the rows'
+        sampling distributions), times scale.  beta is a float or an integer
+        device pointer to one float (what kl_beta() maintains); distrib
+        [total][B] is a host array, an integer device pointer, or None for the
+        record's (set_record(distrib=True)).  want_kl adds "kl_stats" float64
+        [VKL_COUNT] -- the exact KL(q || p) sum, the rows and the sum of
+        squares -- under any loss; it needs the distributions too.  Output row j has the index q = rows[first
         + j] (rows: a host int array or an integer device pointer) or first +
         j into adv, action, p_old and target, all [total]; action / p_old None
         are the record's, with total = P * N.  values [count] with target
@@ -320,7 +348,8 @@ class VecEnv:
         minibatch passes False)."""
         B = self.B
         losses = {"clipped": _lib.LOSS_CLIPPED,
-                  "log": _lib.LOSS_SOFTMAX_GRADIENT_LOG}
+                  "log": _lib.LOSS_SOFTMAX_GRADIENT_LOG,
+                  "kl": _lib.LOSS_KL_REGULATED}
         host = lambda x: x is not None and not isinstance(  # noqa: E731
             x, (int, np.integer))
         rows_ptr = None
@@ -345,7 +374,9 @@ class VecEnv:
                 total = np.asarray(x).size
                 break
         else:
-            if action is not None or p_old is not None:
+            if host(distrib):
+                total = np.asarray(distrib).size // B
+            elif action is not None or p_old is not None:
                 total = self.record_pos() * self.N
         a = _lib.VenvLoss()
         if host(policy):
@@ -372,7 +403,17 @@ class VecEnv:
             a.probs_out = self._scratch("vl_probs", n * B * 4)
         if want_stats:
             a.stats = self._scratch("vl_stats", _lib.VLOSS_COUNT * 8)
+        if want_stats or want_kl:
             a.accumulate = 1 if accumulate else 0
+        if host(distrib):
+            distrib = np.asarray(distrib, np.float32).reshape(-1, B)
+        a.distrib = self._staged("vl_distrib", distrib, np.float32, (total, B))
+        if _beta_ptr(beta) is not None:
+            a.beta_dev = _beta_ptr(beta)
+        else:
+            a.beta = float(beta)
+        if want_kl:
+            a.kl_stats = self._scratch("vl_kl", _lib.VKL_COUNT * 8)
         check(_lib.lib.xh_venv_policy_loss(self.h, C.byref(a)))
         out = {"grad": self._download(a.grad, np.float32, (count, B))}
         if values is not None:
@@ -382,7 +423,30 @@ class VecEnv:
         if want_stats:
             out["stats"] = self._download(a.stats, np.float64,
                                           (_lib.VLOSS_COUNT,))
+        if want_kl:
+            out["kl_stats"] = self._download(a.kl_stats, np.float64,
+                                             (_lib.VKL_COUNT,))
         return out
+
+    def kl_beta(self, kl_stats, d_targ, beta):
+        """kl_ppo_learner's beta rule on the device (xh_venv_kl_beta): from an
+        epoch's accumulated kl_stats -- a host float64 [VKL_COUNT] array or an
+        integer device pointer, e.g. the block policy_loss(want_kl=True) wrote
+        -- beta halves / doubles around d_targ and is clamped to [1e-25, 0.1].
+        beta: an integer device pointer to the float updated in place, or a
+        float (staged, updated and read back).  Returns (beta_after,
+        mean_kl)."""
+        stats = self._staged("kb_stats", kl_stats, np.float64,
+                             (_lib.VKL_COUNT,))
+        bptr = _beta_ptr(beta)
+        if bptr is None:
+            bptr = self._staged("kb_beta", np.array([beta], np.float32),
+                                np.float32, (1,))
+        log = self._scratch("kb_log", 16)
+        check(_lib.lib.xh_venv_kl_beta(self.h, stats, float(d_targ), bptr,
+                                       log))
+        got = self._download(log, np.float32, (3,))
+        return float(got[2]), float(got[1])
 
     def apply(self, mask=None):
         """environment::apply(actions[e], e) for the masked envs (no reset);

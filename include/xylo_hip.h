@@ -712,6 +712,28 @@ int xh_venv_record_rewind(xh_venv *v);
 size_t xh_venv_record_bytes(const xh_venv *v, int which);
 void *xh_venv_record_ptr(xh_venv *v, int which);
 int xh_venv_get_record(xh_venv *v, int which, void *host, size_t bytes);
+/* The distribution record: with it on, the xh_venv_act call at cursor t also
+ * writes distrib[t][e][0..B), the p[] it picked env e's bin from, from the same
+ * launch (no further launch): for XH_ACT_LOGITS its softmax's output, for
+ * XH_ACT_PROBS the bits of the input row; XH_ACT_ARGMAX records the same p.
+ * So distrib[t][e][ACTION] has XH_VREC_PCHOICE's bits, and a refused env's row
+ * is zeros, like its other record entries.  It is what XH_LOSS_KL_REGULATED
+ * and kl_stats of xh_venv_policy_loss read (XH_BUF_QOLD of a trainer made with
+ * record_distrib).  The act launch writes 4 B more bytes per env and step.
+ *   on != 0 allocates the zero-filled f32 [T][N][B] block of the current
+ *     record; XH_ERR_STATE without a record, or when the cursor is not 0 (every
+ *     recorded slot is to have its distribution); at cursor 0 with the block
+ *     on already, XH_OK and nothing done.
+ *   on == 0 frees it.
+ * xh_venv_set_record (any steps) drops the block, as it drops the record it
+ * replaces; xh_venv_record_rewind keeps it.  The accessors follow the other
+ * record arrays': _bytes is the whole block's size (0 when off), _ptr its
+ * device address (NULL when off), xh_venv_get_record_distrib copies the whole
+ * block (XH_ERR_INVALID when off or on another size). */
+int xh_venv_set_record_distrib(xh_venv *v, int on);
+size_t xh_venv_record_distrib_bytes(const xh_venv *v);
+float *xh_venv_record_distrib_ptr(xh_venv *v);
+int xh_venv_get_record_distrib(xh_venv *v, float *host, size_t bytes);
 /* From a recorded window to the learner's minibatches, on the device.  P is
  * the record's cursor (xh_venv_record_pos), a row index is q = t N + e.  The
  * three calls are asynchronous on the context's stream; their pointer
@@ -815,9 +837,20 @@ int xh_venv_advantages(xh_venv *v, const xh_venv_adv *a);
  *     XH_ACT_PROBS: g_ch = d, every other entry 0.  XH_ACT_LOGITS:
  *     softmax_layer::backward (nn.h:393-416) on that one-hot backprop: quad =
  *     p_k * p_ch; pd = (k == ch ? p_k : 0.0f) - quad; g_k = pd * d.
- *   The other loss kinds are XH_ERR_INVALID: XH_LOSS_KL_REGULATED needs each
- *     row's full sampling distribution, which the venv's record does not
- *     hold (use xh_action_loss_grad with a distribution of the caller's own).
+ *   XH_LOSS_KL_REGULATED (kl_regulated_loss, policy_gradient.h:56-75, in
+ *     xh_action_loss_grad's expressions): with the row's sampling distribution
+ *     q = distrib[q] -- the caller's [total][B] array, or with distrib == NULL
+ *     the record's (xh_venv_set_record_distrib) -- and beta = *beta_dev where
+ *     beta_dev != NULL, the field beta otherwise:
+ *       v = p_k * A;  if (k == ch) v = v - A;     softmax_gradient_log
+ *       reg = (p_k - q_k) * beta;  v = v + reg;   + beta * (p - q)
+ *       g_k = v
+ *     As in the reference the net ends in softmax_cross_entropy, so both kinds
+ *     give these bits from their p.  While the parameters have not moved p ==
+ *     q bit for bit and the row is XH_LOSS_SOFTMAX_GRADIENT_LOG's.  eps is not
+ *     read (but for stats).  beta_dev is read by the kernel, so a value
+ *     xh_venv_kl_beta updates on the stream needs no host round trip.
+ *   XH_LOSS_GRADIENT_LOG is XH_ERR_INVALID.
  *   grad[j][k] = g_k * scale.  scale = 1.0f is the reference's row-sum loss; a
  *     caller who wants the mean passes 1 / count.
  *   the value head, where values_new != NULL (square_loss_grad, nn.h:548-550):
@@ -838,12 +871,32 @@ int xh_venv_advantages(xh_venv *v, const xh_venv_adv *a);
  * The block partials (4096 x XH_VLOSS_COUNT doubles) are allocated at the
  * first call with stats and freed with the venv.
  *
+ * kl_stats, where not NULL, receives the XH_VKL_* sums under ANY loss kind
+ * (clipped PPO's exact KL(old || new) too); it needs the rows' distributions
+ * as XH_LOSS_KL_REGULATED does.  Over the rows that are neither skipped nor
+ * out of range: ROWS, and with KL = sum_k q_k (log q_k - log p_k) in double
+ * per row, KL_SUM = sum KL and KL_SQSUM = sum KL^2.  A term with q_k == 0 is
+ * 0; nothing else is masked: p_k == 0 < q_k gives +inf and a NaN stays a NaN
+ * (XH_UPD_KL_SUM's semantics).  The form differs from the reference's
+ * kl_divergence, sum_k q_k log(q_k / p_k) (policy_gradient.h:41-54), by
+ * rounding, and at q_k == 0, where the reference's 0 * log(0) is NaN.  Same
+ * fixed-order double sums, no floating-point atomics; accumulate applies as
+ * it does to stats; the block partials (4096 x XH_VKL_COUNT doubles) are
+ * allocated at the first call with kl_stats.  The sums cover THIS venv's rows
+ * only, as xh_venv_advantages' normalize does: nothing is all-reduced.
+ * The order KL_SUM, ROWS is what xh_venv_kl_beta reads.
+ *
  * XH_ERR_STATE: action or p_old NULL without a record.  XH_ERR_INVALID: a
  * null venv, args, policy, adv or grad; a kind or loss other than the above;
  * first < 0, count < 0, total < 0, or first + count > total without an index
  * list; eps not finite or not positive with XH_LOSS_CLIPPED; values_new
- * without target and dvalue; a misaligned pointer; a partial overlap.  count
- * == 0 returns XH_OK and launches nothing. */
+ * without target and dvalue; a misaligned pointer; a partial overlap;
+ * XH_LOSS_KL_REGULATED or kl_stats with distrib == NULL and no recorded
+ * distributions (or a total above the recorded rows); with
+ * XH_LOSS_KL_REGULATED and beta_dev == NULL a beta that is negative or not
+ * finite; distrib not 16-byte aligned, or overlapping grad or probs_out.
+ * count == 0 returns XH_OK and launches nothing. */
+enum { XH_VKL_KL_SUM = 0, XH_VKL_ROWS = 1, XH_VKL_KL_SQSUM = 2, XH_VKL_COUNT };
 enum { XH_VLOSS_ROWS = 0, XH_VLOSS_SKIPPED, XH_VLOSS_LOGR_SUM,
        XH_VLOSS_LOGR_SQSUM, XH_VLOSS_K3_SUM, XH_VLOSS_CLIPPED,
        XH_VLOSS_SURR_SUM, XH_VLOSS_ENTROPY_SUM, XH_VLOSS_VERR_SUM,
@@ -867,8 +920,30 @@ typedef struct {
   float *probs_out;          /* [count][B] out or NULL                        */
   double *stats;             /* device [XH_VLOSS_COUNT] out or NULL           */
   int accumulate;
+  const float *distrib;      /* [total][B] sampling distributions indexed by q,
+                                16-byte aligned; NULL: the record's
+                                (xh_venv_set_record_distrib)                  */
+  float beta;                /* KL_REGULATED: the regulation's weight ...     */
+  const float *beta_dev;     /* ... or, where not NULL, one device float read
+                                by the kernel (what xh_venv_kl_beta maintains) */
+  double *kl_stats;          /* device [XH_VKL_COUNT] out or NULL; any loss kind */
 } xh_venv_loss;              /* xh_struct_size("xh_venv_loss") */
 int xh_venv_policy_loss(xh_venv *v, const xh_venv_loss *a);
+/* kl_ppo_learner's beta rule (policy_gradient.h:76-80, 310-335) on the device:
+ * one asynchronous single-thread launch on the context's stream.
+ *   d = (float)(kl_stats_dev[XH_VKL_KL_SUM] / kl_stats_dev[XH_VKL_ROWS])
+ *   beta halves where fabsf(d) < d_targ / 1.5f, doubles where fabsf(d) >
+ *   d_targ * 1.5f, and is then clamped to [1e-25f, 0.1f].
+ * A NaN d -- ROWS == 0 gives one -- compares false twice and leaves beta
+ * unchanged apart from the clamp.  log_dev, where not NULL, receives {beta
+ * before, d, beta after}.  The caller runs an epoch's minibatches with
+ * accumulate (the first one without) and calls this once per epoch: the
+ * reference's full-batch rule; the epoch's gradients used the beta from
+ * before the update.  It is not bracketed by xh_venv_set_timing.
+ * XH_ERR_INVALID: a null venv, kl_stats_dev or beta_dev; a d_targ that is not
+ * finite or not positive. */
+int xh_venv_kl_beta(xh_venv *v, const double *kl_stats_dev, float d_targ,
+                    float *beta_dev, float *log_dev);
 /* environment::apply(ACTIONS[e], e) for the envs selected by MASK (all if
  * use_mask == 0), no reset; DONE[e] = game_over after the apply, 0 for the
  * envs this call did not apply (masked out, or an out-of-range action). */

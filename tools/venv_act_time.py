@@ -2,16 +2,18 @@
 """Kernel time of xh_venv_act (PROBS / SAMPLE) and of xh_venv_step, from
 xh_venv_kernel_time (HIP events around each launch): ms per launch and the
 achieved GB/s over the algorithmic bytes, at 64 bins, 2-D, with 32768 and
-1,048,576 envs, the trajectory record off and on (with the states).
+1,048,576 envs, the trajectory record off and on (with the states), and with
+--distrib also with the distribution record (xh_venv_set_record_distrib).
 
     python tools/venv_act_time.py                  # act and step
+    python tools/venv_act_time.py --distrib --bins 128 --envs 32768
     python tools/venv_act_time.py --step-only --package-root build/prev_tree
                         # the parent commit's package, built in its own tree
 
 Bytes per env step: step 2 B D + 13 (bins read and written, item read and
 written, action, stream state read and written ... DESIGN.md §3.2); act adds
 the policy row and the two outputs, 4 B + 8; the record adds 13, and B D + 4
-with the states.  Each figure is the mean over --launches launches, repeated
+with the states, and 4 B with the distributions.  Each figure is the mean over --launches launches, repeated
 --reps times: median [min .. max] of the repetitions.  For an A/B of two
 libraries run the script once per library, alternating, in one session."""
 import argparse
@@ -50,6 +52,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--step-only", action="store_true",
                     help="xh_venv_step alone (a library without xh_venv_act)")
+    ap.add_argument("--distrib", action="store_true",
+                    help="add the arm with the distribution record on")
     ap.add_argument("--package-root", default=REPO,
                     help="import dependence_free_rl_amd from this tree (a "
                     "checkout of another commit with its library built)")
@@ -74,8 +78,13 @@ def main():
             act_bytes = step_bytes + 4 * B + 8
             cases += [("act", 0, act_bytes),
                       ("act+record", a.launches, act_bytes + 13 + B * D + 4)]
+            if a.distrib:
+                cases += [("act+rec+dist", a.launches,
+                           act_bytes + 13 + B * D + 4 + 4 * B)]
         for name, record, nbytes in cases:
-            if record is not None:
+            if name == "act+rec+dist":
+                env.set_record(record, distrib=True)
+            elif record is not None:
                 env.set_record(record)
 
             def launch():
@@ -92,7 +101,7 @@ def main():
                    "ms_min": min(per), "ms_max": max(per),
                    "gb_s": N * nbytes / med / 1e6}
             rows.append(row)
-            print("%-11s %8d envs  %.4f ms [%.4f .. %.4f]  %7.1f GB/s  (%d B "
+            print("%-12s %8d envs  %.4f ms [%.4f .. %.4f]  %7.1f GB/s  (%d B "
                   "per env step)" % (name, N, med, min(per), max(per),
                                      row["gb_s"], nbytes), flush=True)
         env.close()

@@ -4,15 +4,19 @@ around the loss launch; the one-wave launch that reduces the statistics is
 not timed): venv_policy_loss_kernel (xh_venv_policy_loss) on logits, clipped
 loss, a shuffled minibatch gathered through an index list, with the value
 head, with and without probs_out and stats -- at 131,072 and 1,048,576 rows
-of 64 bins and of 128 bins.
+of 64 bins and of 128 bins.  --kl adds the KL-regulated loss on the same
+rows (each row's sampling distribution gathered through the index list), alone
+and with kl_stats, and kl_stats under the clipped loss.
 
     python tools/venv_loss_time.py
+    python tools/venv_loss_time.py --kl
     python tools/venv_loss_time.py --rows 1048576 --bins 64 --json out.json
     python tools/venv_loss_time.py --torch     # the same loss in torch, alone
 
 Bytes by the kernel's model: per row 4 B read, 4 B written,
 4 B more with probs_out, and 28 gathered or scattered (the index, action,
-p_old, adv, target, values_new, dvalue).  Each figure is the mean over
+p_old, adv, target, values_new, dvalue); the KL arms gather 4 B more (the
+row's distribution).  Each figure is the mean over
 --launches launches, repeated --reps times: median [min .. max].
 
 --torch times the loss a caller would otherwise write on the device: gather,
@@ -85,6 +89,8 @@ def main():
     ap.add_argument("--launches", type=int, default=20)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--kl", action="store_true",
+                    help="add the KL-regulated loss and kl_stats arms")
     ap.add_argument("--torch", action="store_true",
                     help="time the eager torch form instead (own process)")
     ap.add_argument("--json", help="also write the result rows to this file")
@@ -123,6 +129,13 @@ def main():
             for k in ("action", "p_old", "adv", "target"):
                 blocks[k] = dev(4 * total)
             blocks["stats"] = dev(8 * _lib.VLOSS_COUNT)
+            if a.kl:  # any positive rows do: the time does not depend on them
+                blocks["distrib"] = dev(4 * total * B)
+                blocks["kl_stats"] = dev(8 * _lib.VKL_COUNT)
+                qs = (g.random(min(total * B, 1 << 22)) / B).astype(np.float32)
+                for off in range(0, total * B, 1 << 22):
+                    put(blocks["distrib"] + 4 * off,
+                        qs[:min(1 << 22, total * B - off)])
             chunk = 1 << 22
             zs = g.standard_normal(min(n * B, chunk)).astype(np.float32)
             for off in range(0, n * B, chunk):
@@ -134,13 +147,16 @@ def main():
                 (g.random(total) * 0.5 + 0.01).astype(np.float32))
             put(blocks["adv"], g.standard_normal(total).astype(np.float32))
             put(blocks["target"], g.standard_normal(total).astype(np.float32))
-            for name, probs, stats in (("venv_policy_loss", 0, 0),
-                                       ("venv_policy_loss +probs", 1, 0),
-                                       ("venv_policy_loss +stats", 0, 1),
-                                       ("venv_policy_loss +probs +stats", 1,
-                                        1),
-                                       ("venv_policy_loss run (no list)", 0,
-                                        0)):
+            arms = [("venv_policy_loss", 0, 0),
+                    ("venv_policy_loss +probs", 1, 0),
+                    ("venv_policy_loss +stats", 0, 1),
+                    ("venv_policy_loss +probs +stats", 1, 1),
+                    ("venv_policy_loss run (no list)", 0, 0)]
+            if a.kl:
+                arms += [("venv_policy_loss kl", 0, 0),
+                         ("venv_policy_loss kl +kl_stats", 0, 0),
+                         ("venv_policy_loss clipped +kl_stats", 0, 0)]
+            for name, probs, stats in arms:
                 v = _lib.VenvLoss()
                 v.policy, v.kind = blocks["z"], _lib.ACT_LOGITS
                 v.loss = _lib.LOSS_CLIPPED
@@ -154,6 +170,13 @@ def main():
                 v.dvalue = blocks["dvalue"]
                 v.probs_out = blocks["probs"] if probs else None
                 v.stats = blocks["stats"] if stats else None
+                gathers_q = "kl" in name
+                if gathers_q:
+                    v.distrib, v.beta = blocks["distrib"], 0.05
+                    if " kl" in name:
+                        v.loss = _lib.LOSS_KL_REGULATED
+                    if "kl_stats" in name:
+                        v.kl_stats = blocks["kl_stats"]
 
                 def launch():
                     check(lib.xh_venv_policy_loss(env.h, C.byref(v)))
@@ -171,7 +194,8 @@ def main():
                     per.append(ms / a.launches)
                 med = float(np.median(per))
                 nbytes = n * (8 * B + (4 * B if probs else 0) + 28
-                              - (0 if v.rows_dev else 4))
+                              - (0 if v.rows_dev else 4)
+                              + (4 * B if gathers_q else 0))
                 rows_out.append({"kernel": name, "rows": n, "bins": B,
                                  "bytes": nbytes, "ms": med,
                                  "ms_min": min(per), "ms_max": max(per),

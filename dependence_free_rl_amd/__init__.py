@@ -34,7 +34,7 @@ from ._lib import (VLOSS_CLIPPED, VLOSS_COUNT, VLOSS_ENTROPY_SUM,  # noqa: F401
                    VLOSS_VERR_SUM)
 from ._lib import (VKL_COUNT, VKL_KL_SQSUM, VKL_KL_SUM,  # noqa: F401
                    VKL_ROWS)
-from .venv import VecEnv  # noqa: F401
+from .venv import VecEnv, legal_words, pack_legal, unpack_legal  # noqa: F401
 
 __all__ = ["Context", "Trainer", "POLICY", "VALUE", "init_policy", "init_value",
            "init_full_policy", "clip_grad_norm", "describe_state", "digest",

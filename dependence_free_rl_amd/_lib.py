@@ -178,6 +178,14 @@ def _load():
         "xh_venv_record_distrib_bytes": (sz, [vp]),
         "xh_venv_record_distrib_ptr": (vp, [vp]),
         "xh_venv_get_record_distrib": (i, [vp, vp, sz]),
+        "xh_venv_legal_words": (i, [vp]),
+        "xh_venv_set_action_mask": (i, [vp, i]),
+        "xh_venv_legal": (i, [vp, vp]),
+        "xh_venv_legal_ptr": (vp, [vp]),
+        "xh_venv_record_legal_bytes": (sz, [vp]),
+        "xh_venv_record_legal_ptr": (vp, [vp]),
+        "xh_venv_get_record_legal": (i, [vp, vp, sz]),
+        "xh_venv_policy_loss_masked": (i, [vp, C.POINTER(VenvLoss), vp]),
         "xh_venv_kl_beta": (i, [vp, vp, C.c_float, vp, vp]),
         "xh_venv_record_obs": (i, [vp, i, vp, C.c_long, C.c_long, vp]),
         "xh_venv_record_ends": (i, [vp, vp, vp]),

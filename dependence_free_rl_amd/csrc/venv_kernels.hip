@@ -260,7 +260,134 @@ __global__ __launch_bounds__(256) void venv_step_kernel(VenvArgs a) {
 #endif
 constexpr bool kVActOwner = XH_VACT_OWNER_STORES != 0;
 
-template <int B, int D, bool RD>
+// ---------------------------------------------------------- legal sets --
+// Invalid-action masking (xh_venv_set_action_mask, xh_venv_legal).  Bin b
+// takes the item iff bins[b][d] >= item[d] for every d < D (environment::
+// apply's bin stays non-negative; any other pick is game over).  legal(e) is
+// that set, eff(e) = legal(e) if it is not empty, else all B bins: when
+// nothing fits every pick ends the episode and the row is used as given.
+//
+// venv_legal_bits: the lane's bins (VStepShape: BPL consecutive ones, their
+// int8 words wv[] already in registers) against the item word, bit k = the
+// lane's k-th bin -- D signed byte compares per bin, no loads.
+// venv_eff_bits: one segment ballot tells whether the env has a legal bin.
+// venv_legal_words: the env's W = max(1, B / 32) words, bit b % 32 of word b /
+// 32 = bin b.  A lane's 16 bits are one half-word: an xor-1 shuffle pairs them
+// on the even lanes, W shuffles bring the pairs to every lane of the env.
+// venv_store_words: one plain vector store by one lane of the env, 16 bytes at
+// 128 bins (row e of an [..][W] array off a 256-byte aligned base is aligned
+// to its 4 W bytes).
+template <int B>
+struct VLegal {
+  static constexpr int W = B >= 32 ? B / 32 : 1;
+};
+
+template <int B, int D>
+__device__ __forceinline__ uint32_t venv_legal_bits(
+    const uint32_t (&wv)[VStepShape<B, D>::NW], unsigned itw) {
+  using S = VStepShape<B, D>;
+  // The words through an empty asm: the act kernel unpacks the same bytes
+  // again after its pick, and merged with these extractions the BPL D
+  // unpacked ints would stay live across the softmax and the pick (+16 D
+  // registers, a wave per SIMD less at 64 and 128 bins); the extraction is
+  // cheaper than the registers.
+  uint32_t ww[S::NW];
+#pragma unroll
+  for (int q = 0; q < S::NW; ++q) {
+    ww[q] = wv[q];
+    asm("" : "+v"(ww[q]));
+  }
+  uint32_t lb = 0u;
+#pragma unroll
+  for (int k = 0; k < S::BPL; ++k) {
+    bool fits = true;
+#pragma unroll
+    for (int d = 0; d < D; ++d) {
+      const int j = k * D + d;
+      const int bv = (int)(signed char)((ww[j >> 2] >> (8 * (j & 3))) & 0xff);
+      const int iv = (int)(signed char)((itw >> (8 * d)) & 0xff);
+      fits &= bv >= iv;
+    }
+    lb |= (uint32_t)fits << k;
+  }
+  return lb;
+}
+
+template <int B, int D>
+__device__ __forceinline__ uint32_t venv_eff_bits(uint32_t lb,
+                                                  unsigned long long segmask) {
+  using S = VStepShape<B, D>;
+  const bool any = (__ballot(lb != 0u) & segmask) != 0;
+  return any ? lb : (1u << S::BPL) - 1u;
+}
+
+template <int B, int D>
+__device__ __forceinline__ void venv_legal_words(uint32_t eb, int seg0,
+                                                 uint32_t (&wd)[VLegal<B>::W]) {
+  using S = VStepShape<B, D>;
+  if constexpr (S::LPE == 1) {
+    wd[0] = eb;
+  } else {
+    const uint32_t pair = eb | ((uint32_t)__shfl_xor((int)eb, 1, kWave) << 16);
+#pragma unroll
+    for (int w = 0; w < VLegal<B>::W; ++w)
+      wd[w] = (uint32_t)__shfl((int)pair, seg0 + 2 * w, kWave);
+  }
+}
+
+template <int W>
+__device__ __forceinline__ void venv_store_words(uint32_t *dst,
+                                                 const uint32_t (&wd)[W]) {
+  if constexpr (W == 4)
+    *reinterpret_cast<uint4 *>(__builtin_assume_aligned(dst, 16)) =
+        make_uint4(wd[0], wd[1], wd[2], wd[3]);
+  else if constexpr (W == 2)
+    *reinterpret_cast<uint2 *>(__builtin_assume_aligned(dst, 8)) =
+        make_uint2(wd[0], wd[1]);
+  else
+    *dst = wd[0];
+}
+
+// xh_venv_legal: eff of every env's current state, out [N][W].  The act
+// kernel's layout and decode; reads bins and items, writes nothing else.
+template <int B, int D>
+__global__ __launch_bounds__(256) void venv_legal_kernel(VenvArgs a,
+                                                         uint32_t *out) {
+  using S = VStepShape<B, D>;
+  const int lane = threadIdx.x & 63;
+  const int wave = (xcd_block() * (int)blockDim.x + (int)threadIdx.x) >> 6;
+  const int el = lane / S::LPE, li = lane % S::LPE;
+  const int env = wave * S::EPW + el;
+  const int seg0 = el * S::LPE;
+  const bool in_range = env < a.N;
+  const size_t ec = in_range ? (size_t)env : 0;
+  const uint32_t *wp = reinterpret_cast<const uint32_t *>(
+      __builtin_assume_aligned(a.bins + ec * S::BD + li * S::BPL * D, S::ALIGN));
+  uint32_t wv[S::NW];
+#pragma unroll
+  for (int q = 0; q < S::NW; ++q) wv[q] = wp[q];
+  const unsigned itw = *reinterpret_cast<const unsigned *>(a.items + ec * 4);
+  const unsigned long long segmask =
+      S::LPE == 64 ? ~0ull : ((1ull << S::LPE) - 1ull) << seg0;
+  const uint32_t eb =
+      venv_eff_bits<B, D>(venv_legal_bits<B, D>(wv, itw), segmask);
+  uint32_t wd[VLegal<B>::W];
+  venv_legal_words<B, D>(eb, seg0, wd);
+  if (in_range && li == 0)
+    venv_store_words<VLegal<B>::W>(out + (size_t)env * VLegal<B>::W, wd);
+}
+
+// MASK (a.legal, xh_venv_set_action_mask): entry k of the row outside eff(e)
+// is replaced right after the loads, before anything reads it -- by -inf
+// under logits, by +0.0f under probabilities, in both pick modes -- so the
+// call does bit for bit what the other instantiation does on the premasked
+// rows: expf(-inf - m) is exactly 0, m is the maximum of the legal entries,
+// and adding zeros changes no sum.  A NaN in a replaced entry is not seen; a
+// probability row whose legal entries sum to zero is refused as a zero-sum
+// row.  The words it masked with go to a.rec_legal's slot (where not null),
+// also for a refused env: they are a function of the state before the step.
+// The other instantiation holds none of this.
+template <int B, int D, bool RD, bool MASK>
 __global__ __launch_bounds__(256) void venv_act_kernel(VenvActArgs a) {
   using S = VStepShape<B, D>;
   static_assert(S::BPL % 4 == 0, "the lane's floats as 16-byte loads");
@@ -297,6 +424,18 @@ __global__ __launch_bounds__(256) void venv_act_kernel(VenvActArgs a) {
   for (int q = 0; q < S::NW; ++q) wv[q] = wp[q];
   const unsigned itw = *reinterpret_cast<const unsigned *>(ip);
   uint32_t x = a.v.rng[ec];
+
+  [[maybe_unused]] uint32_t eb = 0u;  // the lane's bits of eff(e) (MASK)
+  if constexpr (MASK) {
+    // the premasked row: everything below reads z[] as if the caller had
+    // passed it this way
+    const unsigned long long sm =
+        S::LPE == 64 ? ~0ull : ((1ull << S::LPE) - 1ull) << seg0;
+    eb = venv_eff_bits<B, D>(venv_legal_bits<B, D>(wv, itw), sm);
+    const float out = a.logits ? -INFINITY : 0.0f;
+#pragma unroll
+    for (int k = 0; k < S::BPL; ++k) z[k] = (eb >> k) & 1u ? z[k] : out;
+  }
 
   // the row's probabilities
   float p[S::BPL];
@@ -423,10 +562,17 @@ __global__ __launch_bounds__(256) void venv_act_kernel(VenvActArgs a) {
   }
   const bool over = (__ballot(neg_any) & segmask) != 0;
   const bool chosen_over = (__ballot(neg_chosen) & segmask) != 0;
+  [[maybe_unused]] uint32_t lw[VLegal<B>::W];  // the env's words (every lane
+                                               // takes part in the shuffles)
+  if constexpr (MASK) venv_legal_words<B, D>(eb, seg0, lw);
   if (!in_range) return;
 
   // the record's slot: the state before the step (also of a refused env)
   const size_t ro = (size_t)a.slot * a.v.N + env;
+  if constexpr (MASK) {
+    if (a.rec_legal && li == 0)
+      venv_store_words<VLegal<B>::W>(a.rec_legal + ro * VLegal<B>::W, lw);
+  }
   if (a.rec_bins) {
     uint32_t *rp = reinterpret_cast<uint32_t *>(__builtin_assume_aligned(
         a.rec_bins + ro * S::BD + li * S::BPL * D, S::ALIGN));
@@ -605,17 +751,47 @@ hipError_t launch_venv(const VenvArgs &a, int op, hipStream_t s) {
   return hipErrorInvalidValue;
 }
 
+// RD where the call records its distributions, MASK where it masks
+template <int B, int D>
+static void vact_launch(const VenvActArgs &a, hipStream_t s) {
+  const dim3 grid = venv_step_grid(a.v.N, B);
+  if (a.legal) {
+    if (a.rec_distrib)
+      hipLaunchKernelGGL((venv_act_kernel<B, D, true, true>), grid, dim3(256),
+                         0, s, a);
+    else
+      hipLaunchKernelGGL((venv_act_kernel<B, D, false, true>), grid, dim3(256),
+                         0, s, a);
+  } else {
+    if (a.rec_distrib)
+      hipLaunchKernelGGL((venv_act_kernel<B, D, true, false>), grid, dim3(256),
+                         0, s, a);
+    else
+      hipLaunchKernelGGL((venv_act_kernel<B, D, false, false>), grid,
+                         dim3(256), 0, s, a);
+  }
+}
+
 hipError_t launch_venv_act(const VenvActArgs &a, hipStream_t s) {
   const int B = a.v.env.B, D = a.v.env.D;
   if (a.v.N <= 0) return hipSuccess;
 #define X(XB, XD)                                                            \
   if (B == XB && D == XD) {                                                  \
-    if (a.rec_distrib)                                                       \
-      hipLaunchKernelGGL((venv_act_kernel<XB, XD, true>),                    \
-                         venv_step_grid(a.v.N, B), dim3(256), 0, s, a);      \
-    else                                                                     \
-      hipLaunchKernelGGL((venv_act_kernel<XB, XD, false>),                   \
-                         venv_step_grid(a.v.N, B), dim3(256), 0, s, a);      \
+    vact_launch<XB, XD>(a, s);                                               \
+    return hipGetLastError();                                                \
+  }
+  XH_VENV_SHAPES(X)
+#undef X
+  return hipErrorInvalidValue;
+}
+
+hipError_t launch_venv_legal(const VenvArgs &a, uint32_t *out, hipStream_t s) {
+  const int B = a.env.B, D = a.env.D;
+  if (a.N <= 0) return hipSuccess;
+#define X(XB, XD)                                                            \
+  if (B == XB && D == XD) {                                                  \
+    hipLaunchKernelGGL((venv_legal_kernel<XB, XD>), venv_step_grid(a.N, B),  \
+                       dim3(256), 0, s, a, out);                             \
     return hipGetLastError();                                                \
   }
   XH_VENV_SHAPES(X)

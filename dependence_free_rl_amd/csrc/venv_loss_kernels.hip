@@ -20,7 +20,8 @@
 // gradient), another 4 B with probs_out, and about 20 gathered (the index,
 // action, p_old, adv, target; + 8 with the value head's values_new / dvalue);
 // with XH_LOSS_KL_REGULATED or kl_stats another 4 B gathered (the row's
-// sampling distribution).
+// sampling distribution); with legal words (xh_venv_policy_loss_masked)
+// another 4 W, W = max(1, B / 32).
 #include "xh_device.h"
 #include "xh_diag.h"
 #include "xh_kernels.h"
@@ -57,7 +58,16 @@ constexpr bool kVLossOwner = XH_VLOSS_OWNER_STORES != 0;
 // action_loss_kernel's expressions); 2 also the row's exact KL(q || p) in
 // double for kl_stats (a.kl_part != nullptr; diag_bin_terms' form: a term
 // with q_k == 0 is 0, nothing else is masked), under any loss kind.
-template <int B, bool STATS, int KL>
+// MASK (a.legal != nullptr, xh_venv_policy_loss_masked): the row's W = max(1,
+// B / 32) legal words are gathered through q beside action[q] -- each lane
+// its own half-word (a lane's 16 bins; all 8 bits at 8 bins), 4 W more bytes
+// per row, in the round trip of the row's other gathers -- and entry k outside the set is replaced right after the row is
+// loaded, by -inf under logits and by +0.0f under probabilities, before
+// anything reads it: the launch does bit for bit what the other instantiation
+// does on the premasked rows, as venv_act_kernel's MASK does.  A row whose
+// words are all zero is left as it is.  The other instantiation holds none of
+// this.
+template <int B, bool STATS, int KL, bool MASK>
 __global__ __launch_bounds__(256) void venv_policy_loss_kernel(VenvLossArgs a) {
 #pragma clang fp contract(off)
   using S = VLossShape<B>;
@@ -85,6 +95,7 @@ __global__ __launch_bounds__(256) void venv_policy_loss_kernel(VenvLossArgs a) {
     int ch = 0, ok = 0;
     long long qrow = 0;
     float q_old = 0.0f, A = 0.0f, tg = 0.0f, vn = 0.0f;
+    [[maybe_unused]] uint32_t hw = 0u;  // the lane's legal half-word (MASK)
     if (in_range) {
       const vl_f4 *zp = reinterpret_cast<const vl_f4 *>(
           __builtin_assume_aligned(a.policy + (size_t)j * B + li * S::BPL, 16));
@@ -95,6 +106,15 @@ __global__ __launch_bounds__(256) void venv_policy_loss_kernel(VenvLossArgs a) {
         z[4 * w + 1] = t.y;
         z[4 * w + 2] = t.z;
         z[4 * w + 3] = t.w;
+      }
+      if constexpr (MASK) {
+        // every lane of the row reads the index itself (one address per row:
+        // no more traffic) and gathers its own word beside action[q], in the
+        // same round trip -- not a third one behind a shuffle of q
+        constexpr int W = B >= 32 ? B / 32 : 1;
+        const long qr = a.rows ? (long)a.rows[a.first + j] : a.first + j;
+        const long q = qr >= 0 && qr < a.total ? qr : 0;  // a bad index reads
+        hw = a.legal[(size_t)q * W + li / 2];             // row 0's
       }
       if (li == 0) {  // the row's gathers: one lane, 4-byte loads
         const long qr = a.rows ? (long)a.rows[a.first + j] : a.first + j;
@@ -120,9 +140,19 @@ __global__ __launch_bounds__(256) void venv_policy_loss_kernel(VenvLossArgs a) {
     }
     const bool valid = in_range && ok;
     const int chc = valid ? ch : 0;
+    if constexpr (KL > 0 && S::LPE > 1) qrow = __shfl(qrow, seg0, kWave);
+    if constexpr (MASK) {
+      hw = (hw >> (16 * (li & 1))) & ((1u << S::BPL) - 1u);
+      const unsigned long long segmask =
+          S::LPE == 64 ? ~0ull : ((1ull << S::LPE) - 1ull) << seg0;
+      const bool any = (__ballot(hw != 0u) & segmask) != 0;
+      const float out = a.logits ? -INFINITY : 0.0f;
+#pragma unroll
+      for (int k = 0; k < S::BPL; ++k)
+        z[k] = !any || ((hw >> k) & 1u) ? z[k] : out;
+    }
     float qd[S::BPL];  // the row's sampling distribution (KL > 0)
     if constexpr (KL > 0) {
-      if constexpr (S::LPE > 1) qrow = __shfl(qrow, seg0, kWave);
 #pragma unroll
       for (int k = 0; k < S::BPL; ++k) qd[k] = 0.0f;
       if (in_range) {  // a bad index reads row 0's, as the other gathers do
@@ -296,15 +326,23 @@ int venv_loss_grid(int B, long count) {
                                                            : tiles));
 }
 
-// the STATS instantiation where the call asks for stats (a.part)
+// the STATS instantiation where the call asks for stats (a.part), the MASK
+// one where it brings legal words (a.legal)
+template <int B, int KL, bool MASK>
+static void vloss_launch_m(const VenvLossArgs &a, dim3 grid, hipStream_t s) {
+  if (a.part)
+    hipLaunchKernelGGL((venv_policy_loss_kernel<B, true, KL, MASK>), grid,
+                       dim3(256), 0, s, a);
+  else
+    hipLaunchKernelGGL((venv_policy_loss_kernel<B, false, KL, MASK>), grid,
+                       dim3(256), 0, s, a);
+}
 template <int B, int KL>
 static void vloss_launch(const VenvLossArgs &a, dim3 grid, hipStream_t s) {
-  if (a.part)
-    hipLaunchKernelGGL((venv_policy_loss_kernel<B, true, KL>), grid, dim3(256),
-                       0, s, a);
+  if (a.legal)
+    vloss_launch_m<B, KL, true>(a, grid, s);
   else
-    hipLaunchKernelGGL((venv_policy_loss_kernel<B, false, KL>), grid, dim3(256),
-                       0, s, a);
+    vloss_launch_m<B, KL, false>(a, grid, s);
 }
 
 hipError_t launch_venv_policy_loss(VenvLossArgs a, hipStream_t s) {

@@ -364,12 +364,23 @@ struct VenvActArgs {
   int8_t *rec_bins;       // [T][N][B][D] the state before the step, or null
   int8_t *rec_items;      // [T][N][4]
   int slot;
+  // invalid-action masking (xh_venv_set_action_mask): legal != 0 picks the
+  // MASK instantiation, which replaces the row's entries outside the env's
+  // legal set before anything reads them
+  int legal;
   float *rec_distrib;     // [T][N][B] the p[] sampled from, or null
                           // (xh_venv_set_record_distrib)
+  uint32_t *rec_legal;    // [T][N][W] the words it masked with (legal), or null
 };
+// the packed legal set: W = max(1, B / 32) uint32 words per env, bit b % 32
+// of word b / 32 is bin b
+inline int venv_legal_words(int B) { return B >= 32 ? B / 32 : 1; }
 bool venv_shape_supported(int B, int D);
 hipError_t launch_venv(const VenvArgs &a, int op, hipStream_t s);
 hipError_t launch_venv_act(const VenvActArgs &a, hipStream_t s);
+// xh_venv_legal: out [N][W], the legal set (all bins where it is empty) of
+// every env's current state; reads a.bins / a.items only
+hipError_t launch_venv_legal(const VenvArgs &a, uint32_t *out, hipStream_t s);
 hipError_t launch_venv_init(const VenvArgs &a, uint32_t x0, int env_offset,
                             int n_global, int k, hipStream_t s);
 
@@ -444,6 +455,8 @@ struct VenvLossArgs {
   float beta;                 // kLossKlRegulated: the regulation's weight ...
   const float *beta_dev;      // ... or, where not null, one device float
   double *kl_part;            // [venv_loss_grid][XH_VKL_COUNT] or nullptr
+  const uint32_t *legal;      // [total][W] the rows' legal words (a row of
+                              // zeros: unmasked), or nullptr (no mask code)
 };
 int venv_loss_grid(int B, long count);
 hipError_t launch_venv_policy_loss(VenvLossArgs a, hipStream_t s);

@@ -78,6 +78,14 @@ struct xh_venv {
   // xh_venv_act sampled from; dropped with the record
   float *rec_distrib = nullptr;
   size_t rec_distrib_bytes = 0;
+  // xh_venv_set_action_mask: while it is on and a record exists, u32
+  // [rec_steps][N][W] -- the legal words each recorded xh_venv_act masked
+  // with; allocated and dropped with the record
+  bool mask_on = false;
+  uint32_t *rec_legal = nullptr;
+  size_t rec_legal_bytes = 0;
+  // xh_venv_legal's own [N][W] output, allocated at its first use
+  uint32_t *legal_buf = nullptr;
   // scratch of xh_venv_record_ends / xh_venv_advantages, allocated at their
   // first use: launch_end_list's block totals and n_open; the scan's block
   // partials [venv_gae_grid(N)][2], their ended-row counts, and stats [4]
@@ -2538,7 +2546,39 @@ void venv_free_record(xh_venv *v) {
   if (v->rec_distrib) (void)hipFree(v->rec_distrib);
   v->rec_distrib = nullptr;
   v->rec_distrib_bytes = 0;
+  if (v->rec_legal) (void)hipFree(v->rec_legal);
+  v->rec_legal = nullptr;
+  v->rec_legal_bytes = 0;
   v->rec_steps = v->rec_pos = 0;
+}
+// the record's zero-filled legal words (the mask is on, a record exists)
+int venv_alloc_rec_legal(xh_venv *v) {
+  const size_t bytes = (size_t)v->rec_steps * v->N *
+                       xh::venv_legal_words(v->env.B) * 4;
+  void *p = nullptr;
+  if (hipMalloc(&p, bytes) != hipSuccess)
+    return fail(XH_ERR_HIP, "venv action mask: allocating %zu bytes", bytes);
+  if (hipMemsetAsync(p, 0, bytes, v->ctx->stream) != hipSuccess) {
+    (void)hipFree(p);
+    return fail(XH_ERR_HIP, "venv action mask: zero fill");
+  }
+  v->rec_legal = (uint32_t *)p;
+  v->rec_legal_bytes = bytes;
+  return XH_OK;
+}
+int venv_ensure_legal_buf(xh_venv *v) {
+  if (v->legal_buf) return XH_OK;
+  HIPCHK(hipSetDevice(v->ctx->device));
+  const size_t bytes = (size_t)v->N * xh::venv_legal_words(v->env.B) * 4;
+  void *p = nullptr;
+  if (hipMalloc(&p, bytes) != hipSuccess)
+    return fail(XH_ERR_HIP, "venv legal: allocating %zu bytes", bytes);
+  if (hipMemsetAsync(p, 0, bytes, v->ctx->stream) != hipSuccess) {
+    (void)hipFree(p);
+    return fail(XH_ERR_HIP, "venv legal: zero fill");
+  }
+  v->legal_buf = (uint32_t *)p;
+  return XH_OK;
 }
 }  // namespace
 extern "C" {
@@ -2618,6 +2658,7 @@ int xh_venv_destroy(xh_venv *v) {
     if (v->adv_part) (void)hipFree(v->adv_part);  // adv_stats, adv_end_part too
     if (v->loss_part) (void)hipFree(v->loss_part);
     if (v->kl_part) (void)hipFree(v->kl_part);
+    if (v->legal_buf) (void)hipFree(v->legal_buf);
     venv_free_record(v);
     xh_ctx *c = v->ctx;
     const bool counted = v->counted;
@@ -2817,7 +2858,9 @@ int xh_venv_act(xh_venv *v, const float *policy_dev, int kind, int mode,
       a.rec_items = (int8_t *)v->rec[XH_VREC_ITEMS];
       a.slot = v->rec_pos;
       a.rec_distrib = v->rec_distrib;
+      a.rec_legal = v->rec_legal;
     }
+    a.legal = v->mask_on ? 1 : 0;
     const int st = venv_timed(
         v, [&] { return xh::launch_venv_act(a, v->ctx->stream); });
     if (st == XH_OK && v->rec_steps > 0) ++v->rec_pos;
@@ -2848,6 +2891,13 @@ int xh_venv_set_record(xh_venv *v, int steps, int with_states) {
       v->rec_bytes[w] = sz[w];
     }
     v->rec_steps = steps;
+    if (v->mask_on)
+      if (const int st = venv_alloc_rec_legal(v)) {
+        std::string keep = g_err;
+        venv_free_record(v);
+        g_err = keep;
+        return st;
+      }
     return XH_OK;
   });
 }
@@ -2942,6 +2992,85 @@ int xh_venv_get_record_distrib(xh_venv *v, float *host, size_t bytes) {
                   "%zu", bytes, v->rec_distrib_bytes);
     HIPCHK(hipSetDevice(v->ctx->device));
     HIPCHK(copy_to_host(host, v->rec_distrib, bytes, v->ctx->stream));
+    HIPCHK(hipStreamSynchronize(v->ctx->stream));
+    return XH_OK;
+  });
+}
+
+// ---- invalid-action masking (venv_legal_kernel, venv_act_kernel's MASK) ----
+int xh_venv_legal_words(const xh_venv *v) {
+  return v ? xh::venv_legal_words(v->env.B) : 0;
+}
+
+int xh_venv_set_action_mask(xh_venv *v, int on) {
+  return guard([&]() -> int {
+    if (!v) return fail(XH_ERR_INVALID, "null venv");
+    HIPCHK(hipSetDevice(v->ctx->device));
+    if (!on) {
+      if (v->rec_legal) {
+        HIPCHK(hipStreamSynchronize(v->ctx->stream));
+        (void)hipFree(v->rec_legal);
+        v->rec_legal = nullptr;
+        v->rec_legal_bytes = 0;
+      }
+      v->mask_on = false;
+      return XH_OK;
+    }
+    if (v->rec_steps > 0 && v->rec_pos != 0)
+      return fail(XH_ERR_STATE, "venv action mask: the record's cursor is at "
+                  "%d; turn it on at cursor 0 (xh_venv_record_rewind), so "
+                  "every recorded slot has its legal words", v->rec_pos);
+    if (v->rec_steps > 0 && !v->rec_legal)
+      if (const int st = venv_alloc_rec_legal(v)) return st;
+    v->mask_on = true;
+    return XH_OK;
+  });
+}
+
+int xh_venv_legal(xh_venv *v, uint32_t *out_dev) {
+  return guard([&]() -> int {
+    if (!v) return fail(XH_ERR_INVALID, "null venv");
+    const int W = xh::venv_legal_words(v->env.B);
+    if (reinterpret_cast<uintptr_t>(out_dev) & (uintptr_t)(4 * W - 1))
+      return fail(XH_ERR_INVALID, "venv legal: out_dev must be %d-byte aligned "
+                  "(the kernel stores an env's words as one piece)", 4 * W);
+    HIPCHK(hipSetDevice(v->ctx->device));
+    if (!out_dev)
+      if (const int st = venv_ensure_legal_buf(v)) return st;
+    uint32_t *out = out_dev ? out_dev : v->legal_buf;
+    const xh::VenvArgs a = v->args();
+    return venv_timed(
+        v, [&] { return xh::launch_venv_legal(a, out, v->ctx->stream); });
+  });
+}
+
+uint32_t *xh_venv_legal_ptr(xh_venv *v) {
+  if (!v) return nullptr;
+  uint32_t *p = nullptr;
+  guard([&]() -> int {
+    const int st = venv_ensure_legal_buf(v);
+    if (st == XH_OK) p = v->legal_buf;
+    return st;
+  });
+  return p;
+}
+
+size_t xh_venv_record_legal_bytes(const xh_venv *v) {
+  return v ? v->rec_legal_bytes : 0;
+}
+
+uint32_t *xh_venv_record_legal_ptr(xh_venv *v) {
+  return v ? v->rec_legal : nullptr;
+}
+
+int xh_venv_get_record_legal(xh_venv *v, uint32_t *host, size_t bytes) {
+  return guard([&]() -> int {
+    if (!v || !host) return fail(XH_ERR_INVALID, "null arg");
+    if (!v->rec_legal || bytes != v->rec_legal_bytes)
+      return fail(XH_ERR_INVALID, "venv record legal: %zu bytes, expected "
+                  "%zu", bytes, v->rec_legal_bytes);
+    HIPCHK(hipSetDevice(v->ctx->device));
+    HIPCHK(copy_to_host(host, v->rec_legal, bytes, v->ctx->stream));
     HIPCHK(hipStreamSynchronize(v->ctx->stream));
     return XH_OK;
   });
@@ -3084,10 +3213,29 @@ int xh_venv_advantages(xh_venv *v, const xh_venv_adv *p) {
   });
 }
 
-int xh_venv_policy_loss(xh_venv *v, const xh_venv_loss *p) {
+}  // extern "C"
+namespace {
+// xh_venv_policy_loss (masked == false; legal_dev unused) and
+// xh_venv_policy_loss_masked (legal_dev, or with NULL the record's words)
+int venv_policy_loss(xh_venv *v, const xh_venv_loss *p, bool masked,
+                     const uint32_t *legal_dev) {
   return guard([&]() -> int {
     if (!v) return fail(XH_ERR_INVALID, "null venv");
     if (!p) return fail(XH_ERR_INVALID, "venv policy loss: null args");
+    const uint32_t *legal = nullptr;
+    if (masked) {
+      legal = legal_dev ? legal_dev : v->rec_legal;
+      if (!legal)
+        return fail(XH_ERR_STATE, "venv policy loss: legal_dev NULL takes the "
+                    "record's legal words and there are none "
+                    "(xh_venv_set_action_mask with a record)");
+      if (!legal_dev && (p->action || p->p_old))
+        return fail(XH_ERR_INVALID, "venv policy loss: the record's legal "
+                    "words go with the record's rows (action and p_old NULL)");
+      if (reinterpret_cast<uintptr_t>(legal) & 3)
+        return fail(XH_ERR_INVALID, "venv policy loss: legal_dev must be "
+                    "4-byte aligned");
+    }
     if (!p->policy || !p->adv || !p->grad)
       return fail(XH_ERR_INVALID, "venv policy loss: null policy / adv / grad");
     if (p->kind != XH_ACT_PROBS && p->kind != XH_ACT_LOGITS)
@@ -3208,6 +3356,7 @@ int xh_venv_policy_loss(xh_venv *v, const xh_venv_loss *p) {
     a.probs_out = p->probs_out;
     a.part = p->stats ? v->loss_part : nullptr;
     a.err = v->err;
+    a.legal = legal;
     CHK(venv_timed(v, [&] { return xh::launch_venv_policy_loss(a, s); }));
     hipError_t e = hipSuccess;
     if (p->stats)
@@ -3221,6 +3370,17 @@ int xh_venv_policy_loss(xh_venv *v, const xh_venv_loss *p) {
       return fail(XH_ERR_HIP, "venv policy loss: %s", hipGetErrorString(e));
     return XH_OK;
   });
+}
+}  // namespace
+extern "C" {
+
+int xh_venv_policy_loss(xh_venv *v, const xh_venv_loss *p) {
+  return venv_policy_loss(v, p, false, nullptr);
+}
+
+int xh_venv_policy_loss_masked(xh_venv *v, const xh_venv_loss *p,
+                               const uint32_t *legal_dev) {
+  return venv_policy_loss(v, p, true, legal_dev);
 }
 
 int xh_venv_kl_beta(xh_venv *v, const double *kl_stats_dev, float d_targ,

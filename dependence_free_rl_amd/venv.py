@@ -16,6 +16,11 @@ one launch, recording the trajectory):
     batch = env.record()                # action / pchoice / reward / done /
                                         # bins / items, [T][N]...
 
+Invalid-action masking is opt-in: env.set_action_mask(True) makes act() mask
+each row by the env's legal bins (record()["legal"] keeps the sets),
+policy_loss(..., legal=True) masks the minibatch the same way, and env.legal()
+returns the current states' sets.
+
 Mirrors xylo::environment<A,S>::apply / view / reset (rl.h:163-170) with the
 id ranging over the batch, bp::environment (bin_packing.h:46-85) and
 xylo::agent::step (rl.h:325-349).  State lives in HBM; numpy arrays here are
@@ -39,6 +44,30 @@ _MODES = {"sample": ACT_SAMPLE, "argmax": ACT_ARGMAX}
 
 def _ptr(a):
     return a.ctypes.data_as(C.c_void_p)
+
+
+def legal_words(B):
+    """W: uint32 words per env of a packed legal set (xh_venv_legal_words)."""
+    return max(1, B // 32)
+
+
+def pack_legal(legal):
+    """bool [..][B] -> uint32 [..][W]: bit b % 32 of word b // 32 is bin b."""
+    legal = np.asarray(legal, bool)
+    B = legal.shape[-1]
+    W = legal_words(B)
+    bits = legal.reshape(legal.shape[:-1] + (W, B // W)).astype(np.uint32)
+    shifts = np.arange(B // W, dtype=np.uint32)
+    return (bits << shifts).sum(-1, dtype=np.uint32)
+
+
+def unpack_legal(words, B):
+    """uint32 [..][W] -> bool [..][B], pack_legal's inverse."""
+    words = np.asarray(words, np.uint32)
+    W = legal_words(B)
+    shifts = np.arange(B // W, dtype=np.uint32)
+    bits = (words[..., None] >> shifts) & np.uint32(1)
+    return bits.reshape(words.shape[:-1] + (B,)).astype(bool)
 
 
 def _beta_ptr(beta):
@@ -123,6 +152,32 @@ class VecEnv:
                     self.get(VENV_REWARD), self.get(VENV_DONE))
         return None
 
+    # ---- invalid-action masking ------------------------------------------
+    def set_action_mask(self, on):
+        """Invalid-action masking for act() (xh_venv_set_action_mask): every
+        entry of an env's row outside its legal set -- the bins that take the
+        item; all bins where none does -- is replaced by -inf (logits) or 0
+        (probs) before the pick, and the record keeps the sets ("legal" of
+        record(), legal=True of policy_loss()).  Off at creation; with a
+        record, turn it on at cursor 0."""
+        check(_lib.lib.xh_venv_set_action_mask(self.h, 1 if on else 0))
+
+    def legal(self, packed=False, out=None):
+        """The legal set of every env's current state (xh_venv_legal; all
+        bins where nothing fits), with the mask on or off: bool [N][B], or the
+        uint32 [N][W] words when packed.  out: an integer device pointer that
+        receives the words (nothing is returned)."""
+        W = legal_words(self.B)
+        if out is not None:
+            check(_lib.lib.xh_venv_legal(self.h, int(out)))
+            return None
+        ptr = _lib.lib.xh_venv_legal_ptr(self.h)
+        if not ptr:
+            check(_lib.XH_ERR_HIP)
+        check(_lib.lib.xh_venv_legal(self.h, None))
+        words = self._download(ptr, np.uint32, (self.N, W))
+        return words if packed else unpack_legal(words, self.B)
+
     # ---- the trajectory record act() writes -----------------------------
     def set_record(self, steps, states=True, distrib=False):
         """Record the next `steps` act() calls (xh_venv_set_record); 0 turns
@@ -144,7 +199,8 @@ class VecEnv:
         pchoice / reward float32 [t][N], done uint8 [t][N] and, if recorded,
         the states before each step: bins int8 [t][N][B][D], items int8
         [t][N][4]; and, only while the distribution record is on, distrib
-        float32 [t][N][B]."""
+        float32 [t][N][B]; and, only while the action mask is on, legal bool
+        [t][N][B], the sets each slot's act() masked with."""
         N, B, D = self.N, self.B, self.D
         spec = {"action": (VREC_ACTION, np.int32, (N,)),
                 "pchoice": (VREC_PCHOICE, np.float32, (N,)),
@@ -165,6 +221,12 @@ class VecEnv:
             a = np.zeros(nbytes // 4, np.float32)
             check(_lib.lib.xh_venv_get_record_distrib(self.h, _ptr(a), nbytes))
             out["distrib"] = a.reshape(-1, N, B)[:pos]
+        nbytes = _lib.lib.xh_venv_record_legal_bytes(self.h)
+        if nbytes:
+            a = np.zeros(nbytes // 4, np.uint32)
+            check(_lib.lib.xh_venv_get_record_legal(self.h, _ptr(a), nbytes))
+            out["legal"] = unpack_legal(
+                a.reshape(-1, N, legal_words(B))[:pos], B)
         return out
 
     def rewind(self):
@@ -324,7 +386,8 @@ class VecEnv:
                     rows=None, first=0, count=None, eps=0.2, scale=1.0,
                     action=None, p_old=None, values=None, target=None,
                     value_scale=1.0, want_probs=False, want_stats=False,
-                    accumulate=False, beta=0.0, distrib=None, want_kl=False):
+                    accumulate=False, beta=0.0, distrib=None, want_kl=False,
+                    legal=None):
         """The loss head of the caller's network on a minibatch of the
         recorded window (xh_venv_policy_loss): from the network's output rows
         policy [count][B] ("logits": xh_venv_act's softmax first, or "probs")
@@ -345,7 +408,14 @@ class VecEnv:
         of host arrays: "grad" [count][B], and where asked "dvalue" [count],
         "probs" [count][B] and "stats" float64 [VLOSS_COUNT]; accumulate adds
         this call's statistics to the previous call's (the epoch's first
-        minibatch passes False)."""
+        minibatch passes False).
+
+        legal: None, today's call; otherwise the rows are premasked by their
+        legal sets first (xh_venv_policy_loss_masked): True takes the record's
+        (set_action_mask with a record; action / p_old must be the record's
+        too), or the caller's [total] sets indexed by q -- a host bool
+        [total][B] or uint32 [total][W] array, or an integer device pointer to
+        the words.  A set with no bin leaves its row unmasked."""
         B = self.B
         losses = {"clipped": _lib.LOSS_CLIPPED,
                   "log": _lib.LOSS_SOFTMAX_GRADIENT_LOG,
@@ -414,7 +484,26 @@ class VecEnv:
             a.beta = float(beta)
         if want_kl:
             a.kl_stats = self._scratch("vl_kl", _lib.VKL_COUNT * 8)
-        check(_lib.lib.xh_venv_policy_loss(self.h, C.byref(a)))
+        if legal is None:
+            check(_lib.lib.xh_venv_policy_loss(self.h, C.byref(a)))
+        else:
+            lptr = None
+            if isinstance(legal, (int, np.integer)) and not isinstance(
+                    legal, (bool, np.bool_)):
+                lptr = int(legal)
+            elif not isinstance(legal, (bool, np.bool_)):
+                w = np.asarray(legal)
+                if w.dtype == np.bool_:
+                    w = pack_legal(w.reshape(-1, B))
+                w = np.ascontiguousarray(w, np.uint32).reshape(
+                    -1, legal_words(B))
+                lptr = self._staged("vl_legal", w, np.uint32,
+                                    (total, legal_words(B)))
+            elif not legal:
+                raise ValueError("policy_loss: legal is None, True, an array "
+                                 "or a device pointer")
+            check(_lib.lib.xh_venv_policy_loss_masked(self.h, C.byref(a),
+                                                      lptr))
         out = {"grad": self._download(a.grad, np.float32, (count, B))}
         if values is not None:
             out["dvalue"] = self._download(a.dvalue, np.float32, (count,))

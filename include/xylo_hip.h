@@ -734,6 +734,64 @@ int xh_venv_set_record_distrib(xh_venv *v, int on);
 size_t xh_venv_record_distrib_bytes(const xh_venv *v);
 float *xh_venv_record_distrib_ptr(xh_venv *v);
 int xh_venv_get_record_distrib(xh_venv *v, float *host, size_t bytes);
+/* Invalid-action masking (opt-in; nothing in the reference masks, and with it
+ * off every launch is what it was).  Bin b takes env e's current item iff
+ * bins[b][d] >= item[d] for every d < D; any other pick ends the episode
+ * (bp::environment::apply, agent::game_over).  legal(e) is that set of bins and
+ * eff(e) = legal(e) if it is not empty, else all B bins: when nothing fits
+ * every pick ends the episode and the row is used as given.
+ *
+ * With the mask on, xh_venv_act on rows R does, bit for bit, what the
+ * unmasked call does on premask(R): entry k of env e's row outside eff(e) is
+ * replaced by -inf under XH_ACT_LOGITS and by +0.0f under XH_ACT_PROBS, in
+ * XH_ACT_SAMPLE and in XH_ACT_ARGMAX, right after the row is loaded and before
+ * anything reads it; the refusal checks, the softmax, the pick, PCHOICE, the
+ * recorded p_old and the distribution record are the unmasked call's text on
+ * that row (expf(-inf - m) is exactly 0, m is the maximum of the legal
+ * entries, adding zeros changes no sum).  So
+ *   - a NaN in an illegal entry is not seen;
+ *   - a probability row whose legal entries sum to zero is refused as a
+ *     zero-sum row is;
+ *   - XH_ACT_SAMPLE keeps std::discrete_distribution's one edge: with u = 0
+ *     exactly it picks index 0 even at probability 0; the record then has p_old
+ *     = 0 and xh_venv_policy_loss skips the row like a refused one.
+ *
+ * The sets are packed as uint32 words, W = max(1, B / 32) per env
+ * (xh_venv_legal_words): bit b % 32 of word b / 32 is bin b.
+ *
+ * xh_venv_set_action_mask: off at creation.  on != 0 with a record whose
+ *   cursor is not 0 is XH_ERR_STATE (every recorded slot is to have its words;
+ *   xh_venv_record_rewind first).  While the mask is on and a record exists a
+ *   zero-filled uint32 [T][N][W] block exists with it: xh_venv_set_record
+ *   allocates and drops it with the record, xh_venv_record_rewind keeps it,
+ *   on == 0 frees it.  The xh_venv_act call at cursor t writes slot t from its
+ *   own launch (4 W more bytes per env and step): the eff(e) it masked with, a
+ *   function of the state before the step, so also for a refused env.
+ *   xh_venv_record_legal_bytes / _ptr / xh_venv_get_record_legal follow the
+ *   _distrib accessors' contract.
+ * xh_venv_legal: eff(e) of every env's current state, [N][W] words, in one
+ *   asynchronous launch on the context's stream, with the mask on or off (for
+ *   a caller that masks inside its own network, or evaluates).  out_dev is
+ *   device memory aligned to 4 W bytes; NULL writes a buffer the venv owns,
+ *   allocated at first use, whose address is xh_venv_legal_ptr(v).
+ * xh_venv_policy_loss_masked: xh_venv_policy_loss on the minibatch's rows
+ *   premasked the same way, bit for bit -- grad, probs_out, dvalue, stats and
+ *   kl_stats.  Row j's set is legal_dev[q][0..W), gathered through the same
+ *   index q as action and p_old ([total][W], 4 W more bytes per row); a row
+ *   whose words are all zero is left unmasked, so a zero-filled array is safe.
+ *   legal_dev == NULL takes the record's block: XH_ERR_STATE if there is none,
+ *   and XH_ERR_INVALID unless a->action == a->p_old == NULL (the record's
+ *   rows).  The softmax is still the one xh_venv_act compiled, so while the
+ *   parameters have not moved every ratio is exactly 1.0f under masking too;
+ *   gradient entries at masked bins are zeros (of either sign).
+ *   xh_venv_policy_loss itself is unchanged. */
+int xh_venv_legal_words(const xh_venv *v);
+int xh_venv_set_action_mask(xh_venv *v, int on);
+int xh_venv_legal(xh_venv *v, uint32_t *out_dev);
+uint32_t *xh_venv_legal_ptr(xh_venv *v);
+size_t xh_venv_record_legal_bytes(const xh_venv *v);
+uint32_t *xh_venv_record_legal_ptr(xh_venv *v);
+int xh_venv_get_record_legal(xh_venv *v, uint32_t *host, size_t bytes);
 /* From a recorded window to the learner's minibatches, on the device.  P is
  * the record's cursor (xh_venv_record_pos), a row index is q = t N + e.  The
  * three calls are asynchronous on the context's stream; their pointer
@@ -929,6 +987,9 @@ typedef struct {
   double *kl_stats;          /* device [XH_VKL_COUNT] out or NULL; any loss kind */
 } xh_venv_loss;              /* xh_struct_size("xh_venv_loss") */
 int xh_venv_policy_loss(xh_venv *v, const xh_venv_loss *a);
+/* the same on the rows premasked by their legal words (above) */
+int xh_venv_policy_loss_masked(xh_venv *v, const xh_venv_loss *a,
+                               const uint32_t *legal_dev);
 /* kl_ppo_learner's beta rule (policy_gradient.h:76-80, 310-335) on the device:
  * one asynchronous single-thread launch on the context's stream.
  *   d = (float)(kl_stats_dev[XH_VKL_KL_SUM] / kl_stats_dev[XH_VKL_ROWS])

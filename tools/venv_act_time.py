@@ -7,13 +7,16 @@ achieved GB/s over the algorithmic bytes, at 64 bins, 2-D, with 32768 and
 
     python tools/venv_act_time.py                  # act and step
     python tools/venv_act_time.py --distrib --bins 128 --envs 32768
+    python tools/venv_act_time.py --mask --envs 32768   # + the masked arms
     python tools/venv_act_time.py --step-only --package-root build/prev_tree
                         # the parent commit's package, built in its own tree
 
 Bytes per env step: step 2 B D + 13 (bins read and written, item read and
 written, action, stream state read and written ... DESIGN.md §3.2); act adds
 the policy row and the two outputs, 4 B + 8; the record adds 13, and B D + 4
-with the states, and 4 B with the distributions.  Each figure is the mean over --launches launches, repeated
+with the states, and 4 B with the distributions; --mask repeats the act arms
+with invalid-action masking on (xh_venv_set_action_mask), which adds 4 W, W =
+max(1, B / 32), where there is a record.  Each figure is the mean over --launches launches, repeated
 --reps times: median [min .. max] of the repetitions.  For an A/B of two
 libraries run the script once per library, alternating, in one session."""
 import argparse
@@ -54,6 +57,8 @@ def main():
                     help="xh_venv_step alone (a library without xh_venv_act)")
     ap.add_argument("--distrib", action="store_true",
                     help="add the arm with the distribution record on")
+    ap.add_argument("--mask", action="store_true",
+                    help="repeat the act arms with the action mask on")
     ap.add_argument("--package-root", default=REPO,
                     help="import dependence_free_rl_amd from this tree (a "
                     "checkout of another commit with its library built)")
@@ -65,6 +70,8 @@ def main():
     B, D = a.bins, a.dims
     ctx = Context(device=0)
     rows = []
+    if a.mask and not hasattr(VecEnv, "set_action_mask"):
+        ap.error("--mask: this package has no VecEnv.set_action_mask")
     for N in a.envs:
         env = VecEnv(ctx, num_envs=N, bins=B, dims=D, rng_state=7,
                      policy_draws=2)
@@ -81,8 +88,15 @@ def main():
             if a.distrib:
                 cases += [("act+rec+dist", a.launches,
                            act_bytes + 13 + B * D + 4 + 4 * B)]
+            if a.mask:
+                W = max(1, B // 32)
+                cases += [(n + "+mask", r, nb + (4 * W if r else 0))
+                          for n, r, nb in cases[1:]]
         for name, record, nbytes in cases:
-            if name == "act+rec+dist":
+            if a.mask and name != "step":
+                env.set_record(0)  # the mask is switched at cursor 0
+                env.set_action_mask(name.endswith("+mask"))
+            if name.startswith("act+rec+dist"):
                 env.set_record(record, distrib=True)
             elif record is not None:
                 env.set_record(record)
@@ -101,7 +115,7 @@ def main():
                    "ms_min": min(per), "ms_max": max(per),
                    "gb_s": N * nbytes / med / 1e6}
             rows.append(row)
-            print("%-12s %8d envs  %.4f ms [%.4f .. %.4f]  %7.1f GB/s  (%d B "
+            print("%-17s %8d envs  %.4f ms [%.4f .. %.4f]  %7.1f GB/s  (%d B "
                   "per env step)" % (name, N, med, min(per), max(per),
                                      row["gb_s"], nbytes), flush=True)
         env.close()

@@ -6,17 +6,23 @@ loss, a shuffled minibatch gathered through an index list, with the value
 head, with and without probs_out and stats -- at 131,072 and 1,048,576 rows
 of 64 bins and of 128 bins.  --kl adds the KL-regulated loss on the same
 rows (each row's sampling distribution gathered through the index list), alone
-and with kl_stats, and kl_stats under the clipped loss.
+and with kl_stats, and kl_stats under the clipped loss.  --mask adds the
+masked launch (xh_venv_policy_loss_masked: each row's legal words gathered
+through the index list), plain and with probs_out and stats.
 
     python tools/venv_loss_time.py
     python tools/venv_loss_time.py --kl
+    python tools/venv_loss_time.py --mask --rows 32768
+    python tools/venv_loss_time.py --package-root build/prev_tree
+                        # the parent commit's package, built in its own tree
     python tools/venv_loss_time.py --rows 1048576 --bins 64 --json out.json
     python tools/venv_loss_time.py --torch     # the same loss in torch, alone
 
 Bytes by the kernel's model: per row 4 B read, 4 B written,
 4 B more with probs_out, and 28 gathered or scattered (the index, action,
 p_old, adv, target, values_new, dvalue); the KL arms gather 4 B more (the
-row's distribution).  Each figure is the mean over
+row's distribution), the masked arms 4 W more, W = max(1, B / 32) (the row's
+legal words).  Each figure is the mean over
 --launches launches, repeated --reps times: median [min .. max].
 
 --torch times the loss a caller would otherwise write on the device: gather,
@@ -91,6 +97,11 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--kl", action="store_true",
                     help="add the KL-regulated loss and kl_stats arms")
+    ap.add_argument("--mask", action="store_true",
+                    help="add the masked arms (xh_venv_policy_loss_masked)")
+    ap.add_argument("--package-root", default=REPO,
+                    help="import dependence_free_rl_amd from this tree (a "
+                    "checkout of another commit with its library built)")
     ap.add_argument("--torch", action="store_true",
                     help="time the eager torch form instead (own process)")
     ap.add_argument("--json", help="also write the result rows to this file")
@@ -101,7 +112,7 @@ def main():
             with open(a.json, "w") as f:
                 json.dump(rows_out, f, indent=1)
         return
-    sys.path.insert(0, REPO)
+    sys.path.insert(0, os.path.abspath(a.package_root))
 
     from dependence_free_rl_amd import Context, VecEnv, _lib
     lib, check = _lib.lib, _lib.check
@@ -142,7 +153,16 @@ def main():
                 put(blocks["z"] + 4 * off, zs[:min(chunk, n * B - off)])
             put(blocks["idx"], g.permutation(total)[:n].astype(np.int32))
             put(blocks["values"], g.standard_normal(n).astype(np.float32))
-            put(blocks["action"], g.integers(0, B, total).astype(np.int32))
+            action = g.integers(0, B, total).astype(np.int32)
+            put(blocks["action"], action)
+            if a.mask:  # about half the bins legal, the row's action among them
+                W = max(1, B // 32)
+                words = g.integers(0, 1 << min(B, 32), (total, W),
+                                   dtype=np.uint64).astype(np.uint32)
+                words[np.arange(total), action // 32] |= (
+                    np.uint32(1) << (action % 32).astype(np.uint32))
+                blocks["legal"] = dev(4 * total * W)
+                put(blocks["legal"], words)
             put(blocks["p_old"],
                 (g.random(total) * 0.5 + 0.01).astype(np.float32))
             put(blocks["adv"], g.standard_normal(total).astype(np.float32))
@@ -156,6 +176,10 @@ def main():
                 arms += [("venv_policy_loss kl", 0, 0),
                          ("venv_policy_loss kl +kl_stats", 0, 0),
                          ("venv_policy_loss clipped +kl_stats", 0, 0)]
+            if a.mask:
+                arms += [("venv_policy_loss masked", 0, 0),
+                         ("venv_policy_loss masked +probs +stats", 1, 1),
+                         ("venv_policy_loss masked run (no list)", 0, 0)]
             for name, probs, stats in arms:
                 v = _lib.VenvLoss()
                 v.policy, v.kind = blocks["z"], _lib.ACT_LOGITS
@@ -178,8 +202,14 @@ def main():
                     if "kl_stats" in name:
                         v.kl_stats = blocks["kl_stats"]
 
+                masked = "masked" in name
+
                 def launch():
-                    check(lib.xh_venv_policy_loss(env.h, C.byref(v)))
+                    if masked:
+                        check(lib.xh_venv_policy_loss_masked(
+                            env.h, C.byref(v), blocks["legal"]))
+                    else:
+                        check(lib.xh_venv_policy_loss(env.h, C.byref(v)))
                 for _ in range(a.warmup):
                     launch()
                 env.synchronize()
@@ -195,12 +225,13 @@ def main():
                 med = float(np.median(per))
                 nbytes = n * (8 * B + (4 * B if probs else 0) + 28
                               - (0 if v.rows_dev else 4)
-                              + (4 * B if gathers_q else 0))
+                              + (4 * B if gathers_q else 0)
+                              + (4 * max(1, B // 32) if masked else 0))
                 rows_out.append({"kernel": name, "rows": n, "bins": B,
                                  "bytes": nbytes, "ms": med,
                                  "ms_min": min(per), "ms_max": max(per),
                                  "tb_s": nbytes / med / 1e9})
-                print("%-34s %8d rows B=%-3d %.4f ms [%.4f .. %.4f]  %6.1f MB"
+                print("%-37s %8d rows B=%-3d %.4f ms [%.4f .. %.4f]  %6.1f MB"
                       "  %5.2f TB/s" % (name, n, B, med, min(per), max(per),
                                         nbytes / 1e6, nbytes / med / 1e9),
                       flush=True)

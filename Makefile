@@ -24,7 +24,8 @@ OBJS     := $(SRC)/policy_kernels.o $(SRC)/value_kernels.o \
             $(SRC)/stats_kernels.o $(SRC)/clip_kernels.o \
             $(SRC)/diag_kernels.o \
             $(SRC)/train_select.o $(SRC)/model_api.o $(SRC)/tensor_api.o \
-            $(SRC)/xylo_hip.o $(SRC)/digest_kernels.o $(SRC)/state_api.o
+            $(SRC)/xylo_hip.o $(SRC)/digest_kernels.o $(SRC)/state_api.o \
+            $(SRC)/venv_api.o
 # superseded train kernels (the config-3 / config-5
 # epoch's earlier forms), kept for A/B runs in the variant library only
 VARIANT_KERNELS := policy_split_kernels policy_split128_kernels \
@@ -107,6 +108,9 @@ $(SRC)/tensor_api.o: $(SRC)/tensor_api.cpp $(HDRS)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
 $(SRC)/state_api.o: $(SRC)/state_api.cpp $(HDRS)
+	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+
+$(SRC)/venv_api.o: $(SRC)/venv_api.cpp $(HDRS)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
 # the variant library: the product objects + the superseded train kernels,

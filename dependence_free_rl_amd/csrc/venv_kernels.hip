@@ -4,7 +4,7 @@
 // (bin_packing.h:53-70, get_item :76-81), bp::agent::game_over/get_reward
 // (:94-106), xylo::agent::step minus the policy's react (rl.h:325-349),
 // observation::to_vector (bin_packing.h:31-40); generalised to B bins and D
-// dims as the trainer's env (xylo_hip.cpp make_env).
+// dims as the trainer's env (xh_host.h make_env).
 //
 // Layout in HBM: bins int8 [N][B][D], items int8 [N][4], rng u32 [N] (one
 // minstd_rand0 state per env).  A lane owns one (env, bin) pair (two bins per

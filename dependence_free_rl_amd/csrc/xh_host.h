@@ -1,6 +1,9 @@
 // xh_host.h -- internal helpers of the C ABI's host runtime (xylo_hip.cpp,
-// model_api.cpp): the error slot behind xh_last_error, status macros, the
-// exception guard, stream-ordered copies and the context struct.
+// venv_api.cpp, model_api.cpp, tensor_api.cpp, state_api.cpp): the error slot
+// behind xh_last_error, status macros, the exception guard, stream-ordered
+// copies, zero-filled device allocations, pooled timing events, the context
+// struct with its release rule, and the env description both the trainer and
+// the venv start from.
 #ifndef XH_HOST_H_
 #define XH_HOST_H_
 
@@ -11,8 +14,10 @@
 #include <cstdio>
 #include <exception>
 #include <string>
+#include <vector>
 
 #include "../../include/xylo_hip.h"
+#include "xh_kernels.h"
 
 struct xh_ctx {
   int device = 0, rank = 0, world = 1;
@@ -61,6 +66,16 @@ inline int fail(int code, const char *fmt, ...) {
     if (s_ != XH_OK) return s_;  \
   } while (0)
 
+// Runs a cleanup after a failing call and keeps that call's message: the
+// cleanup's own ABI calls may overwrite the error slot.
+template <class F>
+int fail_after(int status, F &&cleanup) {
+  std::string keep = g_err;
+  cleanup();
+  g_err = std::move(keep);
+  return status;
+}
+
 // No exception may cross the ABI.
 template <class F>
 int guard(F &&f) {
@@ -93,6 +108,77 @@ inline hipError_t copy_to_device(void *dev, const void *host, size_t n,
 inline int copy_ok(hipError_t e) {
   return e == hipSuccess ? XH_OK
                          : fail(XH_ERR_HIP, "copy: %s", hipGetErrorString(e));
+}
+
+// A device allocation of `bytes`, zeroed on the context's stream `s`: a
+// null-stream hipMemset is not ordered before the non-blocking stream's next
+// copy / kernel (measured: the zero fill landing after the parameter upload,
+// intermittently).  *out is written on success only; `what` names the owner
+// in the message.
+inline int dev_zalloc(hipStream_t s, void **out, size_t bytes,
+                      const char *what) {
+  void *p = nullptr;
+  if (hipMalloc(&p, bytes) != hipSuccess)
+    return fail(XH_ERR_HIP, "%s: allocating %zu bytes", what, bytes);
+  if (hipMemsetAsync(p, 0, bytes, s) != hipSuccess) {
+    (void)hipFree(p);
+    return fail(XH_ERR_HIP, "%s: zero fill", what);
+  }
+  *out = p;
+  return XH_OK;
+}
+
+// Timing events come from their owner's pool (which gets them back when the
+// timing is reset), without the system-scope fence: they only time launches,
+// every host read of device memory synchronises the stream itself.
+inline hipError_t pooled_event(std::vector<hipEvent_t> &pool, hipEvent_t *e) {
+  if (!pool.empty()) {
+    *e = pool.back();
+    pool.pop_back();
+    return hipSuccess;
+  }
+  return hipEventCreateWithFlags(e, hipEventDisableSystemFence);
+}
+
+inline void ctx_free(xh_ctx *c) {
+  (void)hipSetDevice(c->device);
+  (void)hipStreamSynchronize(c->stream);
+  if (c->comm) ncclCommDestroy(c->comm);
+  (void)hipStreamDestroy(c->stream);
+  delete c;
+}
+
+// A destroyed trainer or venv gives up its reference (counted: it held one):
+// the last one frees a context that xh_ctx_destroy was already called on.
+inline void ctx_release(xh_ctx *c, bool counted) {
+  if (counted && --c->trainers == 0 && c->closing) ctx_free(c);
+}
+
+inline uint32_t mstd_pow(uint64_t k) {  // 16807^k mod (2^31-1)
+  uint64_t acc = 1, base = 16807;
+  while (k) {
+    if (k & 1) acc = acc * base % 2147483647ull;
+    base = base * base % 2147483647ull;
+    k >>= 1;
+  }
+  return (uint32_t)acc;
+}
+
+constexpr int kBinCapacity = 8;  // bin_packing.h:48, every dim
+
+// the bin-packing env of `bins` x `dims` (item sizes and their probability)
+inline xh::EnvDesc make_env(int bins, int dims) {
+  static const int ia[3][3] = {{4, 0, 0}, {4, 2, 0}, {4, 2, 2}};
+  static const int ib[3][3] = {{1, 0, 0}, {1, 2, 0}, {1, 2, 1}};
+  xh::EnvDesc env{};
+  env.B = bins;
+  env.D = dims;
+  for (int d = 0; d < 3; ++d) {
+    env.item_a[d] = ia[dims - 1][d];
+    env.item_b[d] = ib[dims - 1][d];
+  }
+  env.p_a = 0.4;
+  return env;
 }
 
 }  // namespace host

@@ -187,8 +187,6 @@ struct xh_trainer {
 namespace xh {
 namespace host {
 
-constexpr int kBinCapacity = 8;  // bin_packing.h:48, every dim
-
 // Every write of a net's parameters and every host write into the batch (or
 // into what the next rollout starts from) says so here, before it is issued:
 // what was derived from the old contents is stale -- the value net's W0

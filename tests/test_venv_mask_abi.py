@@ -5,6 +5,7 @@ exist; no GPU compute."""
 import ctypes as C
 import inspect
 import os
+import re
 
 from test_stats_abi import _header_enum
 
@@ -25,6 +26,15 @@ def test_header_declares_and_library_exports_the_calls():
     assert _lib.lib.xh_venv_legal_ptr.restype is C.c_void_p
     assert _lib.lib.xh_venv_record_legal_ptr.restype is C.c_void_p
     assert _lib.lib.xh_venv_record_legal_bytes.restype is C.c_size_t
+
+
+def test_the_library_exports_exactly_the_declared_calls():
+    """Every xh_* call the header declares is defined by some object of the
+    library, and nothing else is exported under that prefix."""
+    from dependence_free_rl_amd import _lib
+    out = os.popen("nm -D --defined-only %s" % _lib.LIB_PATH).read()
+    exported = sorted(set(re.findall(r" T (xh_[a-z0-9_]+)$", out, flags=re.M)))
+    assert exported == _lib.header_symbols()
 
 
 def test_null_arguments_are_status_codes():

@@ -34,6 +34,8 @@ from ._lib import (VLOSS_CLIPPED, VLOSS_COUNT, VLOSS_ENTROPY_SUM,  # noqa: F401
                    VLOSS_VERR_SUM)
 from ._lib import (VKL_COUNT, VKL_KL_SQSUM, VKL_KL_SUM,  # noqa: F401
                    VKL_ROWS)
+from ._lib import (VEXT_COUNT, VEXT_ENTROPY_SUM, VEXT_ROWS,  # noqa: F401
+                   VEXT_VCLIP_ROWS, VEXT_VLOSS_SUM)
 from .venv import VecEnv, legal_words, pack_legal, unpack_legal  # noqa: F401
 
 __all__ = ["Context", "Trainer", "POLICY", "VALUE", "init_policy", "init_value",

@@ -33,6 +33,9 @@ VOBS_STATE, VOBS_NEXT = 0, 1
  VLOSS_VERR_SQSUM, VLOSS_COUNT) = range(11)
 # the exact-KL sums of xh_venv_policy_loss's kl_stats (the XH_VKL_* enum)
 VKL_KL_SUM, VKL_ROWS, VKL_KL_SQSUM, VKL_COUNT = range(4)
+# the sums of xh_venv_policy_loss_ex's ext_stats (the XH_VEXT_* enum)
+(VEXT_ROWS, VEXT_ENTROPY_SUM, VEXT_VCLIP_ROWS, VEXT_VLOSS_SUM,
+ VEXT_COUNT) = range(5)
 COPY_H2D, COPY_D2H, COPY_D2D = 0, 1, 2
 (BUF_BINS, BUF_ITEMS, BUF_ACTION, BUF_POLD, BUF_DONE, BUF_RNG, BUF_V_STATE,
  BUF_V_TERM, BUF_TARGETS, BUF_ADV, BUF_VALUE_GRAD, BUF_POLICY_GRADS,
@@ -114,6 +117,15 @@ class VenvLoss(C.Structure):
         ("beta_dev", C.c_void_p), ("kl_stats", C.c_void_p)]
 
 
+class VenvLossExt(C.Structure):
+    """Mirror of xh_venv_loss_ext."""
+    _fields_ = [
+        ("masked", C.c_int), ("legal_dev", C.c_void_p),
+        ("ent_coef", C.c_float), ("ent_coef_dev", C.c_void_p),
+        ("v_old", C.c_void_p), ("vclip", C.c_float),
+        ("ext_stats", C.c_void_p)]
+
+
 def _load():
     if not os.path.exists(LIB_PATH):
         raise ImportError(
@@ -186,6 +198,8 @@ def _load():
         "xh_venv_record_legal_ptr": (vp, [vp]),
         "xh_venv_get_record_legal": (i, [vp, vp, sz]),
         "xh_venv_policy_loss_masked": (i, [vp, C.POINTER(VenvLoss), vp]),
+        "xh_venv_policy_loss_ex": (i, [vp, C.POINTER(VenvLoss),
+                                       C.POINTER(VenvLossExt)]),
         "xh_venv_kl_beta": (i, [vp, vp, C.c_float, vp, vp]),
         "xh_venv_record_obs": (i, [vp, i, vp, C.c_long, C.c_long, vp]),
         "xh_venv_record_ends": (i, [vp, vp, vp]),
@@ -262,7 +276,8 @@ tensor_copy = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                           C.c_size_t, C.c_int)(("xh_tensor_copy", lib))
 for _name, _mirror in (("xh_config", Config), ("xh_eval", Eval),
                        ("xh_layer", Layer), ("xh_venv_adv", VenvAdv),
-                       ("xh_venv_loss", VenvLoss)):
+                       ("xh_venv_loss", VenvLoss),
+                       ("xh_venv_loss_ext", VenvLossExt)):
     if lib.xh_struct_size(_name.encode()) != C.sizeof(_mirror):
         raise ImportError("ctypes mirror of %s is out of date (%d vs %d bytes)"
                           % (_name, C.sizeof(_mirror),

@@ -64,6 +64,9 @@ struct xh_venv {
   // ... and its kl_stats partials [kVenvLossMaxBlocks][XH_VKL_COUNT], at the
   // first call that asks for kl_stats
   double *kl_part = nullptr;
+  // ... and xh_venv_policy_loss_ex's ext_stats partials [kVenvLossMaxBlocks]
+  // [XH_VEXT_COUNT], at the first call that asks for ext_stats
+  double *ext_part = nullptr;
 
   template <class T>
   T *rec_as(int entry) const {
@@ -370,6 +373,29 @@ int loss_check_memory(const xh_venv_loss *p, int B, const loss_inputs &in) {
   return XH_OK;
 }
 
+// xh_venv_policy_loss_ex's own refusals
+int loss_check_ext(const xh_venv_loss *p, const xh_venv_loss_ext *x) {
+  if (x->legal_dev && !x->masked)
+    return fail(XH_ERR_INVALID, "venv policy loss: legal_dev without masked");
+  if (!x->ent_coef_dev &&
+      !(x->ent_coef >= 0.0f && std::isfinite(x->ent_coef)))
+    return fail(XH_ERR_INVALID, "venv policy loss: ent_coef %g",
+                (double)x->ent_coef);
+  if (x->v_old && !p->values_new)
+    return fail(XH_ERR_INVALID, "venv policy loss: v_old needs values_new "
+                "(the value head)");
+  if (x->v_old && !(x->vclip > 0.0f && std::isfinite(x->vclip)))
+    return fail(XH_ERR_INVALID, "venv policy loss: vclip %g",
+                (double)x->vclip);
+  return XH_OK;
+}
+
+// the extension is off: the call is xh_venv_policy_loss[_masked] itself
+bool loss_ext_off(const xh_venv_loss_ext *x) {
+  return !x || (x->ent_coef == 0.0f && !x->ent_coef_dev && !x->v_old &&
+                !x->ext_stats);
+}
+
 xh::VenvLossArgs loss_args(const xh_venv *v, const xh_venv_loss *p,
                            const loss_inputs &in) {
   xh::VenvLossArgs a{};
@@ -404,12 +430,21 @@ xh::VenvLossArgs loss_args(const xh_venv *v, const xh_venv_loss *p,
   return a;
 }
 
-// xh_venv_policy_loss (masked == false; legal_dev unused) and
-// xh_venv_policy_loss_masked (legal_dev, or with NULL the record's words)
+// xh_venv_policy_loss (masked == false; legal_dev unused),
+// xh_venv_policy_loss_masked (legal_dev, or with NULL the record's words) and
+// xh_venv_policy_loss_ex (x: its block, which gives masked and legal_dev; an
+// x that leaves the extension off changes nothing below its checks)
 int venv_policy_loss(xh_venv *v, const xh_venv_loss *p, bool masked,
-                     const uint32_t *legal_dev) {
+                     const uint32_t *legal_dev,
+                     const xh_venv_loss_ext *x = nullptr) {
   return venv_call(v, [&]() -> int {
     if (!p) return fail(XH_ERR_INVALID, "venv policy loss: null args");
+    if (x) {
+      CHK(loss_check_ext(p, x));
+      masked = x->masked != 0;
+      legal_dev = x->legal_dev;
+      if (loss_ext_off(x)) x = nullptr;
+    }
     loss_inputs in;
     CHK(loss_resolve_inputs(v, p, masked, legal_dev, &in));
     CHK(loss_resolve_total(v, p, &in));
@@ -427,7 +462,18 @@ int venv_policy_loss(xh_venv *v, const xh_venv_loss *p, bool masked,
     if (p->kl_stats && !v->kl_part)
       HIPCHK(hipMalloc((void **)&v->kl_part,
                        (size_t)xh::kVenvLossMaxBlocks * XH_VKL_COUNT * 8));
-    const xh::VenvLossArgs a = loss_args(v, p, in);
+    if (x && x->ext_stats && !v->ext_part)
+      HIPCHK(hipMalloc((void **)&v->ext_part,
+                       (size_t)xh::kVenvLossMaxBlocks * XH_VEXT_COUNT * 8));
+    xh::VenvLossArgs a = loss_args(v, p, in);
+    if (x) {
+      a.ext = 1;
+      a.ent_coef = x->ent_coef;
+      a.ent_coef_dev = x->ent_coef_dev;
+      a.v_old = x->v_old;
+      a.vclip = x->vclip;
+      a.ext_part = x->ext_stats ? v->ext_part : nullptr;
+    }
     CHK(venv_timed(v, [&] { return xh::launch_venv_policy_loss(a, s); }));
     hipError_t e = hipSuccess;
     if (p->stats)
@@ -437,6 +483,10 @@ int venv_policy_loss(xh_venv *v, const xh_venv_loss *p, bool masked,
     if (e == hipSuccess && p->kl_stats)
       e = xh::launch_venv_kl_reduce(v->kl_part, xh::venv_loss_grid(B, p->count),
                                     p->accumulate != 0, p->kl_stats, s);
+    if (e == hipSuccess && x && x->ext_stats)
+      e = xh::launch_venv_ext_reduce(v->ext_part,
+                                     xh::venv_loss_grid(B, p->count),
+                                     p->accumulate != 0, x->ext_stats, s);
     if (e != hipSuccess)
       return fail(XH_ERR_HIP, "venv policy loss: %s", hipGetErrorString(e));
     return XH_OK;
@@ -516,6 +566,7 @@ int xh_venv_destroy(xh_venv *v) {
     if (v->adv_part) (void)hipFree(v->adv_part);  // adv_stats, adv_end_part too
     if (v->loss_part) (void)hipFree(v->loss_part);
     if (v->kl_part) (void)hipFree(v->kl_part);
+    if (v->ext_part) (void)hipFree(v->ext_part);
     if (v->legal_buf) (void)hipFree(v->legal_buf);
     venv_free_record(v);
     xh_ctx *c = v->ctx;
@@ -929,6 +980,11 @@ int xh_venv_policy_loss(xh_venv *v, const xh_venv_loss *p) {
 int xh_venv_policy_loss_masked(xh_venv *v, const xh_venv_loss *p,
                                const uint32_t *legal_dev) {
   return venv_policy_loss(v, p, true, legal_dev);
+}
+
+int xh_venv_policy_loss_ex(xh_venv *v, const xh_venv_loss *p,
+                           const xh_venv_loss_ext *x) {
+  return venv_policy_loss(v, p, false, nullptr, x);
 }
 
 int xh_venv_kl_beta(xh_venv *v, const double *kl_stats_dev, float d_targ,

@@ -21,7 +21,8 @@
 // action, p_old, adv, target; + 8 with the value head's values_new / dvalue);
 // with XH_LOSS_KL_REGULATED or kl_stats another 4 B gathered (the row's
 // sampling distribution); with legal words (xh_venv_policy_loss_masked)
-// another 4 W, W = max(1, B / 32).
+// another 4 W, W = max(1, B / 32); with xh_venv_policy_loss_ex's value clip
+// another 4 (v_old) -- its entropy bonus moves no byte.
 #include "xh_device.h"
 #include "xh_diag.h"
 #include "xh_kernels.h"
@@ -67,7 +68,15 @@ constexpr bool kVLossOwner = XH_VLOSS_OWNER_STORES != 0;
 // does on the premasked rows, as venv_act_kernel's MASK does.  A row whose
 // words are all zero is left as it is.  The other instantiation holds none of
 // this.
-template <int B, bool STATS, int KL, bool MASK>
+// EXT (a.ext != 0, xh_venv_policy_loss_ex): the entropy bonus, PPO2's clipped
+// value loss and ext_stats, in the order include/xylo_hip.h gives.  The bonus
+// is f32 throughout -- logf, not a double logarithm: sixteen of those per lane
+// would move an HBM-bound kernel onto the fp64 pipe, as STATS' do -- on the
+// probabilities the row already holds in registers, its row sum S by the
+// softmax's own segment reduction.  Whether a call has the bonus (ent_on),
+// the value clip (a.v_old) or the sums (a.ext_part) is uniform, as
+// a.values_new is.  The other instantiation holds none of this.
+template <int B, bool STATS, int KL, bool MASK, bool EXT>
 __global__ __launch_bounds__(256) void venv_policy_loss_kernel(VenvLossArgs a) {
 #pragma clang fp contract(off)
   using S = VLossShape<B>;
@@ -84,6 +93,15 @@ __global__ __launch_bounds__(256) void venv_policy_loss_kernel(VenvLossArgs a) {
   for (int k = 0; k < XH_VKL_COUNT; ++k) kt[k] = kc[k] = 0.0;
   float beta = 0.0f;  // the regulation's weight, before this epoch's update
   if constexpr (KL > 0) beta = a.beta_dev ? *a.beta_dev : a.beta;
+  [[maybe_unused]] double xt[XH_VEXT_COUNT], xc[XH_VEXT_COUNT];
+  [[maybe_unused]] float entc = 0.0f;  // the bonus's weight
+  [[maybe_unused]] bool ent_on = false;
+  if constexpr (EXT) {
+#pragma unroll
+    for (int k = 0; k < XH_VEXT_COUNT; ++k) xt[k] = xc[k] = 0.0;
+    entc = a.ent_coef_dev ? *a.ent_coef_dev : a.ent_coef;
+    ent_on = a.ent_coef_dev || a.ent_coef > 0.0f;
+  }
 
   for (long tile = blockIdx.x; tile < a.tiles; tile += gridDim.x) {
     const long wbase = (tile * 4 + wib) * S::RPW;
@@ -96,6 +114,7 @@ __global__ __launch_bounds__(256) void venv_policy_loss_kernel(VenvLossArgs a) {
     long long qrow = 0;
     float q_old = 0.0f, A = 0.0f, tg = 0.0f, vn = 0.0f;
     [[maybe_unused]] uint32_t hw = 0u;  // the lane's legal half-word (MASK)
+    [[maybe_unused]] float vo = 0.0f;   // v_old[q] (EXT)
     if (in_range) {
       const vl_f4 *zp = reinterpret_cast<const vl_f4 *>(
           __builtin_assume_aligned(a.policy + (size_t)j * B + li * S::BPL, 16));
@@ -126,6 +145,8 @@ __global__ __launch_bounds__(256) void venv_policy_loss_kernel(VenvLossArgs a) {
         if (a.values_new) {
           tg = a.target[q];
           vn = a.values_new[j];
+          if constexpr (EXT)
+            if (a.v_old) vo = a.v_old[q];
         }
         ok = qok && ch >= 0 && ch < B;
         qrow = q;
@@ -226,11 +247,68 @@ __global__ __launch_bounds__(256) void venv_policy_loss_kernel(VenvLossArgs a) {
         }
       }
     }
+    [[maybe_unused]] float psum = 0.0f;  // S = sum_k p_k log p_k of the row
+    if constexpr (EXT) {
+      if (ent_on) {  // g_k += the gradient of -c H
+        float l[S::BPL];
+#pragma unroll
+        for (int k = 0; k < S::BPL; ++k) {
+          l[k] = logf(p[k]);
+          const float t = p[k] * l[k];
+          psum = p[k] > 0.0f ? psum + t : psum;  // the lane's, in bin order
+        }
+        psum = seg_sum<S::LPE>(psum);
+#pragma unroll
+        for (int k = 0; k < S::BPL; ++k) {
+          float e;
+          if (a.logits) {  // c p_k (log p_k + H)
+            const float d = l[k] - psum;
+            e = p[k] * d;
+            e = e * entc;
+          } else {  // c (log p_k + 1): the unconstrained partial
+            const float d = l[k] + 1.0f;
+            e = d * entc;
+          }
+          e = p[k] > 0.0f ? e : 0.0f;  // not 0 * -inf
+          g[k] = g[k] + e;
+        }
+      }
+    }
 #pragma unroll
     for (int k = 0; k < S::BPL; ++k) g[k] = skipped ? 0.0f : g[k] * a.scale;
     const float dv = vn - tg;  // square_loss_grad (nn.h:548-550)
-    if (valid && li == 0 && a.values_new)
-      a.dvalue[j] = skipped ? 0.0f : dv * a.value_scale;
+    [[maybe_unused]] float e2 = 0.0f;     // the clipped value's error
+    [[maybe_unused]] bool vzero = false;  // the clipped branch is the max
+    if constexpr (EXT) {
+      // the gradient of 0.5 max((v - tg)^2, (v_clip - tg)^2): the clipped
+      // branch does not depend on v.  The test is on hit, not on vc != vn:
+      // vo + (vn - vo) need not return vn
+      if (a.v_old) {
+        const float dl = vn - vo;
+        const bool hit = dl > a.vclip || dl < -a.vclip;
+        const float vc = vo + (dl > a.vclip ? a.vclip : -a.vclip);
+        e2 = vc - tg;
+        const float s1 = dv * dv, s2 = e2 * e2;
+        vzero = hit && s2 > s1;
+      }
+      if (valid && li == 0 && a.values_new)
+        a.dvalue[j] = skipped || vzero ? 0.0f : dv * a.value_scale;
+    } else {
+      if (valid && li == 0 && a.values_new)
+        a.dvalue[j] = skipped ? 0.0f : dv * a.value_scale;
+    }
+    if constexpr (EXT) {
+      if (a.ext_part && valid && !skipped && li == 0) {
+        xt[XH_VEXT_ROWS] += 1.0;
+        sum2(xt[XH_VEXT_ENTROPY_SUM], xc[XH_VEXT_ENTROPY_SUM],
+             (double)(0.0f - psum));
+        if (a.values_new) {
+          xt[XH_VEXT_VCLIP_ROWS] += vzero ? 1.0 : 0.0;
+          sum2(xt[XH_VEXT_VLOSS_SUM], xc[XH_VEXT_VLOSS_SUM],
+               vzero ? (double)e2 * (double)e2 : (double)dv * (double)dv);
+        }
+      }
+    }
 
     if (STATS && valid) {
       if (skipped) {
@@ -298,12 +376,20 @@ __global__ __launch_bounds__(256) void venv_policy_loss_kernel(VenvLossArgs a) {
     block_sums<XH_VKL_COUNT>(kt,
                              a.kl_part + (size_t)blockIdx.x * XH_VKL_COUNT);
   }
+  if constexpr (EXT) {
+    if (a.ext_part) {
+#pragma unroll
+      for (int k = 0; k < XH_VEXT_COUNT; ++k) xt[k] += xc[k];
+      block_sums<XH_VEXT_COUNT>(
+          xt, a.ext_part + (size_t)blockIdx.x * XH_VEXT_COUNT);
+    }
+  }
 }
 
 // stats[k] = (accumulate ? stats[k] : 0) + the column sums of part[nparts]
-// [S] (S = XH_VLOSS_COUNT for stats, XH_VKL_COUNT for kl_stats): lane l adds
-// partials l, l + 64, ... in order, then the shuffle tree (wave_column_sums)
-// -- the same bits for the same inputs.
+// [S] (S = XH_VLOSS_COUNT for stats, XH_VKL_COUNT for kl_stats, XH_VEXT_COUNT
+// for ext_stats): lane l adds partials l, l + 64, ... in order, then the
+// shuffle tree (wave_column_sums) -- the same bits for the same inputs.
 template <int S>
 __global__ __launch_bounds__(64) void venv_loss_reduce_kernel(
     const double *part, int nparts, int accumulate, double *stats) {
@@ -327,15 +413,23 @@ int venv_loss_grid(int B, long count) {
 }
 
 // the STATS instantiation where the call asks for stats (a.part), the MASK
-// one where it brings legal words (a.legal)
-template <int B, int KL, bool MASK>
-static void vloss_launch_m(const VenvLossArgs &a, dim3 grid, hipStream_t s) {
+// one where it brings legal words (a.legal), the EXT one where the extension
+// is on (a.ext)
+template <int B, int KL, bool MASK, bool EXT>
+static void vloss_launch_x(const VenvLossArgs &a, dim3 grid, hipStream_t s) {
   if (a.part)
-    hipLaunchKernelGGL((venv_policy_loss_kernel<B, true, KL, MASK>), grid,
+    hipLaunchKernelGGL((venv_policy_loss_kernel<B, true, KL, MASK, EXT>), grid,
                        dim3(256), 0, s, a);
   else
-    hipLaunchKernelGGL((venv_policy_loss_kernel<B, false, KL, MASK>), grid,
-                       dim3(256), 0, s, a);
+    hipLaunchKernelGGL((venv_policy_loss_kernel<B, false, KL, MASK, EXT>),
+                       grid, dim3(256), 0, s, a);
+}
+template <int B, int KL, bool MASK>
+static void vloss_launch_m(const VenvLossArgs &a, dim3 grid, hipStream_t s) {
+  if (a.ext)
+    vloss_launch_x<B, KL, MASK, true>(a, grid, s);
+  else
+    vloss_launch_x<B, KL, MASK, false>(a, grid, s);
 }
 template <int B, int KL>
 static void vloss_launch(const VenvLossArgs &a, dim3 grid, hipStream_t s) {
@@ -351,6 +445,9 @@ hipError_t launch_venv_policy_loss(VenvLossArgs a, hipStream_t s) {
   // the distribution is gathered for the KL-regulated loss and for kl_stats
   const int kl = a.kl_part ? 2 : a.loss == kLossKlRegulated ? 1 : 0;
   if (kl && !a.distrib) return hipErrorInvalidValue;
+  if (!a.ext && (a.ent_coef_dev || a.ent_coef != 0.0f || a.v_old || a.ext_part))
+    return hipErrorInvalidValue;  // the plain instantiation reads none of them
+  if (a.v_old && !a.values_new) return hipErrorInvalidValue;
 #define X(XB)                                                                \
   if (a.B == XB) {                                                           \
     const long tile = 4l * VLossShape<XB>::RPW;                              \
@@ -381,6 +478,14 @@ hipError_t launch_venv_kl_reduce(const double *part, int nparts, int accumulate,
                                  double *kl_stats, hipStream_t s) {
   hipLaunchKernelGGL(venv_loss_reduce_kernel<XH_VKL_COUNT>, dim3(1), dim3(64),
                      0, s, part, nparts, accumulate, kl_stats);
+  return hipGetLastError();
+}
+
+hipError_t launch_venv_ext_reduce(const double *part, int nparts,
+                                  int accumulate, double *ext_stats,
+                                  hipStream_t s) {
+  hipLaunchKernelGGL(venv_loss_reduce_kernel<XH_VEXT_COUNT>, dim3(1), dim3(64),
+                     0, s, part, nparts, accumulate, ext_stats);
   return hipGetLastError();
 }
 

@@ -457,6 +457,15 @@ struct VenvLossArgs {
   double *kl_part;            // [venv_loss_grid][XH_VKL_COUNT] or nullptr
   const uint32_t *legal;      // [total][W] the rows' legal words (a row of
                               // zeros: unmasked), or nullptr (no mask code)
+  // xh_venv_policy_loss_ex's extension; ext != 0 picks the instantiation
+  // that holds it, the other one reads none of these
+  int ext;
+  float ent_coef;             // the entropy bonus's weight (0: none) ...
+  const float *ent_coef_dev;  // ... or, where not null, one device float
+  const float *v_old;         // [total] the values at collection time, or
+                              // nullptr (no value clipping)
+  float vclip;                // with v_old
+  double *ext_part;           // [venv_loss_grid][XH_VEXT_COUNT] or nullptr
 };
 int venv_loss_grid(int B, long count);
 hipError_t launch_venv_policy_loss(VenvLossArgs a, hipStream_t s);
@@ -467,6 +476,10 @@ hipError_t launch_venv_loss_reduce(const double *part, int nparts,
 // the same for kl_part[nparts][XH_VKL_COUNT] -> kl_stats
 hipError_t launch_venv_kl_reduce(const double *part, int nparts, int accumulate,
                                  double *kl_stats, hipStream_t s);
+// the same for ext_part[nparts][XH_VEXT_COUNT] -> ext_stats
+hipError_t launch_venv_ext_reduce(const double *part, int nparts,
+                                  int accumulate, double *ext_stats,
+                                  hipStream_t s);
 
 // 1 when the kernels were built with the phase-ablation switches
 // (make diag, -DXH_DIAG_ABLATE=1), 0 in the product library.

@@ -1308,6 +1308,7 @@ size_t xh_struct_size(const char *name) {
   if (!std::strcmp(name, "xh_state_section")) return sizeof(xh_state_section);
   if (!std::strcmp(name, "xh_venv_adv")) return sizeof(xh_venv_adv);
   if (!std::strcmp(name, "xh_venv_loss")) return sizeof(xh_venv_loss);
+  if (!std::strcmp(name, "xh_venv_loss_ext")) return sizeof(xh_venv_loss_ext);
   return 0;
 }
 

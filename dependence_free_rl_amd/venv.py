@@ -19,7 +19,10 @@ one launch, recording the trajectory):
 Invalid-action masking is opt-in: env.set_action_mask(True) makes act() mask
 each row by the env's legal bins (record()["legal"] keeps the sets),
 policy_loss(..., legal=True) masks the minibatch the same way, and env.legal()
-returns the current states' sets.
+returns the current states' sets.  So are PPO's two usual extras:
+policy_loss(..., ent_coef=c) adds the entropy bonus's gradient to every row
+and policy_loss(..., v_old=..., vclip=...) clips the value loss
+(xh_venv_policy_loss_ex).
 
 Mirrors xylo::environment<A,S>::apply / view / reset (rl.h:163-170) with the
 id ranging over the batch, bp::environment (bin_packing.h:46-85) and
@@ -70,15 +73,16 @@ def unpack_legal(words, B):
     return bits.reshape(words.shape[:-1] + (B,)).astype(bool)
 
 
-def _beta_ptr(beta):
+def _beta_ptr(beta, name="beta"):
     """The device address in `beta`, or None where it is a value.  An integer
     is an address (as everywhere in this class), so a small one is a mistake:
-    beta = 1 is written 1.0."""
+    beta = 1 is written 1.0.  ent_coef follows the same rule (`name`)."""
     if isinstance(beta, bool) or not isinstance(beta, (int, np.integer)):
         return None
     if int(beta) < 4096:
-        raise ValueError("beta: a float, or an integer device pointer to one "
-                         "(got the integer %d; write it as a float)" % beta)
+        raise ValueError("%s: a float, or an integer device pointer to one "
+                         "(got the integer %d; write it as a float)"
+                         % (name, beta))
     return int(beta)
 
 
@@ -387,7 +391,8 @@ class VecEnv:
                     action=None, p_old=None, values=None, target=None,
                     value_scale=1.0, want_probs=False, want_stats=False,
                     accumulate=False, beta=0.0, distrib=None, want_kl=False,
-                    legal=None):
+                    legal=None, ent_coef=0.0, v_old=None, vclip=None,
+                    want_ext=False):
         """The loss head of the caller's network on a minibatch of the
         recorded window (xh_venv_policy_loss): from the network's output rows
         policy [count][B] ("logits": xh_venv_act's softmax first, or "probs")
@@ -415,7 +420,19 @@ class VecEnv:
         (set_action_mask with a record; action / p_old must be the record's
         too), or the caller's [total] sets indexed by q -- a host bool
         [total][B] or uint32 [total][W] array, or an integer device pointer to
-        the words.  A set with no bin leaves its row unmasked."""
+        the words.  A set with no bin leaves its row unmasked.
+
+        ent_coef, v_old, vclip, want_ext: all at their defaults, today's
+        call; otherwise xh_venv_policy_loss_ex.  ent_coef > 0 -- a float, or
+        an integer device pointer to one float, as beta is -- adds the
+        gradient of the entropy bonus -ent_coef * H(p) to every row before
+        scale (for "probs" the unconstrained partial: the caller's softmax
+        sits behind it).  v_old [total] (with values, target and vclip > 0)
+        makes the value head PPO2's clipped one: dvalue is 0 where the
+        clipped error is the larger.  want_ext adds "ext_stats" float64
+        [VEXT_COUNT]: the rows, the f32 entropies' sum, the rows whose dvalue
+        the clip zeroed and the sum of the larger squared errors; accumulate
+        applies to it as to "stats"."""
         B = self.B
         losses = {"clipped": _lib.LOSS_CLIPPED,
                   "log": _lib.LOSS_SOFTMAX_GRADIENT_LOG,
@@ -439,7 +456,7 @@ class VecEnv:
                                  "pointers only")
             count = np.asarray(policy).reshape(-1, B).shape[0]
         total = 0
-        for x in (adv, action, p_old, target):
+        for x in (adv, action, p_old, target, v_old):
             if host(x):
                 total = np.asarray(x).size
                 break
@@ -473,7 +490,7 @@ class VecEnv:
             a.probs_out = self._scratch("vl_probs", n * B * 4)
         if want_stats:
             a.stats = self._scratch("vl_stats", _lib.VLOSS_COUNT * 8)
-        if want_stats or want_kl:
+        if want_stats or want_kl or want_ext:
             a.accumulate = 1 if accumulate else 0
         if host(distrib):
             distrib = np.asarray(distrib, np.float32).reshape(-1, B)
@@ -484,10 +501,11 @@ class VecEnv:
             a.beta = float(beta)
         if want_kl:
             a.kl_stats = self._scratch("vl_kl", _lib.VKL_COUNT * 8)
-        if legal is None:
-            check(_lib.lib.xh_venv_policy_loss(self.h, C.byref(a)))
-        else:
-            lptr = None
+        ent_ptr = _beta_ptr(ent_coef, "ent_coef")
+        ext = (ent_ptr is not None or float(ent_coef) != 0.0 or
+               v_old is not None or vclip is not None or want_ext)
+        lptr = None
+        if legal is not None:
             if isinstance(legal, (int, np.integer)) and not isinstance(
                     legal, (bool, np.bool_)):
                 lptr = int(legal)
@@ -502,6 +520,23 @@ class VecEnv:
             elif not legal:
                 raise ValueError("policy_loss: legal is None, True, an array "
                                  "or a device pointer")
+        if ext:
+            x = _lib.VenvLossExt()
+            x.masked, x.legal_dev = 0 if legal is None else 1, lptr
+            if ent_ptr is not None:
+                x.ent_coef_dev = ent_ptr
+            else:
+                x.ent_coef = float(ent_coef)
+            x.v_old = flat("vl_vold", v_old, np.float32, total)
+            if vclip is not None:
+                x.vclip = float(vclip)
+            if want_ext:
+                x.ext_stats = self._scratch("vl_ext", _lib.VEXT_COUNT * 8)
+            check(_lib.lib.xh_venv_policy_loss_ex(self.h, C.byref(a),
+                                                  C.byref(x)))
+        elif legal is None:
+            check(_lib.lib.xh_venv_policy_loss(self.h, C.byref(a)))
+        else:
             check(_lib.lib.xh_venv_policy_loss_masked(self.h, C.byref(a),
                                                       lptr))
         out = {"grad": self._download(a.grad, np.float32, (count, B))}
@@ -515,6 +550,9 @@ class VecEnv:
         if want_kl:
             out["kl_stats"] = self._download(a.kl_stats, np.float64,
                                              (_lib.VKL_COUNT,))
+        if want_ext:
+            out["ext_stats"] = self._download(x.ext_stats, np.float64,
+                                              (_lib.VEXT_COUNT,))
         return out
 
     def kl_beta(self, kl_stats, d_targ, beta):

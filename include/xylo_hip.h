@@ -990,6 +990,88 @@ int xh_venv_policy_loss(xh_venv *v, const xh_venv_loss *a);
 /* the same on the rows premasked by their legal words (above) */
 int xh_venv_policy_loss_masked(xh_venv *v, const xh_venv_loss *a,
                                const uint32_t *legal_dev);
+/* xh_venv_policy_loss with the two terms every PPO learner adds to it: an
+ * entropy bonus, -c * H(pi), and PPO2's clipped value loss.  Neither is in
+ * the reference; both are opt-in through the extension block x, and xh_venv_
+ * loss and its enums are as they were.
+ *
+ * The extension is off where x == NULL, or where ent_coef == 0, ent_coef_dev
+ * == NULL, v_old == NULL and ext_stats == NULL.  The call is then
+ * xh_venv_policy_loss(v, a) -- with x->masked != 0, xh_venv_policy_loss_
+ * masked(v, a, x->legal_dev) -- itself: the same host path, the same kernel
+ * instantiation, the same bits in every output, stats and kl_stats included.
+ * Otherwise one launch of the instantiation that holds the extension (plus
+ * the one-wave launches of stats, kl_stats and ext_stats) does what the plain
+ * call does, premasked in the same way with masked, and in addition, every
+ * f32 operation rounded once, in this order (no fused multiply-add):
+ *
+ * The entropy bonus, where ent_coef_dev != NULL or ent_coef > 0, with c =
+ * *ent_coef_dev where given (read by the kernel: a schedule needs no host
+ * round trip), the field ent_coef otherwise; under all three loss kinds, on
+ * the row's p (XH_ACT_LOGITS: the softmax above):
+ *   l_k = logf(p_k) where p_k > 0; a bin with p_k == 0 contributes nothing
+ *   t_k = p_k * l_k
+ *   S   = the sums of 16 consecutive t_k in bin order (all 8 at 8 bins), those
+ *         sums added by the softmax's xor butterfly (partners 1, 2, 4); S =
+ *         sum_k p_k log p_k <= 0 and the row's f32 entropy is -S
+ *   XH_ACT_LOGITS: d = l_k - S; e = p_k * d; e = e * c   the gradient of
+ *     -c * H(softmax(z)), c p_k (log p_k + H); a row's e sum to 0 but for
+ *     rounding
+ *   XH_ACT_PROBS:  d = l_k + 1.0f; e = d * c   the unconstrained partial of
+ *     -c * H(p): the caller's own softmax sits behind it
+ *   g_k = g_k + e, after the loss's own row g is formed and before grad[j][k]
+ *     = g_k * scale.
+ * e is 0 at a bin with p_k == 0 by a select, not by 0 * -inf; a masked bin has
+ * p_k == 0 (its -inf logit gives exactly 0), so masked bins keep exact zero
+ * gradients, and a row whose legal set is one bin has e == 0 throughout.  The
+ * bonus does not touch p, so at epoch zero every ratio is still exactly 1.0f.
+ * A skipped row stays all zeros.
+ *
+ * The clipped value loss, where v_old != NULL (it needs values_new), with vn =
+ * values_new[j], tg = target[q], vo = v_old[q]:
+ *   dl  = vn - vo
+ *   hit = dl > vclip || dl < -vclip            |dl| == vclip is not a hit
+ *   vc  = vo + (dl > vclip ? vclip : -vclip)   used only where hit
+ *   e1  = vn - tg                              the plain call's dv
+ *   e2  = vc - tg;  s1 = e1 * e1;  s2 = e2 * e2
+ *   zero = hit && s2 > s1
+ *   dvalue[j] = zero ? 0.0f : e1 * value_scale
+ * the gradient of 0.5 * max((v - tg)^2, (v_clip - tg)^2), v_clip = vo + clamp(
+ * v - vo, -vclip, vclip): the clipped branch does not depend on v once the
+ * clip is hit.  The test is on hit, not on vc != vn -- vo + (vn - vo) need not
+ * return vn, and an unclipped row never loses its gradient to that rounding.
+ * A NaN compares false and propagates through e1; nothing is masked.
+ * XH_VLOSS_VERR_SUM / _SQSUM stay the sums of e1.
+ *
+ * ext_stats, where not NULL, receives the XH_VEXT_* sums over the rows that
+ * are neither skipped nor out of range: ROWS; ENTROPY_SUM = sum (double)(-S),
+ * the f32 entropy the gradient used (0 without the bonus); VCLIP_ROWS, the
+ * rows with zero; VLOSS_SUM = sum (zero ? (double)e2 * e2 : (double)e1 * e1),
+ * twice the value loss (0 without the value head).  In double in a fixed
+ * order, no floating-point atomics: the same inputs give the same bits.
+ * a->accumulate applies as it does to stats; the block partials (4096 x
+ * XH_VEXT_COUNT doubles) are allocated at the first call with ext_stats and
+ * freed with the venv.  The sums cover THIS venv's rows only.
+ *
+ * XH_ERR_INVALID: a null venv; with ent_coef_dev == NULL an ent_coef that is
+ * negative or not finite; v_old without a->values_new; v_old with a vclip that
+ * is not finite and positive; legal_dev with masked == 0; and whatever
+ * xh_venv_policy_loss[_masked] refuses, with its code. */
+enum { XH_VEXT_ROWS = 0, XH_VEXT_ENTROPY_SUM, XH_VEXT_VCLIP_ROWS,
+       XH_VEXT_VLOSS_SUM, XH_VEXT_COUNT };
+typedef struct {
+  int masked;                  /* != 0: premask as xh_venv_policy_loss_masked */
+  const uint32_t *legal_dev;   /* with masked: the caller's words, NULL: the record's */
+  float ent_coef;              /* >= 0, finite; the bonus's weight ...        */
+  const float *ent_coef_dev;   /* ... or, where not NULL, one device float read
+                                  by the kernel (a schedule with no host trip) */
+  const float *v_old;          /* [total] indexed by q, the values at collection
+                                  time; NULL: no value clipping                */
+  float vclip;                 /* > 0, finite, with v_old                      */
+  double *ext_stats;           /* device [XH_VEXT_COUNT] out or NULL           */
+} xh_venv_loss_ext;            /* xh_struct_size("xh_venv_loss_ext") */
+int xh_venv_policy_loss_ex(xh_venv *v, const xh_venv_loss *a,
+                           const xh_venv_loss_ext *x);
 /* kl_ppo_learner's beta rule (policy_gradient.h:76-80, 310-335) on the device:
  * one asynchronous single-thread launch on the context's stream.
  *   d = (float)(kl_stats_dev[XH_VKL_KL_SUM] / kl_stats_dev[XH_VKL_ROWS])

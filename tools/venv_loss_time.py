@@ -8,11 +8,15 @@ of 64 bins and of 128 bins.  --kl adds the KL-regulated loss on the same
 rows (each row's sampling distribution gathered through the index list), alone
 and with kl_stats, and kl_stats under the clipped loss.  --mask adds the
 masked launch (xh_venv_policy_loss_masked: each row's legal words gathered
-through the index list), plain and with probs_out and stats.
+through the index list), plain and with probs_out and stats.  --ent adds
+xh_venv_policy_loss_ex's arms: the entropy bonus alone, with the clipped value
+loss (v_old gathered through the index list) and with ext_stats, and
+ext_stats alone (the same instantiation, no logarithm).
 
     python tools/venv_loss_time.py
     python tools/venv_loss_time.py --kl
     python tools/venv_loss_time.py --mask --rows 32768
+    python tools/venv_loss_time.py --ent
     python tools/venv_loss_time.py --package-root build/prev_tree
                         # the parent commit's package, built in its own tree
     python tools/venv_loss_time.py --rows 1048576 --bins 64 --json out.json
@@ -22,7 +26,7 @@ Bytes by the kernel's model: per row 4 B read, 4 B written,
 4 B more with probs_out, and 28 gathered or scattered (the index, action,
 p_old, adv, target, values_new, dvalue); the KL arms gather 4 B more (the
 row's distribution), the masked arms 4 W more, W = max(1, B / 32) (the row's
-legal words).  Each figure is the mean over
+legal words), the value clip 4 more (v_old), the bonus none.  Each figure is the mean over
 --launches launches, repeated --reps times: median [min .. max].
 
 --torch times the loss a caller would otherwise write on the device: gather,
@@ -99,6 +103,9 @@ def main():
                     help="add the KL-regulated loss and kl_stats arms")
     ap.add_argument("--mask", action="store_true",
                     help="add the masked arms (xh_venv_policy_loss_masked)")
+    ap.add_argument("--ent", action="store_true",
+                    help="add the entropy-bonus / value-clip arms "
+                    "(xh_venv_policy_loss_ex)")
     ap.add_argument("--package-root", default=REPO,
                     help="import dependence_free_rl_amd from this tree (a "
                     "checkout of another commit with its library built)")
@@ -163,6 +170,11 @@ def main():
                     np.uint32(1) << (action % 32).astype(np.uint32))
                 blocks["legal"] = dev(4 * total * W)
                 put(blocks["legal"], words)
+            if a.ent:
+                blocks["v_old"] = dev(4 * total)
+                blocks["ext_stats"] = dev(8 * _lib.VEXT_COUNT)
+                put(blocks["v_old"],
+                    g.standard_normal(total).astype(np.float32))
             put(blocks["p_old"],
                 (g.random(total) * 0.5 + 0.01).astype(np.float32))
             put(blocks["adv"], g.standard_normal(total).astype(np.float32))
@@ -180,6 +192,12 @@ def main():
                 arms += [("venv_policy_loss masked", 0, 0),
                          ("venv_policy_loss masked +probs +stats", 1, 1),
                          ("venv_policy_loss masked run (no list)", 0, 0)]
+            if a.ent:
+                arms += [("venv_policy_loss ent", 0, 0),
+                         ("venv_policy_loss ent +vclip", 0, 0),
+                         ("venv_policy_loss ent +ext_stats", 0, 0),
+                         # the same instantiation without the logarithms
+                         ("venv_policy_loss ext_stats alone", 0, 0)]
             for name, probs, stats in arms:
                 v = _lib.VenvLoss()
                 v.policy, v.kind = blocks["z"], _lib.ACT_LOGITS
@@ -203,9 +221,20 @@ def main():
                         v.kl_stats = blocks["kl_stats"]
 
                 masked = "masked" in name
+                x = None
+                if " ent" in name or "ext_stats" in name:
+                    x = _lib.VenvLossExt()
+                    x.ent_coef = 0.01 if " ent" in name else 0.0
+                    if "vclip" in name:
+                        x.v_old, x.vclip = blocks["v_old"], 0.2
+                    if "ext_stats" in name:
+                        x.ext_stats = blocks["ext_stats"]
 
                 def launch():
-                    if masked:
+                    if x is not None:
+                        check(lib.xh_venv_policy_loss_ex(env.h, C.byref(v),
+                                                         C.byref(x)))
+                    elif masked:
                         check(lib.xh_venv_policy_loss_masked(
                             env.h, C.byref(v), blocks["legal"]))
                     else:
@@ -226,7 +255,8 @@ def main():
                 nbytes = n * (8 * B + (4 * B if probs else 0) + 28
                               - (0 if v.rows_dev else 4)
                               + (4 * B if gathers_q else 0)
-                              + (4 * max(1, B // 32) if masked else 0))
+                              + (4 * max(1, B // 32) if masked else 0)
+                              + (4 if "vclip" in name else 0))
                 rows_out.append({"kernel": name, "rows": n, "bins": B,
                                  "bytes": nbytes, "ms": med,
                                  "ms_min": min(per), "ms_max": max(per),

@@ -13,7 +13,8 @@ OBJS     := $(SRC)/policy_kernels.o $(SRC)/value_kernels.o \
             $(SRC)/env_kernels.o $(SRC)/kl_kernels.o \
             $(SRC)/heuristic_kernels.o $(SRC)/dense_kernels.o \
             $(SRC)/pg_kernels.o $(SRC)/venv_kernels.o $(SRC)/venv_learn_kernels.o \
-            $(SRC)/venv_loss_kernels.o $(SRC)/value_net_kernels.o \
+            $(SRC)/venv_loss_kernels.o $(SRC)/venv_episode_kernels.o \
+            $(SRC)/value_net_kernels.o \
             $(SRC)/policy_spec8_kernels.o $(SRC)/policy_spec8_kl_kernels.o \
             $(SRC)/policy_spec8_e0_kernels.o \
             $(SRC)/policy_spec4_kernels.o \

@@ -36,6 +36,11 @@ from ._lib import (VKL_COUNT, VKL_KL_SQSUM, VKL_KL_SUM,  # noqa: F401
                    VKL_ROWS)
 from ._lib import (VEXT_COUNT, VEXT_ENTROPY_SUM, VEXT_ROWS,  # noqa: F401
                    VEXT_VCLIP_ROWS, VEXT_VLOSS_SUM)
+from ._lib import (VEP_CALLS, VEP_COUNT, VEP_ENVS_FINISHED,  # noqa: F401
+                   VEP_EPISODES, VEP_FIRST_LEN_SQSUM, VEP_FIRST_LEN_SUM,
+                   VEP_LEN_MAX, VEP_LEN_MIN, VEP_LEN_SQSUM, VEP_LEN_SUM,
+                   VEP_ROW, VEP_RUNNING_MAX, VEP_RUNNING_SUM, VEPS_COUNT,
+                   VEPS_FIRST, VEPS_RUNNING)
 from .venv import VecEnv, legal_words, pack_legal, unpack_legal  # noqa: F401
 
 __all__ = ["Context", "Trainer", "POLICY", "VALUE", "init_policy", "init_value",

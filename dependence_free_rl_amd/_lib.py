@@ -36,6 +36,12 @@ VKL_KL_SUM, VKL_ROWS, VKL_KL_SQSUM, VKL_COUNT = range(4)
 # the sums of xh_venv_policy_loss_ex's ext_stats (the XH_VEXT_* enum)
 (VEXT_ROWS, VEXT_ENTROPY_SUM, VEXT_VCLIP_ROWS, VEXT_VLOSS_SUM,
  VEXT_COUNT) = range(5)
+# one row of the VecEnv's episode statistics (the XH_VEP_* enum;
+# xh_venv_set_episode_stats) and its per-env state arrays (XH_VEPS_*)
+(VEP_ROW, VEP_CALLS, VEP_EPISODES, VEP_LEN_SUM, VEP_LEN_SQSUM, VEP_LEN_MIN,
+ VEP_LEN_MAX, VEP_ENVS_FINISHED, VEP_FIRST_LEN_SUM, VEP_FIRST_LEN_SQSUM,
+ VEP_RUNNING_SUM, VEP_RUNNING_MAX, VEP_COUNT) = range(13)
+VEPS_RUNNING, VEPS_FIRST, VEPS_COUNT = range(3)
 COPY_H2D, COPY_D2H, COPY_D2D = 0, 1, 2
 (BUF_BINS, BUF_ITEMS, BUF_ACTION, BUF_POLD, BUF_DONE, BUF_RNG, BUF_V_STATE,
  BUF_V_TERM, BUF_TARGETS, BUF_ADV, BUF_VALUE_GRAD, BUF_POLICY_GRADS,
@@ -212,6 +218,14 @@ def _load():
         "xh_venv_set_timing": (i, [vp, i]),
         "xh_venv_kernel_time": (i, [vp, C.POINTER(C.c_double),
                                     C.POINTER(C.c_long)]),
+        "xh_venv_set_episode_stats": (i, [vp, i]),
+        "xh_venv_episode_row": (i, [vp]),
+        "xh_venv_episode_count": (i, [vp, C.POINTER(C.c_long)]),
+        "xh_venv_get_episode_rows": (i, [vp, C.c_long, i, vp]),
+        "xh_venv_episode_bytes": (sz, [vp, i]),
+        "xh_venv_episode_ptr": (vp, [vp, i]),
+        "xh_venv_episode_get": (i, [vp, i, vp, sz]),
+        "xh_venv_episode_set": (i, [vp, i, vp, sz]),
         "xh_model_eval": (i, [vp, vp, i, vp, sz, vp, i, i, vp, sz,
                               C.POINTER(C.c_int)]),
         "xh_model_forward": (i, [vp, vp, i, vp, sz, vp, i, i, vp, sz,
@@ -290,6 +304,10 @@ if lib.xh_struct_size(b"xh_upd_row") != UPD_COUNT * 8:
     raise ImportError("UPD_* indices are out of date (%d entries, the library "
                       "has %d)" % (UPD_COUNT,
                                    lib.xh_struct_size(b"xh_upd_row") // 8))
+if lib.xh_struct_size(b"xh_vep_row") != VEP_COUNT * 8:
+    raise ImportError("VEP_* indices are out of date (%d entries, the library "
+                      "has %d)" % (VEP_COUNT,
+                                   lib.xh_struct_size(b"xh_vep_row") // 8))
 if lib.xh_struct_size(b"xh_state_header") != STATE_HEADER_BYTES:
     raise ImportError("the state blob's header has %d bytes in the library, %d "
                       "here" % (lib.xh_struct_size(b"xh_state_header"),

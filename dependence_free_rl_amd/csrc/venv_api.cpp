@@ -4,10 +4,12 @@
 // the trajectory record with its optional distributions and legal words, the
 // learner's side of a recorded window (record_obs / record_ends / advantages,
 // venv_learn_kernels.hip) and the loss head (policy_loss / kl_beta,
-// venv_loss_kernels.hip).  A venv holds a reference on its context and never
-// touches a trainer.
+// venv_loss_kernels.hip) and the opt-in episode statistics (set_episode_stats /
+// episode_row, venv_episode_kernels.hip).  A venv holds a reference on its
+// context and never touches a trainer.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -67,6 +69,18 @@ struct xh_venv {
   // ... and xh_venv_policy_loss_ex's ext_stats partials [kVenvLossMaxBlocks]
   // [XH_VEXT_COUNT], at the first call that asks for ext_stats
   double *ext_part = nullptr;
+  // xh_venv_set_episode_stats (opt-in; everything null / 0 while off): the
+  // per-env blocks the step / act / apply launches count into, the row
+  // kernel's workgroup partials, and the device ring of XH_VEP_COUNT doubles
+  // per row; `rows` counts the rows taken, `calls` the launches since the
+  // last one
+  struct episode_stats {
+    int history = 0;
+    long rows = 0, calls = 0;
+    int32_t *state[XH_VEPS_COUNT] = {};  // XH_VEPS_RUNNING, XH_VEPS_FIRST
+    xh::VenvEpAcc *acc = nullptr;
+    double *psum = nullptr, *pext = nullptr, *ring = nullptr;
+  } ep;
 
   template <class T>
   T *rec_as(int entry) const {
@@ -86,6 +100,9 @@ struct xh_venv {
     a.err = err;
     a.skip_mul = skip_mul;
     a.jump_mul = jump_mul;
+    a.ep_running = ep.state[XH_VEPS_RUNNING];
+    a.ep_first = ep.state[XH_VEPS_FIRST];
+    a.ep_acc = ep.acc;
     return a;
   }
 };
@@ -242,7 +259,9 @@ int venv_launch(xh_venv *v, int op, int mode, bool use_mask, bool obs) {
   a.obs = obs ? (float *)v->buf[XH_VENV_OBS] : nullptr;
   if (op == xh::kVenvObserve) a.obs = (float *)v->buf[XH_VENV_OBS];
   if (mode == 0) a.reward = nullptr;
-  return venv_timed(v, [&] { return xh::launch_venv(a, op, v->ctx->stream); });
+  CHK(venv_timed(v, [&] { return xh::launch_venv(a, op, v->ctx->stream); }));
+  if (op == xh::kVenvStep && v->ep.history) ++v->ep.calls;
+  return XH_OK;
 }
 
 // the recorded pairs back into the pool (the stream is synchronised first)
@@ -252,6 +271,37 @@ void venv_drop_events(xh_venv *v) {
     v->event_pool.push_back(ev.second);
   }
   v->events.clear();
+}
+
+// ---- episode statistics ----
+constexpr int kMaxEpisodeRows = 1 << 20;  // the trainer's bound: 100 MB
+
+// the stream must be idle
+void venv_free_episode_stats(xh_venv *v) {
+  auto &ep = v->ep;
+  for (int32_t *p : ep.state)
+    if (p) (void)hipFree(p);
+  if (ep.acc) (void)hipFree(ep.acc);
+  if (ep.psum) (void)hipFree(ep.psum);
+  if (ep.pext) (void)hipFree(ep.pext);
+  if (ep.ring) (void)hipFree(ep.ring);
+  ep = xh_venv::episode_stats{};
+}
+
+bool veps_which(int which) { return which >= 0 && which < XH_VEPS_COUNT; }
+
+// xh_venv_episode_get / _set: statistics are on, the array exists and `bytes`
+// is its size
+int venv_check_episode_array(const xh_venv *v, int which, const void *host,
+                             size_t bytes, const char *what) {
+  if (!v || !host) return fail(XH_ERR_INVALID, "null arg");
+  if (!v->ep.history)
+    return fail(XH_ERR_STATE, "%s: episode statistics are off "
+                "(xh_venv_set_episode_stats)", what);
+  if (!veps_which(which) || bytes != (size_t)v->N * 4)
+    return fail(XH_ERR_INVALID, "%s %d: %zu bytes, expected %zu", what, which,
+                bytes, xh_venv_episode_bytes(v, which));
+  return XH_OK;
 }
 
 // ---- xh_venv_policy_loss, in the order its refusals are tested ----
@@ -568,6 +618,7 @@ int xh_venv_destroy(xh_venv *v) {
     if (v->kl_part) (void)hipFree(v->kl_part);
     if (v->ext_part) (void)hipFree(v->ext_part);
     if (v->legal_buf) (void)hipFree(v->legal_buf);
+    venv_free_episode_stats(v);
     venv_free_record(v);
     xh_ctx *c = v->ctx;
     const bool counted = v->counted;
@@ -619,6 +670,10 @@ int xh_venv_set(xh_venv *v, int which, const void *host, size_t bytes) {
     HIPCHK(hipSetDevice(v->ctx->device));
     if (const int st = venv_ensure(v, which)) return st;
     HIPCHK(copy_to_device(v->buf[which], host, bytes, v->ctx->stream));
+    // new bins are new episodes: every running length restarts
+    if (which == XH_VENV_BINS && v->ep.history)
+      HIPCHK(hipMemsetAsync(v->ep.state[XH_VEPS_RUNNING], 0, (size_t)v->N * 4,
+                            v->ctx->stream));
     HIPCHK(hipStreamSynchronize(v->ctx->stream));
     return XH_OK;
   });
@@ -694,6 +749,7 @@ int xh_venv_act(xh_venv *v, const float *policy_dev, int kind, int mode,
     const int st = venv_timed(
         v, [&] { return xh::launch_venv_act(a, v->ctx->stream); });
     if (st == XH_OK && v->rec_steps > 0) ++v->rec_pos;
+    if (st == XH_OK && v->ep.history) ++v->ep.calls;
     return st;
   });
 }
@@ -1030,6 +1086,143 @@ int xh_venv_kernel_time(xh_venv *v, double *ms, long *launches) {
     }
     *ms = total;
     *launches = (long)v->events.size();
+    return XH_OK;
+  });
+}
+
+// ---- episode statistics (venv_episode_kernels.hip) ----
+int xh_venv_set_episode_stats(xh_venv *v, int history_rows) {
+  return venv_call(v, [&]() -> int {
+    if (history_rows < 0 || history_rows > kMaxEpisodeRows)
+      return fail(XH_ERR_INVALID, "venv episode stats: history_rows %d not in "
+                  "[0, %d]", history_rows, kMaxEpisodeRows);
+    HIPCHK(hipSetDevice(v->ctx->device));
+    hipStream_t s = v->ctx->stream;
+    HIPCHK(hipStreamSynchronize(s));
+    venv_free_episode_stats(v);
+    if (history_rows == 0) return XH_OK;
+    auto &ep = v->ep;
+    const size_t N = (size_t)v->N, grid = (size_t)xh::venv_ep_grid(v->N);
+    const size_t ring = (size_t)history_rows * XH_VEP_COUNT * 8;
+    hipError_t e = hipSuccess;
+    for (int32_t *&p : ep.state)
+      if (e == hipSuccess) e = hipMalloc((void **)&p, N * 4);
+    if (e == hipSuccess)
+      e = hipMalloc((void **)&ep.acc, N * sizeof(xh::VenvEpAcc));
+    if (e == hipSuccess)
+      e = hipMalloc((void **)&ep.psum, grid * xh::kVepSums * 8);
+    if (e == hipSuccess)
+      e = hipMalloc((void **)&ep.pext, grid * xh::kVepExts * 8);
+    if (e == hipSuccess) e = hipMalloc((void **)&ep.ring, ring);
+    // unwritten rows read as NaN (all-ones bytes)
+    if (e == hipSuccess) e = hipMemsetAsync(ep.ring, 0xFF, ring, s);
+    if (e == hipSuccess)
+      e = xh::launch_venv_ep_init(v->N, ep.state[XH_VEPS_RUNNING],
+                                  ep.state[XH_VEPS_FIRST], ep.acc, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) {
+      venv_free_episode_stats(v);
+      return fail(XH_ERR_HIP, "venv episode stats(%d): %s", history_rows,
+                  hipGetErrorString(e));
+    }
+    ep.history = history_rows;
+    return XH_OK;
+  });
+}
+
+int xh_venv_episode_row(xh_venv *v) {
+  return venv_call(v, [&]() -> int {
+    auto &ep = v->ep;
+    if (!ep.history)
+      return fail(XH_ERR_STATE, "venv episode row: episode statistics are off "
+                  "(xh_venv_set_episode_stats)");
+    HIPCHK(hipSetDevice(v->ctx->device));
+    double *row = ep.ring + (size_t)(ep.rows % ep.history) * XH_VEP_COUNT;
+    CHK(venv_timed(v, [&] {
+      return xh::launch_venv_ep_row(v->N, ep.state[XH_VEPS_RUNNING],
+                                    ep.state[XH_VEPS_FIRST], ep.acc, ep.psum,
+                                    ep.pext, (double)ep.rows, (double)ep.calls,
+                                    row, v->ctx->stream);
+    }));
+    ++ep.rows;
+    ep.calls = 0;
+    return XH_OK;
+  });
+}
+
+int xh_venv_episode_count(xh_venv *v, long *total_rows) {
+  return guard([&]() -> int {
+    if (!v || !total_rows) return fail(XH_ERR_INVALID, "null arg");
+    if (!v->ep.history)
+      return fail(XH_ERR_STATE, "venv episode count: episode statistics are "
+                  "off (xh_venv_set_episode_stats)");
+    *total_rows = v->ep.rows;
+    return XH_OK;
+  });
+}
+
+int xh_venv_get_episode_rows(xh_venv *v, long first, int count, double *out) {
+  return guard([&]() -> int {
+    if (!v || (count > 0 && !out)) return fail(XH_ERR_INVALID, "null arg");
+    const auto &ep = v->ep;
+    if (!ep.history)
+      return fail(XH_ERR_STATE, "venv episode rows: episode statistics are off "
+                  "(xh_venv_set_episode_stats)");
+    if (first < 0 || count < 0 || first > ep.rows - count)
+      return fail(XH_ERR_INVALID, "venv episode rows: %d rows from row %ld, "
+                  "%ld written", count, first, ep.rows);
+    if (first < ep.rows - ep.history)
+      return fail(XH_ERR_INVALID, "venv episode rows: row %ld is overwritten "
+                  "(the ring holds rows %ld .. %ld)", first,
+                  ep.rows - ep.history, ep.rows - 1);
+    HIPCHK(hipSetDevice(v->ctx->device));
+    hipStream_t s = v->ctx->stream;
+    HIPCHK(hipStreamSynchronize(s));
+    // at most two runs of the ring
+    const long at = first % ep.history;
+    const long n1 = std::min<long>(count, ep.history - at);
+    const size_t rowb = (size_t)XH_VEP_COUNT * 8;
+    if (n1 > 0)
+      HIPCHK(copy_to_host(out, ep.ring + (size_t)at * XH_VEP_COUNT,
+                          (size_t)n1 * rowb, s));
+    if (count > n1)
+      HIPCHK(copy_to_host(out + (size_t)n1 * XH_VEP_COUNT, ep.ring,
+                          (size_t)(count - n1) * rowb, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return XH_OK;
+  });
+}
+
+size_t xh_venv_episode_bytes(const xh_venv *v, int which) {
+  return v && v->ep.history && veps_which(which) ? (size_t)v->N * 4 : 0;
+}
+
+void *xh_venv_episode_ptr(xh_venv *v, int which) {
+  return v && veps_which(which) ? v->ep.state[which] : nullptr;
+}
+
+int xh_venv_episode_get(xh_venv *v, int which, void *host, size_t bytes) {
+  return guard([&]() -> int {
+    CHK(venv_check_episode_array(v, which, host, bytes, "venv episode get"));
+    HIPCHK(hipSetDevice(v->ctx->device));
+    HIPCHK(copy_to_host(host, v->ep.state[which], bytes, v->ctx->stream));
+    HIPCHK(hipStreamSynchronize(v->ctx->stream));
+    return XH_OK;
+  });
+}
+
+int xh_venv_episode_set(xh_venv *v, int which, const void *host,
+                        size_t bytes) {
+  return guard([&]() -> int {
+    CHK(venv_check_episode_array(v, which, host, bytes, "venv episode set"));
+    const int32_t *a = static_cast<const int32_t *>(host);
+    for (int i = 0; i < v->N; ++i)
+      if (a[i] < (which == XH_VEPS_FIRST ? -1 : 0))
+        return fail(XH_ERR_INVALID, "venv episode set %d: %d at env %d", which,
+                    a[i], i);
+    HIPCHK(hipSetDevice(v->ctx->device));
+    HIPCHK(copy_to_device(v->ep.state[which], host, bytes, v->ctx->stream));
+    HIPCHK(hipStreamSynchronize(v->ctx->stream));
     return XH_OK;
   });
 }

@@ -11,7 +11,8 @@
 // lane at B = 128), so a wave covers 64 / B envs with fully coalesced int8
 // row loads; the env's verdicts (game over = any bin negative) are segment
 // ballots and the item / RNG / reward record is written by the env's bin-0
-// lane.  HBM-bound: 2 * B * D + 4 + 4 + 4 + 1 bytes per env step.
+// lane.  HBM-bound: 2 * B * D + 4 + 4 + 4 + 1 bytes per env step (+ 8 with
+// episode statistics on: the env's running length, venv_ep_count).
 // venv_act_kernel (xh_venv_act) picks the action from the caller's policy
 // row first -- react's sampling -- and writes the trajectory record.
 #include "xh_device.h"
@@ -94,7 +95,37 @@ __device__ __forceinline__ int xcd_block() {
   return (G & 7) == 0 ? (b & 7) * (G >> 3) + (b >> 3) : b;
 }
 
-template <int B, int D>
+// Episode statistics (a.ep_running, xh_venv_set_episode_stats; null while
+// off): EP, an instantiation of its own as MASK is -- measured as a nullable
+// pointer tested in the one kernel, the act launch without statistics was 1 to
+// 2% slower than the parent's at 1M envs; the other
+// instantiation holds none of this.  The env's running length is loaded with
+// the kernel's other loads and stored with the record by the env's bin-0
+// lane, the record's only writer: 8 bytes per env and step, no atomics.
+// venv_ep_count is that lane's store for a live step: len = the length with
+// this step; where the step ended the episode, len goes into the env's window
+// accumulators (and into first_len if it is the env's first) and the count
+// restarts.  The accumulators are touched by such steps alone.
+__device__ __forceinline__ void venv_ep_count(const VenvArgs &a, int env,
+                                              int run, bool over) {
+  const int len = run + 1;
+  a.ep_running[env] = over ? 0 : len;
+  if (!over) return;
+  // both loads before either store (which might alias them for all the
+  // compiler knows): one round trip at the kernel's tail, not two
+  VenvEpAcc *ac = a.ep_acc + env;
+  VenvEpAcc v = *ac;
+  const int fl = a.ep_first[env];
+  v.count += 1;
+  v.len_min = len < v.len_min ? len : v.len_min;
+  v.len_max = len > v.len_max ? len : v.len_max;
+  v.len_sum += (int64_t)len;
+  v.len_sqsum += (uint64_t)len * (uint64_t)len;
+  *ac = v;
+  if (fl < 0) a.ep_first[env] = len;
+}
+
+template <int B, int D, bool EP>
 __global__ __launch_bounds__(256) void venv_step_kernel(VenvArgs a) {
   using S = VStepShape<B, D>;
   const int lane = threadIdx.x & 63;
@@ -110,6 +141,8 @@ __global__ __launch_bounds__(256) void venv_step_kernel(VenvArgs a) {
   const bool masked_in = !a.mask || a.mask[ec];
   const unsigned itw = *reinterpret_cast<const unsigned *>(ip);
   uint32_t x = a.rng[ec];
+  [[maybe_unused]] int run = 0;  // the episode in flight (EP)
+  if constexpr (EP) run = a.ep_running[ec];
   // this lane's bins li BPL .. li BPL + BPL - 1: NW words, byte k D + d =
   // bin k, dim d
   const uint32_t *wp = reinterpret_cast<const uint32_t *>(
@@ -194,6 +227,7 @@ __global__ __launch_bounds__(256) void venv_step_kernel(VenvArgs a) {
     if (a.mode == 1 && a.reward) a.reward[env] = over ? 0.0f : 1.0f;
     if (a.done) a.done[env] = (uint8_t)over;
     a.rng[env] = x;
+    if constexpr (EP) venv_ep_count(a, env, run, over);
   }
   if (a.obs) {  // observation::to_vector of the resulting state
 #pragma unroll
@@ -387,7 +421,7 @@ __global__ __launch_bounds__(256) void venv_legal_kernel(VenvArgs a,
 // row.  The words it masked with go to a.rec_legal's slot (where not null),
 // also for a refused env: they are a function of the state before the step.
 // The other instantiation holds none of this.
-template <int B, int D, bool RD, bool MASK>
+template <int B, int D, bool RD, bool MASK, bool EP>
 __global__ __launch_bounds__(256) void venv_act_kernel(VenvActArgs a) {
   using S = VStepShape<B, D>;
   static_assert(S::BPL % 4 == 0, "the lane's floats as 16-byte loads");
@@ -424,6 +458,8 @@ __global__ __launch_bounds__(256) void venv_act_kernel(VenvActArgs a) {
   for (int q = 0; q < S::NW; ++q) wv[q] = wp[q];
   const unsigned itw = *reinterpret_cast<const unsigned *>(ip);
   uint32_t x = a.v.rng[ec];
+  [[maybe_unused]] int run = 0;  // the episode in flight (EP)
+  if constexpr (EP) run = a.v.ep_running[ec];
 
   [[maybe_unused]] uint32_t eb = 0u;  // the lane's bits of eff(e) (MASK)
   if constexpr (MASK) {
@@ -636,6 +672,7 @@ __global__ __launch_bounds__(256) void venv_act_kernel(VenvActArgs a) {
       a.rec_reward[ro] = rew;
       a.rec_done[ro] = (uint8_t)over;
     }
+    if constexpr (EP) venv_ep_count(a.v, env, run, over);
   }
   if (a.v.obs) {  // observation::to_vector of the resulting state
 #pragma unroll
@@ -668,6 +705,8 @@ __global__ __launch_bounds__(256) void venv_reset_kernel(VenvArgs a) {
     uint32_t x = a.rng[env];
     venv_item(a.env, x, a.items + (size_t)env * 4);
     a.rng[env] = x;
+    // the abandoned episode is not counted
+    if (a.ep_running) a.ep_running[env] = 0;
   }
 }
 
@@ -735,9 +774,12 @@ hipError_t launch_venv(const VenvArgs &a, int op, hipStream_t s) {
   if (a.N <= 0) return hipSuccess;
 #define X(XB, XD)                                                            \
   if (B == XB && D == XD) {                                                  \
-    if (op == kVenvStep)                                                     \
-      hipLaunchKernelGGL((venv_step_kernel<XB, XD>), venv_step_grid(a.N, B), \
-                         dim3(256), 0, s, a);                                \
+    if (op == kVenvStep && a.ep_running)                                     \
+      hipLaunchKernelGGL((venv_step_kernel<XB, XD, true>),                   \
+                         venv_step_grid(a.N, B), dim3(256), 0, s, a);        \
+    else if (op == kVenvStep)                                                \
+      hipLaunchKernelGGL((venv_step_kernel<XB, XD, false>),                  \
+                         venv_step_grid(a.N, B), dim3(256), 0, s, a);        \
     else if (op == kVenvReset)                                               \
       hipLaunchKernelGGL((venv_reset_kernel<XB, XD>), venv_grid(a.N, B),     \
                          dim3(256), 0, s, a);                                \
@@ -751,24 +793,31 @@ hipError_t launch_venv(const VenvArgs &a, int op, hipStream_t s) {
   return hipErrorInvalidValue;
 }
 
-// RD where the call records its distributions, MASK where it masks
+// RD where the call records its distributions, MASK where it masks, EP where
+// it counts episodes
+template <int B, int D, bool RD, bool MASK>
+static void vact_launch_ep(const VenvActArgs &a, hipStream_t s) {
+  const dim3 grid = venv_step_grid(a.v.N, B);
+  if (a.v.ep_running)
+    hipLaunchKernelGGL((venv_act_kernel<B, D, RD, MASK, true>), grid,
+                       dim3(256), 0, s, a);
+  else
+    hipLaunchKernelGGL((venv_act_kernel<B, D, RD, MASK, false>), grid,
+                       dim3(256), 0, s, a);
+}
+
 template <int B, int D>
 static void vact_launch(const VenvActArgs &a, hipStream_t s) {
-  const dim3 grid = venv_step_grid(a.v.N, B);
   if (a.legal) {
     if (a.rec_distrib)
-      hipLaunchKernelGGL((venv_act_kernel<B, D, true, true>), grid, dim3(256),
-                         0, s, a);
+      vact_launch_ep<B, D, true, true>(a, s);
     else
-      hipLaunchKernelGGL((venv_act_kernel<B, D, false, true>), grid, dim3(256),
-                         0, s, a);
+      vact_launch_ep<B, D, false, true>(a, s);
   } else {
     if (a.rec_distrib)
-      hipLaunchKernelGGL((venv_act_kernel<B, D, true, false>), grid, dim3(256),
-                         0, s, a);
+      vact_launch_ep<B, D, true, false>(a, s);
     else
-      hipLaunchKernelGGL((venv_act_kernel<B, D, false, false>), grid,
-                         dim3(256), 0, s, a);
+      vact_launch_ep<B, D, false, false>(a, s);
   }
 }
 

@@ -333,6 +333,18 @@ hipError_t launch_pg_loss(const PgLearnArgs &a, int max_rows, hipStream_t s);
 // Vectorised environment for callers with their own policy (xh_venv_*,
 // venv_kernels.hip): bins int8 [N][B*D], items int8 [N][4], rng u32 [N].
 enum VenvOp { kVenvStep = 0, kVenvReset = 1, kVenvObserve = 2 };
+// Episode statistics (xh_venv_set_episode_stats, venv_episode_kernels.hip):
+// an env's window accumulators, 32 bytes, touched only by the step that ends
+// an episode of the env (its bin-0 lane) and by the row kernel, which clears
+// them (count 0, sums 0, len_min INT32_MAX, len_max 0).
+struct VenvEpAcc {
+  int32_t count;             // episodes ended since the last row
+  int32_t len_min, len_max;  // of their lengths
+  int32_t pad;
+  int64_t len_sum;
+  uint64_t len_sqsum;
+};
+static_assert(sizeof(VenvEpAcc) == 32, "one env's accumulators are 32 bytes");
 struct VenvArgs {
   EnvDesc env;
   int N;
@@ -347,6 +359,12 @@ struct VenvArgs {
   int mode;               // 0 environment::apply, 1 agent::step minus react
   uint32_t skip_mul;      // a^policy_draws (step)
   uint32_t jump_mul;      // a^(k (Nglobal - 1)) after a step (reference order)
+  // episode statistics: all three null while off.  ep_running is read and
+  // written by every live env step; the other two only where a step ends an
+  // episode
+  int32_t *ep_running;    // [N] steps of the episode in flight
+  int32_t *ep_first;      // [N] the env's first finished length, -1 until then
+  VenvEpAcc *ep_acc;      // [N] the window accumulators
 };
 // xh_venv_act: react's sampling + agent::step in one launch (venv_act_kernel).
 struct VenvActArgs {
@@ -383,6 +401,22 @@ hipError_t launch_venv_act(const VenvActArgs &a, hipStream_t s);
 hipError_t launch_venv_legal(const VenvArgs &a, uint32_t *out, hipStream_t s);
 hipError_t launch_venv_init(const VenvArgs &a, uint32_t x0, int env_offset,
                             int n_global, int k, hipStream_t s);
+
+// Episode statistics of a venv (venv_episode_kernels.hip).
+// running 0, first -1, the accumulators cleared
+hipError_t launch_venv_ep_init(int N, int32_t *running, int32_t *first,
+                               VenvEpAcc *acc, hipStream_t s);
+// One row of XH_VEP_COUNT doubles from the per-env blocks, which it clears:
+// workgroup partials psum [venv_ep_grid(N)][kVepSums] and pext
+// [venv_ep_grid(N)][kVepExts] (min length, max length, max running), then
+// one wave's fixed-order sum into row.
+constexpr int kVepSums = 7;
+constexpr int kVepExts = 3;
+int venv_ep_grid(int N);
+hipError_t launch_venv_ep_row(int N, const int32_t *running,
+                              const int32_t *first, VenvEpAcc *acc,
+                              double *psum, double *pext, double row_index,
+                              double calls, double *row, hipStream_t s);
 
 // The learner's side of a recorded window (xh_venv_record_obs /
 // xh_venv_advantages, venv_learn_kernels.hip).

@@ -1309,6 +1309,7 @@ size_t xh_struct_size(const char *name) {
   if (!std::strcmp(name, "xh_venv_adv")) return sizeof(xh_venv_adv);
   if (!std::strcmp(name, "xh_venv_loss")) return sizeof(xh_venv_loss);
   if (!std::strcmp(name, "xh_venv_loss_ext")) return sizeof(xh_venv_loss_ext);
+  if (!std::strcmp(name, "xh_vep_row")) return XH_VEP_COUNT * sizeof(double);
   return 0;
 }
 

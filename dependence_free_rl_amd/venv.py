@@ -22,7 +22,11 @@ policy_loss(..., legal=True) masks the minibatch the same way, and env.legal()
 returns the current states' sets.  So are PPO's two usual extras:
 policy_loss(..., ent_coef=c) adds the entropy bonus's gradient to every row
 and policy_loss(..., v_old=..., vclip=...) clips the value loss
-(xh_venv_policy_loss_ex).
+(xh_venv_policy_loss_ex).  And episode statistics: after
+env.set_episode_stats(rows) the step() / act() / apply() launches count every
+env's episode lengths on the device, env.episode_row() appends one row of sums
+to a device ring, and env.episode_stats() / episode_curve() /
+first_episode_lengths() read them back.
 
 Mirrors xylo::environment<A,S>::apply / view / reset (rl.h:163-170) with the
 id ranging over the batch, bp::environment (bin_packing.h:46-85) and
@@ -95,6 +99,7 @@ class VecEnv:
         self.N, self.B, self.D = num_envs, bins, dims
         self.h = C.c_void_p()
         self._dev = {}  # device scratch: name -> (address, bytes)
+        self._ep_history = 0  # the episode ring's rows (set_episode_stats)
         check(_lib.lib.xh_venv_create(ctx.h, num_envs, bins, dims, rng_state,
                                       env_offset, num_envs_global or num_envs,
                                       policy_draws, C.byref(self.h)))
@@ -574,6 +579,102 @@ class VecEnv:
                                        log))
         got = self._download(log, np.float32, (3,))
         return float(got[2]), float(got[1])
+
+    # ---- episode statistics, counted on the device ------------------------
+    def set_episode_stats(self, rows):
+        """Episode statistics (xh_venv_set_episode_stats): from now on every
+        step() / act() / apply() launch counts each env's steps and, where the
+        step ends the episode, the finished length; episode_row() reduces the
+        counts into one row of a device ring of `rows` rows.  Calling it again
+        restarts everything; 0 turns the statistics off and frees them.  An
+        episode in flight is counted from this call on: switch on after
+        creation or a reset."""
+        check(_lib.lib.xh_venv_set_episode_stats(self.h, int(rows)))
+        self._ep_history = int(rows)
+
+    def episode_row(self):
+        """Append one row to the ring (xh_venv_episode_row; asynchronous) and
+        clear the window's accumulators."""
+        check(_lib.lib.xh_venv_episode_row(self.h))
+
+    def episode_count(self):
+        """Rows taken since set_episode_stats (xh_venv_episode_count)."""
+        n = C.c_long()
+        check(_lib.lib.xh_venv_episode_count(self.h, C.byref(n)))
+        return n.value
+
+    def episode_stats(self, first=None, count=None):
+        """Rows [first, first + count) as float64 [rows][VEP_COUNT]
+        (xh_venv_get_episode_rows; synchronises).  Default: every row still in
+        the ring."""
+        total = self.episode_count()
+        if first is None:
+            held = min(total, self._ep_history)
+            first = total - (held if count is None else min(count, held))
+        if count is None:
+            count = total - first
+        out = np.zeros((count, _lib.VEP_COUNT), np.float64)
+        check(_lib.lib.xh_venv_get_episode_rows(self.h, first, count,
+                                                _ptr(out)))
+        return out
+
+    def episode_curve(self):
+        """Per-row series derived from episode_stats(): a dict of float64
+        arrays, one entry per row in the ring -- "row", "calls", "episodes",
+        "len_mean", "len_std" (population), "return_mean" (an episode's
+        return is its length - 1), "len_min", "len_max", "return_min",
+        "return_max", "envs_finished", "first_len_mean", "first_len_std",
+        "first_return_mean".  NaN where a row has no episode (or, for the
+        first-episode entries, no env has finished one)."""
+        r = self.episode_stats()
+        L = _lib
+        with np.errstate(invalid="ignore", divide="ignore"):
+            n = r[:, L.VEP_EPISODES]
+            mean = r[:, L.VEP_LEN_SUM] / n
+            var = r[:, L.VEP_LEN_SQSUM] / n - mean * mean
+            k = r[:, L.VEP_ENVS_FINISHED]
+            fmean = r[:, L.VEP_FIRST_LEN_SUM] / k
+            fvar = r[:, L.VEP_FIRST_LEN_SQSUM] / k - fmean * fmean
+        return {"row": r[:, L.VEP_ROW], "calls": r[:, L.VEP_CALLS],
+                "episodes": n, "len_mean": mean,
+                "len_std": np.sqrt(np.maximum(var, 0.0)),
+                "return_mean": mean - 1.0,
+                "len_min": r[:, L.VEP_LEN_MIN], "len_max": r[:, L.VEP_LEN_MAX],
+                "return_min": r[:, L.VEP_LEN_MIN] - 1.0,
+                "return_max": r[:, L.VEP_LEN_MAX] - 1.0,
+                "envs_finished": k, "first_len_mean": fmean,
+                "first_len_std": np.sqrt(np.maximum(fvar, 0.0)),
+                "first_return_mean": fmean - 1.0}
+
+    def episode_state(self):
+        """(running, first): int32 [N] each -- the steps of every env's
+        episode in flight and every env's first finished length, -1 where it
+        has none yet (xh_venv_episode_get)."""
+        out = []
+        for which in (_lib.VEPS_RUNNING, _lib.VEPS_FIRST):
+            a = np.zeros(self.N, np.int32)
+            check(_lib.lib.xh_venv_episode_get(self.h, which, _ptr(a),
+                                               a.nbytes))
+            out.append(a)
+        return tuple(out)
+
+    def set_episode_state(self, running, first):
+        """Continue another run's counts (xh_venv_episode_set): after
+        set(VENV_BINS / ITEMS / RNG) of a saved state -- set(VENV_BINS) zeroes
+        the running lengths, so this call comes last.  Take a row before
+        saving: the window's accumulators are not part of the state."""
+        for which, arr in ((_lib.VEPS_RUNNING, running),
+                           (_lib.VEPS_FIRST, first)):
+            a = np.ascontiguousarray(arr, np.int32).reshape(self.N)
+            check(_lib.lib.xh_venv_episode_set(self.h, which, _ptr(a),
+                                               a.nbytes))
+
+    def first_episode_lengths(self):
+        """The lengths of the envs' first finished episodes, int32 [k], k =
+        the envs that have finished one: one episode per env, the unbiased
+        sample of a vector env's evaluation."""
+        first = self.episode_state()[1]
+        return first[first >= 0]
 
     def apply(self, mask=None):
         """environment::apply(actions[e], e) for the masked envs (no reset);

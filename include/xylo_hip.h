@@ -1111,6 +1111,76 @@ int xh_venv_synchronize(xh_venv *v);
  * that reduces its statistics is not timed. */
 int xh_venv_set_timing(xh_venv *v, int on);
 int xh_venv_kernel_time(xh_venv *v, double *ms, long *launches);
+/* Episode statistics, counted on the device (opt-in; off at creation, and
+ * while off every launch computes and writes what it did without them and
+ * nothing is allocated).  With them on, the xh_venv_step / xh_venv_act /
+ * xh_venv_apply launches themselves count, per env, the steps of the episode
+ * in flight -- every step of an env the call applied; an env that was masked
+ * out, or whose action or policy row was refused, took no step and is not
+ * counted.  Where the step ended the episode (DONE[e] = 1) the finished
+ * length, the overflowing step included (what XH_STAT_EPLEN_SUM counts), goes
+ * into the env's window accumulators, into the env's first-episode length if
+ * it is the env's first since the switch-on, and the running length restarts
+ * at 0.  xh_venv_apply does not reset the env, but it ends the episode where
+ * it reports game over, so the caller's xh_venv_reset that follows changes
+ * no count.  An episode's return in this env is its length - 1
+ * (bin_packing.h:102-106), so no float is tracked.
+ *
+ * xh_venv_episode_row appends one row of XH_VEP_COUNT doubles to a device
+ * ring of history_rows rows, asynchronously on the context's stream (a
+ * reduction over the envs and a one-wave launch; fixed order, no atomics:
+ * every entry is an exact integer, bit-identical from run to run), and clears
+ * the window accumulators -- not the running lengths, not the first-episode
+ * lengths:
+ *   XH_VEP_ROW        rows taken since the switch-on (this row's index)
+ *   XH_VEP_CALLS      step / act / apply launches counted into this row
+ *   XH_VEP_EPISODES   episodes that ended in this row's span
+ *   XH_VEP_LEN_SUM, XH_VEP_LEN_SQSUM   the sum of their lengths, of the squares
+ *   XH_VEP_LEN_MIN, XH_VEP_LEN_MAX     NaN where EPISODES is 0
+ *   XH_VEP_ENVS_FINISHED   envs with at least one finished episode since the
+ *                     switch-on (cumulative)
+ *   XH_VEP_FIRST_LEN_SUM, XH_VEP_FIRST_LEN_SQSUM   over those envs, each env's
+ *                     first episode (cumulative): one episode per env, the
+ *                     unbiased evaluation protocol of a vector env ("the
+ *                     first K episodes to finish" over-represents short ones)
+ *   XH_VEP_RUNNING_SUM, XH_VEP_RUNNING_MAX   the episodes in flight at the row
+ * A row covers this venv's envs only: nothing is all-reduced.
+ *
+ * xh_venv_set_episode_stats: history_rows in [1, 2^20] gives a fresh ring and
+ *   fresh per-env blocks -- every running length 0, every first length -1,
+ *   the row counter 0 -- also when statistics are on already; 0 turns them
+ *   off and frees everything.  An episode in flight at the switch-on is
+ *   counted from that call on: switch on after xh_venv_create or a reset.
+ * xh_venv_episode_count: rows taken so far.  xh_venv_get_episode_rows
+ *   synchronises and copies rows [first, first + count) to out; XH_ERR_INVALID
+ *   for a row that is overwritten or not yet written.  All three ring calls
+ *   return XH_ERR_STATE while statistics are off.
+ * The per-env state: XH_VEPS_RUNNING int32 [N], XH_VEPS_FIRST int32 [N] (-1:
+ *   none yet).  xh_venv_episode_bytes is an array's size (0 while off),
+ *   xh_venv_episode_ptr its device address (NULL while off), xh_venv_episode_
+ *   get / _set copy from / to host memory (synchronising; `bytes` must be the
+ *   array's size).  _set exists so that a run resumed from xh_venv_get / set
+ *   of BINS / ITEMS / RNG continues its counts: take a row before saving (the
+ *   window accumulators are not part of the saved state), and set BINS before
+ *   the episode state.
+ * State rules: xh_venv_reset zeroes the running length of the envs it resets
+ *   (the abandoned episode is not counted); xh_venv_set(XH_VENV_BINS) zeroes
+ *   every running length; XH_VENV_ITEMS, XH_VENV_RNG and xh_venv_record_rewind
+ *   change no count.  xh_venv_destroy frees everything.  With xh_venv_set_
+ *   timing on, xh_venv_episode_row is one bracket around its two launches. */
+enum { XH_VEP_ROW = 0, XH_VEP_CALLS, XH_VEP_EPISODES, XH_VEP_LEN_SUM,
+       XH_VEP_LEN_SQSUM, XH_VEP_LEN_MIN, XH_VEP_LEN_MAX, XH_VEP_ENVS_FINISHED,
+       XH_VEP_FIRST_LEN_SUM, XH_VEP_FIRST_LEN_SQSUM, XH_VEP_RUNNING_SUM,
+       XH_VEP_RUNNING_MAX, XH_VEP_COUNT };  /* xh_struct_size("xh_vep_row") */
+enum { XH_VEPS_RUNNING = 0, XH_VEPS_FIRST, XH_VEPS_COUNT };
+int xh_venv_set_episode_stats(xh_venv *v, int history_rows);
+int xh_venv_episode_row(xh_venv *v);
+int xh_venv_episode_count(xh_venv *v, long *total_rows);
+int xh_venv_get_episode_rows(xh_venv *v, long first, int count, double *out);
+size_t xh_venv_episode_bytes(const xh_venv *v, int which);
+void *xh_venv_episode_ptr(xh_venv *v, int which);
+int xh_venv_episode_get(xh_venv *v, int which, void *host, size_t bytes);
+int xh_venv_episode_set(xh_venv *v, int which, const void *host, size_t bytes);
 
 /* ------------------------------------------------------ model::eval -- */
 /* xylo::model::eval (nn.h:473-479) of a layer chain on the device: rows x

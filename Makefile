@@ -26,18 +26,21 @@ OBJS     := $(SRC)/policy_kernels.o $(SRC)/value_kernels.o \
             $(SRC)/diag_kernels.o \
             $(SRC)/train_select.o $(SRC)/model_api.o $(SRC)/tensor_api.o \
             $(SRC)/xylo_hip.o $(SRC)/digest_kernels.o $(SRC)/state_api.o \
-            $(SRC)/venv_api.o
+            $(SRC)/venv_api.o $(SRC)/ctx_api.o $(SRC)/trainer_learn.o \
+            $(SRC)/trainer_pg.o $(SRC)/trainer_diag.o $(SRC)/eval_api.o \
+            $(SRC)/phase_trace.o
 # superseded train kernels (the config-3 / config-5
 # epoch's earlier forms), kept for A/B runs in the variant library only
 VARIANT_KERNELS := policy_split_kernels policy_split128_kernels \
             policy_split8w_kernels policy_split8wp_kernels \
             policy_split4p_kernels policy_split8wg_kernels
 HDRS     := $(SRC)/xh_device.h $(SRC)/xh_kernels.h $(SRC)/xh_split.h \
+            $(SRC)/xh_img16.h \
             $(SRC)/spec8_layout.h $(SRC)/spec8_e0_layout.h $(SRC)/spec8_l1_layout.h \
             $(SRC)/xh_opt.h $(SRC)/xh_clip.h \
             $(SRC)/xh_diag.h $(SRC)/xh_sums.h $(SRC)/xh_seg.h $(SRC)/xh_vstore.h \
             $(SRC)/xh_digest.h $(SRC)/xh_state_blob.h $(SRC)/xh_trainer.h \
-            $(SRC)/xh_host.h include/xylo_hip.h
+            $(SRC)/xh_host.h $(SRC)/xh_ring.h include/xylo_hip.h
 
 # Drop-in C++20 layer (include/xylo_compat): the reference's unmodified
 # apps/bin_packing drivers (when the reference tree is present) and our own
@@ -96,22 +99,7 @@ $(SRC)/policy_split4h_kl_kernels.o: $(SRC)/policy_split4h_kernels.hip $(HDRS)
 	$(HIPCC) $(HIPFLAGS) $(FLAGS_policy_split4h_kernels) -DXH_4H_KL_TU=1 \
 	    -mllvm -pragma-unroll-threshold=200000 -c $< -o $@
 
-$(SRC)/xylo_hip.o: $(SRC)/xylo_hip.cpp $(HDRS)
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-
-$(SRC)/train_select.o: $(SRC)/train_select.cpp $(HDRS)
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-
-$(SRC)/model_api.o: $(SRC)/model_api.cpp $(HDRS)
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-
-$(SRC)/tensor_api.o: $(SRC)/tensor_api.cpp $(HDRS)
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-
-$(SRC)/state_api.o: $(SRC)/state_api.cpp $(HDRS)
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-
-$(SRC)/venv_api.o: $(SRC)/venv_api.cpp $(HDRS)
+$(SRC)/%.o: $(SRC)/%.cpp $(HDRS)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
 # the variant library: the product objects + the superseded train kernels,

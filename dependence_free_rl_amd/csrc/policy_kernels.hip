@@ -33,7 +33,7 @@
 #endif
 // Every ablation test folds to `false` in the product build, so a stray
 // XH_ABLATE in the environment cannot change what the shipped kernels compute
-// (the host refuses it too: xylo_hip.cpp do_learn).
+// (the host refuses it too: phase_trace.cpp).
 #define XH_ABL(a, k) (XH_DIAG_ABLATE && ((a).ablate & (k)))
 // Phase stamps (trace build, make variant VFLAGS=-DXH_DIAG_TRACE=1, run with
 // XH_PHASE_TRACE=1): lane 0 of every wave of the first kTraceBlocks
@@ -206,12 +206,6 @@ __device__ __forceinline__ float row_feature(const RowRaw<S> &rr, int rt,
     if (f == S::D + d) v = rr.iv[rt][d];
   }
   return f < S::F0 ? (float)v / (float)kCapacity : 0.0f;
-}
-
-// relu as max(bits, 0) on the int view: one v_max_i32 (x > 0 ? x : 0 costs a
-// NaN-canonicalise + v_max_f32); identical for every non-NaN x, -0 -> +0.
-__device__ __forceinline__ float relu(float x) {
-  return __int_as_float(max(__float_as_int(x), 0));
 }
 
 // 4 consecutive LDS floats (16-byte aligned) -> bias / weight values of

@@ -37,6 +37,7 @@
 
 #include "spec8_layout.h"
 #include "xh_device.h"
+#include "xh_img16.h"
 #include "xh_kernels.h"
 #include "xh_split.h"
 
@@ -99,58 +100,19 @@ static_assert(kLds <= 160 * 1024, "LDS");
 static_assert(F_Z % 4 == 0 && F_G % 4 == 0 && F_X % 4 == 0 && F_REC % 4 == 0 &&
                   F_B2 % 4 == 0 && F_W3 % 4 == 0,
               "16-byte aligned f32 vectors");
-#define FENCE() __builtin_amdgcn_sched_barrier(0)
+// the 16x16 image helpers (xh_img16.h)
+using img16::f32x4, img16::lbf16x8, img16::lbf16x4, img16::ls16x4,
+    img16::lf16x8;
+using img16::ld8, img16::ld8h, img16::st4, img16::st8h, img16::ldtr,
+    img16::lds4v, img16::opaque, img16::add_halves;
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __attribute__((address_space(3))) bf16x8 lbf16x8;
-typedef __attribute__((address_space(3))) bf16x4 lbf16x4;
-typedef __attribute__((address_space(3))) f16x8 lf16x8;
-typedef __attribute__((address_space(3))) s16x4 ls16x4;
 
-__device__ __forceinline__ bf16x8 ld8(int off) {
-  return *(const lbf16x8 *)(size_t)(unsigned)off;
-}
-__device__ __forceinline__ f16x8 ld8h(int off) {
-  return *(const lf16x8 *)(size_t)(unsigned)off;
-}
-__device__ __forceinline__ void st4(int off, bf16x4 v) {
-  *(lbf16x4 *)(size_t)(unsigned)off = v;
-}
-__device__ __forceinline__ void st8h(int off, f16x8 v) {
-  *(lf16x8 *)(size_t)(unsigned)off = v;
-}
-// two ds_read_b64_tr_b16 (EXEC full): elements 0-3 from o0, 4-7 from o1
-__device__ __forceinline__ bf16x8 ldtr(int o0, int o1) {
-  const s16x4 v0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((ls16x4 *)(size_t)(unsigned)o0);
-  const s16x4 v1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((ls16x4 *)(size_t)(unsigned)o1);
-  typedef short s16x8 __attribute__((ext_vector_type(8)));
-  const s16x8 v = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
-  return __builtin_bit_cast(bf16x8, v);
-}
-__device__ __forceinline__ f32x4 lds4v(const float *p) {
-  return *reinterpret_cast<const f32x4 *>(p);
-}
 __device__ __forceinline__ f32x2 lds2v(const float *p) {
   return *reinterpret_cast<const f32x2 *>(p);
 }
-__device__ __forceinline__ float relu(float x) {
-  return __int_as_float(max(__float_as_int(x), 0));
-}
-// a lane base that the compiler must not re-derive (so that image offsets
-// below 64 KB fold into the ds instructions' immediates)
-__device__ __forceinline__ int opaque(int v) {
-  asm volatile("" : "+v"(v));
-  return v;
-}
 template <int V>
 using Par = std::integral_constant<int, V>;
-// v + the other lane half's v, the same bits in both halves
-__device__ __forceinline__ float add_halves(float v) {
-  const auto b = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v),
-                                                  false, false);
-  return __uint_as_float(b[0]) + __uint_as_float(b[1]);
-}
 
 __global__ __launch_bounds__(kThreads, 2) void policy_train_spec4_kernel(PolicyTrainArgs a) {
   extern __shared__ __attribute__((aligned(16))) char lds[];

@@ -25,6 +25,7 @@
 #include <cstdlib>
 
 #include "xh_device.h"
+#include "xh_img16.h"
 #include "xh_kernels.h"
 #include "xh_split.h"
 
@@ -84,96 +85,18 @@ static_assert(F_REC % 4 == 0 && F_GW % 4 == 0 && F_GP % 4 == 0 && F_X % 4 == 0 &
                   F_B2 % 4 == 0 && F_W3 % 4 == 0,
               "16-byte aligned f32 vectors");
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) bf16x8 lbf16x8;
-typedef __attribute__((address_space(3))) bf16x4 lbf16x4;
-typedef __attribute__((address_space(3))) s16x4 ls16x4;
-
-typedef __attribute__((address_space(3))) f16x8 lf16x8;
-typedef __attribute__((address_space(3))) f16x4 lf16x4;
-
-__device__ __forceinline__ f32x4 mfma16(bf16x8 a, bf16x8 b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
-__device__ __forceinline__ f32x4 mfma16h(f16x8 a, f16x8 b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
-}
-__device__ __forceinline__ f16x8 ld8h(int off) {
-  return *(const lf16x8 *)(size_t)(unsigned)off;
-}
-__device__ __forceinline__ void st4h(int off, f16x4 v) {
-  *(lf16x4 *)(size_t)(unsigned)off = v;
-}
-// image accesses at absolute LDS byte addresses
-__device__ __forceinline__ bf16x8 ld8(int off) {
-  return *(const lbf16x8 *)(size_t)(unsigned)off;
-}
-__device__ __forceinline__ void st4(int off, bf16x4 v) {
-  *(lbf16x4 *)(size_t)(unsigned)off = v;
-}
-// two ds_read_b64_tr_b16 (EXEC full): elements 0-3 from o0, 4-7 from o1
-__device__ __forceinline__ bf16x8 ldtr(int o0, int o1) {
-  const s16x4 v0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((ls16x4 *)(size_t)(unsigned)o0);
-  const s16x4 v1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((ls16x4 *)(size_t)(unsigned)o1);
-  typedef short s16x8 __attribute__((ext_vector_type(8)));
-  const s16x8 v = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
-  return __builtin_bit_cast(bf16x8, v);
-}
-// the images' swizzle: chunk ^= swz2(row & 15)
-__device__ __forceinline__ constexpr int swz2(int r) {
-  return ((r & 7) << 1) ^ ((r & 8) ? 9 : 0);
-}
-__device__ __forceinline__ int ioff2(int row, int ch) {
-  return kImgRow * row + 16 * (ch ^ swz2(row & 15));
-}
-// row reads: lane (G, li) reads row 16 rt + li, chunk 4s + G at
-// (rd_base ^ 64 s) + 4096 rt
-__device__ __forceinline__ int rd_base(int G, int li) {
-  return kImgRow * li + 16 * (G ^ swz2(li));
-}
-// dW2's A operand M^T by transposed reads: K-step ks element j of lane group
-// G is row 32 ks + 4G + j (j < 4) or 32 ks + 16 + 4G + j - 4 (the T layout's
-// r-tiles 2 ks, 2 ks + 1); read t: lane 4q + p supplies row 16t + 4G + q,
-// columns 16 ot + 4p .. +3, at (trm_base(t) ^ 32 ot) + 8192 ks
-__device__ __forceinline__ int trm_base(int l, int t) {
-  const int G = l >> 4, li = l & 15, q = li >> 2, p = li & 3;
-  const int row = 16 * t + 4 * G + q;
-  return kImgRow * row + 16 * ((p >> 1) ^ swz2(row & 15)) + 8 * (p & 1);
-}
-// stores from the C layout (row 16 rt + li, features 16 ft + 4G .. +3):
-// (st_base ^ 32 ft) + 4096 rt
-__device__ __forceinline__ int st_base(int G, int li) {
-  return kImgRow * li + 16 * ((G >> 1) ^ swz2(li)) + 8 * (G & 1);
-}
-__device__ __forceinline__ f32x4 lds4v(const float *p) {
-  return *reinterpret_cast<const f32x4 *>(p);
-}
-__device__ __forceinline__ float relu(float x) {
-  return __int_as_float(max(__float_as_int(x), 0));
-}
-// relu'(x) in {0, 1} from x's bits: v_med3_i32(bits, 0, 1) (a compare would
-// write VCC, and its consumer would wait the VCC hazard's s_nop)
-__device__ __forceinline__ int relu_bit(float x) {
-  int m;
-  asm("v_med3_i32 %0, %1, 0, 1" : "=v"(m) : "v"(__float_as_int(x)));
-  return m;
-}
+// the 16x16 image helpers (xh_img16.h); st_base is the 16x16 layout's
+using img16::f32x4, img16::lbf16x8, img16::lbf16x4, img16::ls16x4,
+    img16::lf16x8, img16::lf16x4;
+using img16::mfma16, img16::mfma16h, img16::ld8, img16::ld8h, img16::st4,
+    img16::st4h, img16::ldtr, img16::lds4v, img16::swz2, img16::ioff2,
+    img16::rd_base, img16::trm_base, img16::st_base, img16::relu_bit,
+    img16::sum_groups;
 // the integer relu masks of policy_split8wh_kernels.hip: here the inline asm
 // costs 74 spilled registers (4.88 -> 33.6 ms per epoch): off
 #ifndef XH_8X_IMASK
 #define XH_8X_IMASK 0
 #endif
-// sum over the four lane groups (rows of 16 lanes) without an LDS round
-// trip: ((g0 + g1) + (g2 + g3)) in every lane, as two __shfl_xor steps
-__device__ __forceinline__ float sum_groups(float v) {
-  const auto a = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v),
-                                                  false, false);
-  v = __uint_as_float(a[0]) + __uint_as_float(a[1]);
-  const auto b = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v),
-                                                  false, false);
-  return __uint_as_float(b[0]) + __uint_as_float(b[1]);
-}
-#define FENCE() __builtin_amdgcn_sched_barrier(0)
 
 #if XH_8X_KL_TU
 // kl_ppo_learner's epoch over every row of its state matrix, as

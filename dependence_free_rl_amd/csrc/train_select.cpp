@@ -15,7 +15,7 @@
 //                                  parameters and batch:
 //                                  policy_train_spec8_e0_kernel, on the
 //                                  rollout's relu masks and distributions --
-//                                  chosen by the trainer (xylo_hip.cpp do_learn,
+//                                  chosen by the trainer (trainer_learn.cpp,
 //                                  e0_valid; XH_E0_REUSE), not here: the later
 //                                  epochs come through this file as before
 //   128 bins, 3-D, [128,128] (config 5)      policy_train_split8x_kernel

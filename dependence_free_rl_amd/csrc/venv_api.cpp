@@ -72,14 +72,14 @@ struct xh_venv {
   // xh_venv_set_episode_stats (opt-in; everything null / 0 while off): the
   // per-env blocks the step / act / apply launches count into, the row
   // kernel's workgroup partials, and the device ring of XH_VEP_COUNT doubles
-  // per row; `rows` counts the rows taken, `calls` the launches since the
-  // last one
+  // per row (ring.rows counts the rows taken); `calls` counts the launches
+  // since the last one
   struct episode_stats {
-    int history = 0;
-    long rows = 0, calls = 0;
+    xh::host::row_ring ring{nullptr, XH_VEP_COUNT};
+    long calls = 0;
     int32_t *state[XH_VEPS_COUNT] = {};  // XH_VEPS_RUNNING, XH_VEPS_FIRST
     xh::VenvEpAcc *acc = nullptr;
-    double *psum = nullptr, *pext = nullptr, *ring = nullptr;
+    double *psum = nullptr, *pext = nullptr;
   } ep;
 
   template <class T>
@@ -260,7 +260,7 @@ int venv_launch(xh_venv *v, int op, int mode, bool use_mask, bool obs) {
   if (op == xh::kVenvObserve) a.obs = (float *)v->buf[XH_VENV_OBS];
   if (mode == 0) a.reward = nullptr;
   CHK(venv_timed(v, [&] { return xh::launch_venv(a, op, v->ctx->stream); }));
-  if (op == xh::kVenvStep && v->ep.history) ++v->ep.calls;
+  if (op == xh::kVenvStep && v->ep.ring.history) ++v->ep.calls;
   return XH_OK;
 }
 
@@ -284,7 +284,7 @@ void venv_free_episode_stats(xh_venv *v) {
   if (ep.acc) (void)hipFree(ep.acc);
   if (ep.psum) (void)hipFree(ep.psum);
   if (ep.pext) (void)hipFree(ep.pext);
-  if (ep.ring) (void)hipFree(ep.ring);
+  if (ep.ring.dev) (void)hipFree(ep.ring.dev);
   ep = xh_venv::episode_stats{};
 }
 
@@ -295,7 +295,7 @@ bool veps_which(int which) { return which >= 0 && which < XH_VEPS_COUNT; }
 int venv_check_episode_array(const xh_venv *v, int which, const void *host,
                              size_t bytes, const char *what) {
   if (!v || !host) return fail(XH_ERR_INVALID, "null arg");
-  if (!v->ep.history)
+  if (!v->ep.ring.history)
     return fail(XH_ERR_STATE, "%s: episode statistics are off "
                 "(xh_venv_set_episode_stats)", what);
   if (!veps_which(which) || bytes != (size_t)v->N * 4)
@@ -671,7 +671,7 @@ int xh_venv_set(xh_venv *v, int which, const void *host, size_t bytes) {
     if (const int st = venv_ensure(v, which)) return st;
     HIPCHK(copy_to_device(v->buf[which], host, bytes, v->ctx->stream));
     // new bins are new episodes: every running length restarts
-    if (which == XH_VENV_BINS && v->ep.history)
+    if (which == XH_VENV_BINS && v->ep.ring.history)
       HIPCHK(hipMemsetAsync(v->ep.state[XH_VEPS_RUNNING], 0, (size_t)v->N * 4,
                             v->ctx->stream));
     HIPCHK(hipStreamSynchronize(v->ctx->stream));
@@ -749,7 +749,7 @@ int xh_venv_act(xh_venv *v, const float *policy_dev, int kind, int mode,
     const int st = venv_timed(
         v, [&] { return xh::launch_venv_act(a, v->ctx->stream); });
     if (st == XH_OK && v->rec_steps > 0) ++v->rec_pos;
-    if (st == XH_OK && v->ep.history) ++v->ep.calls;
+    if (st == XH_OK && v->ep.ring.history) ++v->ep.calls;
     return st;
   });
 }
@@ -1113,9 +1113,9 @@ int xh_venv_set_episode_stats(xh_venv *v, int history_rows) {
       e = hipMalloc((void **)&ep.psum, grid * xh::kVepSums * 8);
     if (e == hipSuccess)
       e = hipMalloc((void **)&ep.pext, grid * xh::kVepExts * 8);
-    if (e == hipSuccess) e = hipMalloc((void **)&ep.ring, ring);
+    if (e == hipSuccess) e = hipMalloc((void **)&ep.ring.dev, ring);
     // unwritten rows read as NaN (all-ones bytes)
-    if (e == hipSuccess) e = hipMemsetAsync(ep.ring, 0xFF, ring, s);
+    if (e == hipSuccess) e = hipMemsetAsync(ep.ring.dev, 0xFF, ring, s);
     if (e == hipSuccess)
       e = xh::launch_venv_ep_init(v->N, ep.state[XH_VEPS_RUNNING],
                                   ep.state[XH_VEPS_FIRST], ep.acc, s);
@@ -1125,7 +1125,7 @@ int xh_venv_set_episode_stats(xh_venv *v, int history_rows) {
       return fail(XH_ERR_HIP, "venv episode stats(%d): %s", history_rows,
                   hipGetErrorString(e));
     }
-    ep.history = history_rows;
+    ep.ring.history = history_rows;
     return XH_OK;
   });
 }
@@ -1133,18 +1133,18 @@ int xh_venv_set_episode_stats(xh_venv *v, int history_rows) {
 int xh_venv_episode_row(xh_venv *v) {
   return venv_call(v, [&]() -> int {
     auto &ep = v->ep;
-    if (!ep.history)
+    if (!ep.ring.history)
       return fail(XH_ERR_STATE, "venv episode row: episode statistics are off "
                   "(xh_venv_set_episode_stats)");
     HIPCHK(hipSetDevice(v->ctx->device));
-    double *row = ep.ring + (size_t)(ep.rows % ep.history) * XH_VEP_COUNT;
+    double *row = ring_row(ep.ring, ep.ring.rows);
     CHK(venv_timed(v, [&] {
       return xh::launch_venv_ep_row(v->N, ep.state[XH_VEPS_RUNNING],
                                     ep.state[XH_VEPS_FIRST], ep.acc, ep.psum,
-                                    ep.pext, (double)ep.rows, (double)ep.calls,
-                                    row, v->ctx->stream);
+                                    ep.pext, (double)ep.ring.rows,
+                                    (double)ep.calls, row, v->ctx->stream);
     }));
-    ++ep.rows;
+    ++ep.ring.rows;
     ep.calls = 0;
     return XH_OK;
   });
@@ -1153,10 +1153,10 @@ int xh_venv_episode_row(xh_venv *v) {
 int xh_venv_episode_count(xh_venv *v, long *total_rows) {
   return guard([&]() -> int {
     if (!v || !total_rows) return fail(XH_ERR_INVALID, "null arg");
-    if (!v->ep.history)
+    if (!v->ep.ring.history)
       return fail(XH_ERR_STATE, "venv episode count: episode statistics are "
                   "off (xh_venv_set_episode_stats)");
-    *total_rows = v->ep.rows;
+    *total_rows = v->ep.ring.rows;
     return XH_OK;
   });
 }
@@ -1165,36 +1165,15 @@ int xh_venv_get_episode_rows(xh_venv *v, long first, int count, double *out) {
   return guard([&]() -> int {
     if (!v || (count > 0 && !out)) return fail(XH_ERR_INVALID, "null arg");
     const auto &ep = v->ep;
-    if (!ep.history)
+    if (!ep.ring.history)
       return fail(XH_ERR_STATE, "venv episode rows: episode statistics are off "
                   "(xh_venv_set_episode_stats)");
-    if (first < 0 || count < 0 || first > ep.rows - count)
-      return fail(XH_ERR_INVALID, "venv episode rows: %d rows from row %ld, "
-                  "%ld written", count, first, ep.rows);
-    if (first < ep.rows - ep.history)
-      return fail(XH_ERR_INVALID, "venv episode rows: row %ld is overwritten "
-                  "(the ring holds rows %ld .. %ld)", first,
-                  ep.rows - ep.history, ep.rows - 1);
-    HIPCHK(hipSetDevice(v->ctx->device));
-    hipStream_t s = v->ctx->stream;
-    HIPCHK(hipStreamSynchronize(s));
-    // at most two runs of the ring
-    const long at = first % ep.history;
-    const long n1 = std::min<long>(count, ep.history - at);
-    const size_t rowb = (size_t)XH_VEP_COUNT * 8;
-    if (n1 > 0)
-      HIPCHK(copy_to_host(out, ep.ring + (size_t)at * XH_VEP_COUNT,
-                          (size_t)n1 * rowb, s));
-    if (count > n1)
-      HIPCHK(copy_to_host(out + (size_t)n1 * XH_VEP_COUNT, ep.ring,
-                          (size_t)(count - n1) * rowb, s));
-    HIPCHK(hipStreamSynchronize(s));
-    return XH_OK;
+    return ring_read(ep.ring, v->ctx, first, count, out, "venv episode rows");
   });
 }
 
 size_t xh_venv_episode_bytes(const xh_venv *v, int which) {
-  return v && v->ep.history && veps_which(which) ? (size_t)v->N * 4 : 0;
+  return v && v->ep.ring.history && veps_which(which) ? (size_t)v->N * 4 : 0;
 }
 
 void *xh_venv_episode_ptr(xh_venv *v, int which) {

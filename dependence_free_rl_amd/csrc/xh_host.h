@@ -1,9 +1,9 @@
-// xh_host.h -- internal helpers of the C ABI's host runtime (xylo_hip.cpp,
-// venv_api.cpp, model_api.cpp, tensor_api.cpp, state_api.cpp): the error slot
-// behind xh_last_error, status macros, the exception guard, stream-ordered
-// copies, zero-filled device allocations, pooled timing events, the context
-// struct with its release rule, and the env description both the trainer and
-// the venv start from.
+// xh_host.h -- internal helpers of the C ABI's host runtime (every .cpp unit
+// here): the error slot behind xh_last_error, status macros, the exception
+// guard, stream-ordered copies, zero-filled device allocations, pooled timing
+// events, the device row ring of the opt-in statistics (index arithmetic:
+// xh_ring.h), the context struct with its release rule, and the env
+// description both the trainer and the venv start from.
 #ifndef XH_HOST_H_
 #define XH_HOST_H_
 
@@ -18,6 +18,7 @@
 
 #include "../../include/xylo_hip.h"
 #include "xh_kernels.h"
+#include "xh_ring.h"
 
 struct xh_ctx {
   int device = 0, rank = 0, world = 1;
@@ -138,6 +139,47 @@ inline hipError_t pooled_event(std::vector<hipEvent_t> &pool, hipEvent_t *e) {
     return hipSuccess;
   }
   return hipEventCreateWithFlags(e, hipEventDisableSystemFence);
+}
+
+// A device ring of rows of `width` doubles (the trainer's statistics and
+// update diagnostics, the venv's episode statistics): row r lives in slot
+// r % history, `rows` counts the rows written so far, unwritten rows are NaN.
+// Its owner allocates and fills `dev`; history == 0 while it is off.
+struct row_ring {
+  double *dev = nullptr;
+  int width = 0;
+  int history = 0;
+  long rows = 0;
+};
+
+inline double *ring_row(const row_ring &r, long row) {
+  return r.dev + (size_t)(row % r.history) * r.width;
+}
+
+// Rows [first, first + count) of the ring -> out, in at most two runs, after
+// one synchronisation of the context's stream; `who` prefixes the messages.
+inline int ring_read(const row_ring &r, const xh_ctx *c, long first, int count,
+                     double *out, const char *who) {
+  switch (ring_check(first, count, r.history, r.rows)) {
+    case kRingRange:
+      return fail(XH_ERR_INVALID, "%s: %d rows from row %ld, %ld written", who,
+                  count, first, r.rows);
+    case kRingOverwritten:
+      return fail(XH_ERR_INVALID, "%s: row %ld is overwritten (the ring holds "
+                  "rows %ld .. %ld)", who, first, r.rows - r.history,
+                  r.rows - 1);
+  }
+  HIPCHK(hipSetDevice(c->device));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  const ring_runs run = ring_span(first, count, r.history);
+  const size_t rowb = (size_t)r.width * 8;
+  if (run.n1 > 0)
+    HIPCHK(copy_to_host(out, r.dev + (size_t)run.at * r.width,
+                        (size_t)run.n1 * rowb, c->stream));
+  if (run.n2 > 0)
+    HIPCHK(copy_to_host(out + (size_t)run.n1 * r.width, r.dev,
+                        (size_t)run.n2 * rowb, c->stream));
+  return XH_OK;
 }
 
 inline void ctx_free(xh_ctx *c) {

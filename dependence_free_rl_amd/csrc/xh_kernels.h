@@ -1,5 +1,5 @@
 // xh_kernels.h -- kernel argument blocks and launch entry points shared by the
-// host runtime (xylo_hip.cpp) and the HIP kernel files.  No torch types.
+// host runtime (the .cpp units) and the HIP kernel files.  No torch types.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -320,13 +320,16 @@ __device__ __forceinline__ void img_store_h2(char *img_hi, char *img_lo, int bas
   }
 }
 
+// relu as max(bits, 0) on the int view: one v_max_i32 (x > 0 ? x : 0 costs a
+// NaN-canonicalise + v_max_f32); identical for every non-NaN x, -0 -> +0.
+__device__ __forceinline__ float relu(float x) {
+  return __int_as_float(max(__float_as_int(x), 0));
+}
+
 // ---- helpers of the split train kernels (variants/policy_split_kernels.hip,
 // variants/policy_split128_kernels.hip)
 namespace split {
 
-__device__ __forceinline__ float relu(float x) {
-  return __int_as_float(max(__float_as_int(x), 0));
-}
 __device__ __forceinline__ float4 lds4(const float *p) {
   return *reinterpret_cast<const float4 *>(p);
 }

@@ -1,11 +1,16 @@
 // xh_trainer.h -- the trainer behind the C ABI's xh_trainer handle, shared by
-// the translation units that implement calls on it (xylo_hip.cpp: create,
-// rollout, learn and the accessors; state_api.cpp: save / restore / digest).
+// the translation units that implement calls on it (xylo_hip.cpp: lifecycle,
+// data accessors and the rollout; trainer_learn.cpp: learn() and the optimizer
+// step; trainer_pg.cpp: REINFORCE; trainer_diag.cpp: the opt-in diagnostics;
+// eval_api.cpp: the evaluators; phase_trace.cpp: the diagnostic build's
+// phase trace; state_api.cpp: save / restore / digest), with the helpers and
+// entry points they share.
 #ifndef XH_TRAINER_H_
 #define XH_TRAINER_H_
 
 #include <hip/hip_runtime.h>
 
+#include <cstring>
 #include <map>
 #include <string>
 #include <vector>
@@ -90,13 +95,13 @@ struct xh_trainer {
   } pg;
   // xh_trainer_set_stats (opt-in; everything null / 0 while off): the device
   // ring of rows, the envs' running episode lengths, the kernels' workgroup
-  // partials and the three gradient norms; rows = rows opened so far; open =
-  // the last row's window is not consumed yet (learn() fills its learner part)
+  // partials and the three gradient norms; ring.rows = rows opened so far;
+  // open = the last row's window is not consumed yet (learn() fills its
+  // learner part)
   struct stats_state {
-    int history = 0;
-    long rows = 0;
+    xh::host::row_ring ring{nullptr, XH_STAT_COUNT};
     bool open = false;
-    double *ring = nullptr, *part = nullptr, *norms = nullptr;
+    double *part = nullptr, *norms = nullptr;
     int *ep_len = nullptr;
   } stats;
   // xh_trainer_set_grad_clip of the policy [0] and value [1] nets (opt-in;
@@ -112,12 +117,13 @@ struct xh_trainer {
   // xh_trainer_set_update_diag (opt-in; everything null / 0 while off): one
   // device block holding the ring of rows, the sum kernel's workgroup partials
   // and the per-row records [T][N] of the last probed learn() (ent, kl, then
-  // p_new); learns = learn() calls since it was set, rows = probed ones (ring
-  // rows written); info / kl_source = what the last probed learn() ran
+  // p_new); learns = learn() calls since it was set, ring.rows = probed ones
+  // (ring rows written); info / kl_source = what the last probed learn() ran
   struct upd_state {
-    int history = 0, every = 1;
-    long learns = 0, rows = 0;
-    double *ring = nullptr, *part = nullptr, *ent = nullptr, *kl = nullptr;
+    xh::host::row_ring ring{nullptr, XH_UPD_COUNT};
+    int every = 1;
+    long learns = 0;
+    double *part = nullptr, *ent = nullptr, *kl = nullptr;
     float *p_new = nullptr;
     xh::KernelInfo info;
     const char *kl_source = nullptr;
@@ -197,6 +203,76 @@ inline void wrote(xh_trainer *t, int what) {
   if (what & kWroteValue) t->vfrag_ready = false;
   if (what & (kWrotePolicy | kWroteBatch)) t->e0_valid = false;
 }
+inline int wrote_net(int which) {
+  return which == XH_POLICY ? kWrotePolicy : kWroteValue;
+}
+
+constexpr uint64_t kEvalStride = 1ull << 26;  // draws between env streams
+
+template <class P>
+int dalloc(xh_trainer *t, P **p, size_t bytes) {
+  void *q = nullptr;
+  CHK(dev_zalloc(t->ctx->stream, &q, bytes < 16 ? 16 : bytes, "trainer"));
+  t->allocs.push_back(q);
+  *p = reinterpret_cast<P *>(q);
+  return XH_OK;
+}
+
+// Launch wrapper: optional HIP-event timing on the trainer's stream.
+template <class F>
+int timed(xh_trainer *t, const char *name, F &&launch) {
+  hipStream_t s = t->ctx->stream;
+  timed_event ev;
+  const bool rec = t->timing == 1 ||
+                   (t->timing == XH_TIMING_TRAIN && std::strcmp(name, "policy_train") == 0);
+  if (rec) {
+    ev.name = name;
+    HIPCHK(pooled_event(t->event_pool, &ev.start));
+    HIPCHK(pooled_event(t->event_pool, &ev.stop));
+    HIPCHK(hipEventRecord(ev.start, s));
+  }
+  hipError_t e = launch();
+  if (e != hipSuccess)
+    return fail(XH_ERR_HIP, "launch %s: %s", name, hipGetErrorString(e));
+  if (rec) {
+    HIPCHK(hipEventRecord(ev.stop, s));
+    t->events.push_back(ev);
+  }
+  return XH_OK;
+}
+
+// A slot of the batch learn() reads may hold a bin below -capacity (bins_wide)
+inline bool batch_wide(const xh_trainer *t) {
+  bool wide = false;
+  for (size_t sl = 0; sl < t->T() && sl < t->bins_wide.size(); ++sl)
+    wide |= t->bins_wide[sl] != 0;
+  return wide;
+}
+
+// trainer_learn.cpp
+int allreduce(xh_trainer *t, float *buf, int n);
+int allreduce_d(xh_trainer *t, double *buf, int n);
+xh::MlpArgs value_mlp(xh_trainer *t, int rows, float *out);
+int reduce_and_step(xh_trainer *t, int which, int step, const float *slab,
+                    int nslab, int stride, int n, float *grad, float *params,
+                    xh::SlabAlias al = xh::SlabAlias{0, 0, 0, 0});
+int do_learn(xh_trainer *t);
+// trainer_pg.cpp
+int create_pg(xh_ctx *ctx, const xh_config &c, xh_trainer **out);
+int do_pg_rollout(xh_trainer *t);
+int do_pg_learn(xh_trainer *t);
+// trainer_diag.cpp: the hooks of the opt-in diagnostics in rollout / learn
+void stats_free(xh_trainer *t);
+int stats_rollout(xh_trainer *t);
+int stats_learn(xh_trainer *t);
+void upd_free(xh_trainer *t);
+int upd_learn(xh_trainer *t, bool e0_at_entry);
+void clip_free(xh_trainer *t, int which);
+// phase_trace.cpp: XH_ABLATE -> pa->ablate (refused by the product library)
+// and, in the diagnostic build under XH_PHASE_TRACE, pa->trace armed for the
+// next train launch; the report reads it back, prints it and disarms it
+int phase_trace_begin(xh_trainer *t, xh::PolicyTrainArgs *pa);
+int phase_trace_report(xh_trainer *t, xh::PolicyTrainArgs *pa);
 
 }  // namespace host
 }  // namespace xh

@@ -112,7 +112,6 @@ __device__ __forceinline__ bf16x8 ldtr_at(const char *lds, int o0, int o1) {
   return __builtin_bit_cast(bf16x8, v);
 }
 using split::lds4;
-using split::relu;
 #define FENCE() __builtin_amdgcn_sched_barrier(0)
 
 __global__ __launch_bounds__(kThreads, 1) void policy_train_split4p_kernel(

@@ -36,6 +36,7 @@
 #include <cstdlib>
 
 #include "xh_device.h"
+#include "xh_img16.h"
 #include "xh_kernels.h"
 #include "xh_split.h"
 
@@ -93,11 +94,9 @@ static_assert((L_F + 4 * F_Z) % 16 == 0 && (L_F + 4 * F_X) % 16 == 0 &&
                   (L_F + 4 * F_G) % 16 == 0,
               "16-byte aligned f32 vectors");
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+// from the 16x16 image helpers (xh_img16.h); the image layout is this file's
+using img16::f32x4, img16::mfma16, img16::lds4v;
 
-__device__ __forceinline__ f32x4 mfma16(bf16x8 a, bf16x8 b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
 // the six products of two split operands, small terms first (xh_split.h)
 __device__ __forceinline__ f32x4 split6(const bf16x8 (&a)[3], const bf16x8 (&b)[3],
                                         f32x4 c) {
@@ -174,12 +173,6 @@ __device__ __forceinline__ void st_split(char *img, int off, const f32x4 &v) {
   *reinterpret_cast<bf16x4 *>(img + off) = ph;
   *reinterpret_cast<bf16x4 *>(img + kImg + off) = pm;
   *reinterpret_cast<bf16x4 *>(img + 2 * kImg + off) = pl;
-}
-__device__ __forceinline__ f32x4 lds4v(const float *p) {
-  return *reinterpret_cast<const f32x4 *>(p);
-}
-__device__ __forceinline__ float relu(float x) {
-  return __int_as_float(max(__float_as_int(x), 0));
 }
 
 __global__ __launch_bounds__(kThreads, 2) void policy_train_split8w_kernel(

@@ -8,7 +8,6 @@ HF="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-result -Iinclud
 D=build/t8x${2:+_$2}
 mkdir -p $D
 /opt/rocm/bin/hipcc $HF -DXH_DIAG_TRACE=1 -c dependence_free_rl_amd/csrc/policy_kernels.hip -o $D/policy_kernels.o
-/opt/rocm/bin/hipcc $HF -DXH_DIAG_TRACE=1 -c dependence_free_rl_amd/csrc/xylo_hip.cpp -o $D/xylo_hip.o
 /opt/rocm/bin/hipcc $HF -mllvm -amdgpu-mfma-vgpr-form -DXH_DIAG_TRACE=1 $1 -c dependence_free_rl_amd/csrc/policy_split8x_kernels.hip -o $D/policy_split8x_kernels.o
-OBJS=$(ls dependence_free_rl_amd/csrc/*.o | grep -v "/policy_kernels.o\|/policy_split8x_kernels.o\|/xylo_hip.o")
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -o $D/libxylo_hip.so $D/policy_kernels.o $D/xylo_hip.o $D/policy_split8x_kernels.o $OBJS -L/opt/rocm/lib -lrccl -Wl,-rpath,/opt/rocm/lib
+OBJS=$(ls dependence_free_rl_amd/csrc/*.o | grep -v "/policy_kernels.o\|/policy_split8x_kernels.o")
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -o $D/libxylo_hip.so $D/policy_kernels.o $D/policy_split8x_kernels.o $OBJS -L/opt/rocm/lib -lrccl -Wl,-rpath,/opt/rocm/lib

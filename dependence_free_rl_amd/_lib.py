@@ -174,6 +174,8 @@ def _load():
                                        C.POINTER(C.c_long)]),
         "xh_trainer_reset_timing": (i, [vp]),
         "xh_trainer_kernel_info": (i, [vp, C.c_char_p, sz]),
+        "xh_trainer_pack_stats": (i, [vp, C.POINTER(C.c_long), C.POINTER(C.c_long),
+                                      C.POINTER(C.c_long)]),
         "xh_ctx_inject_fault": (i, [vp, i]),
         "xh_trainer_get_env_state": (i, [vp, i, i, vp, vp]),
         "xh_trainer_set_env_state": (i, [vp, i, i, vp, vp]),

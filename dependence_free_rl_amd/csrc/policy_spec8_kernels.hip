@@ -93,6 +93,7 @@
 #include "spec8_e0_layout.h"
 #include "spec8_l1_layout.h"
 #include "spec8_layout.h"
+#include "spec8_pack_layout.h"
 #include "xh_device.h"
 #include "xh_img16.h"
 #include "xh_kernels.h"
@@ -177,6 +178,36 @@
 #endif
 #if XH_SP8_E0_TU && (XH_SP8_KL_TU || XH_SP8_DW2_3P || XH_SP8_ABLATE)
 #error "the epoch-0 build is the plain PPO kernel's (f16-pair dW2, no ablation)"
+#endif
+// XH_SP8_PACK_TU=1 (policy_spec8_pack_kernels.o): the plain PPO / actor-critic
+// kernel over the PACKED batch of spec8_pack_kernels.hip (spec8_pack_layout.h,
+// DESIGN.md §3.0e "duplicate rows").  A 64-row group holds four 16-row
+// segments, one env-step each: the env-step's distinct rows k with their
+// multiplicities c_k.  The softmax and its backward are closed under
+// multiplicities,
+//   se = sum_k c_k e^{z_k},  p_k = e^{z_k} / se,  p_a = p_{k*},
+//   PPO  G_k = gc p_a ([k = k*] - c_k p_k),   AC  G_k = A (c_k p_k - [k = k*]),
+// and everything behind g is linear in g per row, so only the staging (a
+// group's record in place of a transition's rows) and the softmax stages
+// differ: sums over the 16 lanes of a segment weighted by the counts, the
+// record (chosen row, p_old, A) per segment in place of the wave-uniform
+// one.  A row with count 0 (unused slot, empty segment of a class's last
+// group) gets g = 0.  A group past the packed ones is "wide": ONE env-step
+// of more than 16 distinct rows, all 64 with count 1 and the four segment
+// records equal -- its sums run over all four segments, which is today's
+// arithmetic.  The group count comes from device memory (pk_hdr); a workgroup
+// with no group writes a zero slab.  Layer 1, layer 2, the masks, dH1, g (x)
+// H1, dW2, dW1 and the write-outs are the plain build's, line for line.
+#ifndef XH_SP8_PACK_TU
+#define XH_SP8_PACK_TU 0
+#endif
+#if XH_SP8_PACK_TU && (XH_SP8_KL_TU || XH_SP8_E0_TU || XH_SP8_DW2_3P || XH_SP8_ABLATE)
+#error "the packed build is the plain PPO / actor-critic kernel's"
+#endif
+#if XH_SP8_KL_TU || XH_SP8_PACK_TU
+#define SP8KLP(...) __VA_ARGS__
+#else
+#define SP8KLP(...)
 #endif
 #ifndef XH_SP8_GH2
 #define XH_SP8_GH2 0
@@ -268,6 +299,7 @@ namespace xh {
 namespace sp8 {
 
 constexpr int kB = 64, kD = 2, kF0 = 2 * kD, kH = 128;
+static_assert(kB == kPkSegs * kPkSegRows, "a group: four segments");
 constexpr int kThreads = 512;
 constexpr int kImg = 16384;        // one [128][64] / [64][128] 16-bit image
 constexpr int kGhParts = XH_SP8_DW2_3P ? 3 : 2;
@@ -323,8 +355,16 @@ constexpr int F_W3 = F_B2 + kH;    // [128] w3 / S2 (unscales the partial logits
 constexpr int F_Z = F_W3 + kH;     // [64 rows][4 matrix waves] partial logits
 constexpr int F_G = F_Z + 256;     // [2 slots][3][64] g, g x0, g x1 of a group
 constexpr int F_X = F_G + 384;     // [4 slots][2 dims][64 rows] bins / 8
+#if XH_SP8_PACK_TU
+// (packed build: a slot holds its group's four segment records [chosen row,
+// pold, adv, env-step], the group's "item is item_a" in place of segment 0's
+// env-step index)
+constexpr int kRec = 16;
+#else
+constexpr int kRec = 4;
+#endif
 constexpr int F_REC = F_X + 512;   // [4 slots][action, pold, adv, item is item_a]
-constexpr int F_SC = F_REC + 16;   // [16] scale reduction scratch, the scales
+constexpr int F_SC = F_REC + 4 * kRec;  // [16] scale reduction scratch, the scales
 constexpr int F_B3 = F_SC + 16;    // [4]
 constexpr int F_DB3 = F_B3 + 4;    // [32] matrix wave 0's db3 sums, per lane
 constexpr int F_SIMD = F_DB3 + 32; // [8] the SIMD each wave runs on (ints)
@@ -334,6 +374,9 @@ constexpr int F_FU = F_FS + kH;    // [128] 2^-15 / s_i (the masks' 2^15 with it
 constexpr int F_Q = F_FU + kH;     // [4 slots][64 bins] old distribution q
 constexpr int F_KL = F_Q + 256;    // [4 matrix waves][32 lanes] KL sums (doubles)
 constexpr int F_END = F_KL + 256;
+#elif XH_SP8_PACK_TU
+constexpr int F_CNT = F_FU + kH;   // [4 slots][64 rows] the rows' multiplicities
+constexpr int F_END = F_CNT + 256;
 #else
 constexpr int F_END = F_FU + kH;
 #endif
@@ -368,6 +411,8 @@ __global__ __launch_bounds__(kThreads, 2) void policy_train_spec8_3p_kernel(Poli
 #elif XH_SP8_E0_TU
 __global__ __launch_bounds__(kThreads, 2) void policy_train_spec8_e0_kernel(PolicyTrainArgs a,
                                                                             PolicyTrainE0Args ea) {
+#elif XH_SP8_PACK_TU
+__global__ __launch_bounds__(kThreads, 2) void policy_train_spec8_pk_kernel(PolicyTrainArgs a) {
 #else
 __global__ __launch_bounds__(kThreads, 2) void policy_train_spec8_kernel(PolicyTrainArgs a) {
 #endif
@@ -383,6 +428,13 @@ __global__ __launch_bounds__(kThreads, 2) void policy_train_spec8_kernel(PolicyT
   const int n_end = *a.n_end;
   const int ngroups = NT + a.b.N + n_end;
   const float beta = *a.beta;
+#elif XH_SP8_PACK_TU
+  // the packed batch's groups: the packed ones (item_a's, then item_b's), then
+  // the wide ones
+  const int ngroups = __builtin_amdgcn_readfirstlane(a.pk_hdr[kPkGroups]);
+  const int pk_ga = __builtin_amdgcn_readfirstlane(a.pk_hdr[kPkGA]);
+  const int pk_np = pk_ga + __builtin_amdgcn_readfirstlane(a.pk_hdr[kPkGB]);
+  const int pk_ua = __builtin_amdgcn_readfirstlane(a.pk_hdr[kPkUA]);  // wide, item_a
 #else
   const int ngroups = a.b.T * a.b.N;
 #endif
@@ -393,6 +445,13 @@ __global__ __launch_bounds__(kThreads, 2) void policy_train_spec8_kernel(PolicyT
                      ? ((int)blockIdx.x & 7) * ((int)gridDim.x >> 3) + ((int)blockIdx.x >> 3)
                      : (int)blockIdx.x;
   const int J = b0 < ngroups ? (ngroups - b0 + (int)gridDim.x - 1) / (int)gridDim.x : 0;
+#if XH_SP8_PACK_TU
+  if (J == 0) {  // (the grid is sized by env-steps: no group left for this one)
+    float *z = a.slab + (size_t)blockIdx.x * a.slab_stride;
+    for (int e = tid; e < a.slab_stride; e += kThreads) z[e] = 0.0f;
+    return;
+  }
+#endif
   if (J == 0) return;  // uniform over the workgroup
   const int gstep = (int)gridDim.x;
   auto tindex = [&](int j) { return (size_t)(b0 + min(j, J - 1) * gstep); };
@@ -610,6 +669,37 @@ __global__ __launch_bounds__(kThreads, 2) void policy_train_spec8_kernel(PolicyT
       }
     };
 #endif
+#if XH_SP8_PACK_TU
+    // (packed build: the group's record, spec8_pack_layout.h -- the 64 rows'
+    // bins as above; lanes 0-15 the four segment records' dwords, lanes 16-31
+    // the 64 counts, four bytes each; the item follows from the group's class)
+    auto stage_load = [&](int j) {
+      const size_t gi = tindex(j);
+      const int lane =
+          opaque((int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)));
+      const unsigned char *rec = a.pk + gi * (size_t)kPkGroupBytes;
+      const int bins = reinterpret_cast<const unsigned short *>(rec)[lane];
+      // dwords 32 .. 47 of the record are the counts, 48 .. 63 the segments
+      const int dw = 32 + ((lane + 16) & 31);
+      return Raw{bins, reinterpret_cast<const int *>(rec)[dw]};
+    };
+    auto stage_store = [&](const Raw &r, int sl, int j) {
+      const float x0 = (float)(signed char)(r.bi & 0xff) / (float)kCapacity;
+      const float x1 = (float)(signed char)((r.bi >> 8) & 0xff) / (float)kCapacity;
+      lf[F_X + sl * 128 + l] = x0;
+      lf[F_X + sl * 128 + 64 + l] = x1;
+      const int g = (int)tindex(j);
+      const bool ia = g < pk_ga || (g >= pk_np && g < pk_np + pk_ua);
+      if (l < 16) lf[F_REC + kRec * sl + l] = (l == 3) ? (ia ? 1.0f : 0.0f) : __int_as_float(r.rec);
+      if (l >= 16 && l < 32) {
+        const unsigned c = (unsigned)r.rec;
+        float *cp = lf + F_CNT + 64 * sl + 4 * (l - 16);
+        *reinterpret_cast<f32x4 *>(cp) =
+            f32x4{(float)(c & 0xffu), (float)((c >> 8) & 0xffu), (float)((c >> 16) & 0xffu),
+                  (float)(c >> 24)};
+      }
+    };
+#else
     auto stage_load = [&](int j) {
 #if XH_SP8_KL_TU
       size_t ti = tindex(j), qi = 0;
@@ -689,6 +779,7 @@ __global__ __launch_bounds__(kThreads, 2) void policy_train_spec8_kernel(PolicyT
         lf[F_REC + 4 * sl + 3] =
             (i0 == a.env.item_a[0] && i1 == a.env.item_a[1]) ? 1.0f : 0.0f;
     };
+#endif
 
 #if XH_SP8_E0_TU
     // the rollout's forward outputs of group j (clamped as tindex): p of rows
@@ -802,6 +893,13 @@ __global__ __launch_bounds__(kThreads, 2) void policy_train_spec8_kernel(PolicyT
       float q0, q1;  // the old distribution of rows l31, 32 + l31 (pc, gc:
                      // the probability-space gradients; po: the row counts)
 #endif
+#if XH_SP8_PACK_TU
+      // (packed build) the records [chosen row, pold, adv, -] of the segments
+      // rows l31 and 32 + l31 lie in, the rows' counts, and the second row's
+      // se / pc / gc (se, pc, gc: the first row's)
+      f32x4 ra, rb;
+      float c0, c1, se1, pc1, gc1;
+#endif
     } sm;
 #if XH_SP8_KL_TU
     // KL(q || p) of the valid rows this wave summed: per-lane doubles in LDS
@@ -810,8 +908,99 @@ __global__ __launch_bounds__(kThreads, 2) void policy_train_spec8_kernel(PolicyT
     double *kl_lane = reinterpret_cast<double *>(lf + F_KL) + 32 * s;
     if (h == 0) kl_lane[l31] = 0.0;
 #endif
+#if XH_SP8_PACK_TU
+    // the packed build's stages 0 .. 5 (the header's formulas): a lane's two
+    // rows lie in segments l31 >> 4 and 2 + (l31 >> 4); a wide group's sums
+    // run over all four
+    auto pack_stage = [&](int gi, int stage) {
+      const int rs = gi & 3;
+      switch (stage) {
+        case 0: {
+          const float *rp = lf + F_REC + kRec * rs + 4 * opaque(l31 >> 4);
+          sm.ra = lds4v(rp);
+          sm.rb = lds4v(rp + 8);
+          sm.b3 = lf[F_B3];
+          sm.z0 = lds4v(lf + F_Z + 4 * l31);
+          sm.z1 = lds4v(lf + F_Z + 4 * (32 + l31));
+          if (s == 0) {
+            const float *xr = lf + F_X + rs * 128 + opaque(l31);
+            sm.x = f32x4{xr[0], xr[32], xr[64], xr[96]};
+          }
+          break;
+        }
+        case 1: {
+          const float *cp = lf + F_CNT + 64 * rs + opaque(l31);
+          sm.c0 = cp[0];
+          sm.c1 = cp[32];
+          sm.ex0 = __expf(((sm.z0[0] + sm.z0[1]) + (sm.z0[2] + sm.z0[3])) + sm.b3);
+          sm.ex1 = __expf(((sm.z1[0] + sm.z1[1]) + (sm.z1[2] + sm.z1[3])) + sm.b3);
+          break;
+        }
+        case 2: {
+          // the segments' count-weighted sums, every lane its own segment's
+          // (DPP row reductions)
+          float s0 = seg_sum<16>(sm.c0 * sm.ex0), s1 = seg_sum<16>(sm.c1 * sm.ex1);
+          if ((int)tindex(gi) >= pk_np) {  // wide (wave-uniform): all 64 rows
+            float t = s0 + s1;
+            t += __shfl_xor(t, 16, kWave);
+            s0 = s1 = t;
+          }
+          // (an empty segment: no row counts, p stays finite)
+          sm.se = s0 > 0.0f ? s0 : 1.0f;
+          sm.se1 = s1 > 0.0f ? s1 : 1.0f;
+          break;
+        }
+        case 3:
+          sm.p0 = sm.ex0 * __builtin_amdgcn_rcpf(sm.se);
+          sm.p1 = sm.ex1 * __builtin_amdgcn_rcpf(sm.se1);
+          break;
+        case 4: {
+          // p of the chosen rows: a segment's lanes share the record, so the
+          // source lane picks the value (p0 / p1) its readers mean
+          const int cu0 = __float_as_int(sm.ra[0]), cu1 = __float_as_int(sm.rb[0]);
+          sm.pc = __shfl(cu0 >= 32 ? sm.p1 : sm.p0, cu0 & 31, kWave);
+          sm.pc1 = __shfl(cu1 >= 32 ? sm.p1 : sm.p0, cu1 & 31, kWave);
+          if (a.algo == kPPO) {
+            float ce = a.clip_eps;
+            asm volatile("" : "+s"(ce));
+            const float r0 = sm.pc * __builtin_amdgcn_rcpf(sm.ra[1]),
+                        r1 = sm.pc1 * __builtin_amdgcn_rcpf(sm.rb[1]);
+            const float k0 = fminf(fmaxf(r0, 1.0f - ce), 1.0f + ce),
+                        k1 = fminf(fmaxf(r1, 1.0f - ce), 1.0f + ce);
+            const float ig0 = fminf(k0 * sm.ra[2], r0 * sm.ra[2]) * -1.0f,
+                        ig1 = fminf(k1 * sm.rb[2], r1 * sm.rb[2]) * -1.0f;
+            sm.gc = ig0 * __builtin_amdgcn_rcpf(sm.pc);
+            sm.gc1 = ig1 * __builtin_amdgcn_rcpf(sm.pc1);
+          }
+          break;
+        }
+        default: {
+          const int cu0 = __float_as_int(sm.ra[0]), cu1 = __float_as_int(sm.rb[0]);
+          const float cp0 = sm.c0 * sm.p0, cp1 = sm.c1 * sm.p1;
+          float g0, g1;
+          if (a.algo == kPPO) {
+            g0 = ((l31 == cu0 ? sm.p0 : 0.0f) - cp0 * sm.pc) * sm.gc;
+            g1 = ((32 + l31 == cu1 ? sm.p1 : 0.0f) - cp1 * sm.pc1) * sm.gc1;
+          } else {
+            g0 = cp0 * sm.ra[2];
+            g1 = cp1 * sm.rb[2];
+            if (l31 == cu0) g0 -= sm.ra[2];
+            if (32 + l31 == cu1) g1 -= sm.rb[2];
+          }
+          gz[0] = sm.c0 != 0.0f ? g0 : 0.0f;
+          gz[1] = sm.c1 != 0.0f ? g1 : 0.0f;
+        }
+      }
+    };
+#endif
     auto softmax_stage = [&](int gi, int gpar, bool acc, int stage) {
       const int rs = gi & 3;
+#if XH_SP8_PACK_TU
+      if (stage < 6) {
+        pack_stage(gi, stage);
+        return;
+      }
+#endif
       switch (stage) {
         case 0:
           sm.rec = lds4v(lf + F_REC + 4 * rs);
@@ -1107,9 +1296,9 @@ __global__ __launch_bounds__(kThreads, 2) void policy_train_spec8_kernel(PolicyT
     f32x16s c[2];
 #endif
     if (s == 0) {
-      stage_store(stage_load(0), 0 SP8KL(, 0));
-      stage_store(stage_load(1), 1 SP8KL(, 1));
-      stage_store(stage_load(2), 2 SP8KL(, 2));
+      stage_store(stage_load(0), 0 SP8KLP(, 0));
+      stage_store(stage_load(1), 1 SP8KLP(, 1));
+      stage_store(stage_load(2), 2 SP8KLP(, 2));
     }
     __syncthreads();  // P1: rows staged          (vector: L1(0))
     __syncthreads();  // P2
@@ -1214,7 +1403,7 @@ __global__ __launch_bounds__(kThreads, 2) void policy_train_spec8_kernel(PolicyT
       __syncthreads();
       // B(j): dW2 of group j with group j+1's softmax, dW3 / db2 sums and
       // masks in its MFMA slots
-      if (s == 0) stage_store(raw, (j + 3) & 3 SP8KL(, j + 3));
+      if (s == 0) stage_store(raw, (j + 3) & 3 SP8KLP(, j + 3));
       const bool acc = j + 1 < J;
       if (SP8_RUN(1 | 16))
         dw2(par, [&](int k) { b_task(c, j + 1, 1 - par, acc, k); });
@@ -1343,7 +1532,7 @@ __global__ __launch_bounds__(kThreads, 2) void policy_train_spec8_kernel(PolicyT
     };
     auto b1_of = [&](int gi) {
       const bool ia =
-          __builtin_amdgcn_readfirstlane(__float_as_int(lf[F_REC + 4 * (gi & 3) + 3])) != 0;
+          __builtin_amdgcn_readfirstlane(__float_as_int(lf[F_REC + kRec * (gi & 3) + 3])) != 0;
       return ia ? b1a : b1b;
     };
 #if !XH_SP8_E0_TU
@@ -1432,7 +1621,7 @@ __global__ __launch_bounds__(kThreads, 2) void policy_train_spec8_kernel(PolicyT
     auto l1_mfma = [&](int gi, f32x16s (&pre)[2]) {
       const int sl = gi & 3;
       const bool ia =
-          __builtin_amdgcn_readfirstlane(__float_as_int(lf[F_REC + 4 * sl + 3])) != 0;
+          __builtin_amdgcn_readfirstlane(__float_as_int(lf[F_REC + kRec * sl + 3])) != 0;
       // X fragment (the B operand), lane column r = 32 t + l31, k = 8 h + e:
       // the row's five inputs three times over (l1_x_word); both lane halves
       // carry data
@@ -1453,7 +1642,7 @@ __global__ __launch_bounds__(kThreads, 2) void policy_train_spec8_kernel(PolicyT
     auto l1_mfma = [&](int gi, f32x16s (&pre)[2]) {
       const int sl = gi & 3;
       const bool ia =
-          __builtin_amdgcn_readfirstlane(__float_as_int(lf[F_REC + 4 * sl + 3])) != 0;
+          __builtin_amdgcn_readfirstlane(__float_as_int(lf[F_REC + kRec * sl + 3])) != 0;
       // X fragment (the B operand), lane column r = 32 t + l31, k = 8 h + e:
       // (x0, x1), (1, ia), (ib, 0), (0, 0) in lane half 0, zeros in half 1
       const unsigned d1 = h ? 0u : (ia ? 0x3F803F80u : 0x00003F80u);
@@ -1668,7 +1857,7 @@ __global__ __launch_bounds__(kThreads, 2) void policy_train_spec8_kernel(PolicyT
       w1 += a1[0] + a1[1];
       const float sg = ag[0] + ag[1];
       const bool ia =
-          __builtin_amdgcn_readfirstlane(__float_as_int(lf[F_REC + 4 * (gi & 3) + 3])) != 0;
+          __builtin_amdgcn_readfirstlane(__float_as_int(lf[F_REC + kRec * (gi & 3) + 3])) != 0;
       if (ia)
         sa += sg;
       else
@@ -1769,7 +1958,7 @@ __global__ __launch_bounds__(kThreads, 2) void policy_train_spec8_kernel(PolicyT
       w1 += a1[0] + a1[1];
       const float sg = ag[0] + ag[1];
       const bool ia =
-          __builtin_amdgcn_readfirstlane(__float_as_int(lf[F_REC + 4 * (gi & 3) + 3])) != 0;
+          __builtin_amdgcn_readfirstlane(__float_as_int(lf[F_REC + kRec * (gi & 3) + 3])) != 0;
       if (ia)
         sa += sg;
       else
@@ -1883,6 +2072,19 @@ hipError_t launch_policy_train_spec8_e0(const PolicyTrainArgs &a, const PolicyTr
   }
   hipLaunchKernelGGL(sp8::policy_train_spec8_e0_kernel, dim3(grid), dim3(sp8::kThreads),
                      sp8::kLds, s, a, ea);
+  return hipGetLastError();
+}
+#elif XH_SP8_PACK_TU
+hipError_t launch_policy_train_spec8_pack(const PolicyTrainArgs &a, int grid, hipStream_t s) {
+  if (!a.g_bound || !a.pk || !a.pk_hdr) return hipErrorInvalidValue;
+  static bool attr = false;
+  if (!attr) {
+    (void)hipFuncSetAttribute((const void *)sp8::policy_train_spec8_pk_kernel,
+                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)sp8::kLds);
+    attr = true;
+  }
+  hipLaunchKernelGGL(sp8::policy_train_spec8_pk_kernel, dim3(grid), dim3(sp8::kThreads),
+                     sp8::kLds, s, a);
   return hipGetLastError();
 }
 #elif XH_SP8_DW2_3P

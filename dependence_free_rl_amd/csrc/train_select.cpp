@@ -18,6 +18,21 @@
 //                                  chosen by the trainer (trainer_learn.cpp,
 //                                  e0_valid; XH_E0_REUSE), not here: the later
 //                                  epochs come through this file as before
+//                                  PPO / actor-critic by default, chosen by
+//                                  the trainer as well (trainer_learn.cpp,
+//                                  decide_pack; XH_SP8_PACK=0 switches it
+//                                  off): the same kernel's PACKED build
+//                                  (policy_spec8_pack_kernels.o, reported under
+//                                  the same name and math) over the batch
+//                                  spec8_pack_kernels.hip compacts once per
+//                                  learn() -- an env-step's distinct bin states
+//                                  with their counts in a 16-row segment, four
+//                                  env-steps per group; env-steps with more
+//                                  than 16 distinct states keep their 64 rows
+//                                  in the same launch.  Epoch 0 runs packed
+//                                  too (XH_E0_REUSE=2 keeps the e0 kernel).  A
+//                                  kernel override, a wide slot, ablation or a
+//                                  phase trace come through this file unpacked
 //   128 bins, 3-D, [128,128] (config 5)      policy_train_split8x_kernel
 //                                  (KL-PPO: policy_train_split8x_kl_kernel)
 //   32 bins, 1-D, [64,64] (config 2)         policy_train_split4h_kernel

@@ -12,6 +12,7 @@
 #include <string>
 
 #include "../../include/xylo_hip.h"
+#include "spec8_pack_layout.h"
 #include "xh_host.h"
 #include "xh_kernels.h"
 #include "xh_trainer.h"
@@ -479,6 +480,21 @@ int xh_trainer_kernel_info(xh_trainer *t, char *buf, size_t cap) {
     if (js.size() + 1 > cap)
       return fail(XH_ERR_INVALID, "kernel_info: %zu bytes needed", js.size() + 1);
     std::memcpy(buf, js.c_str(), js.size() + 1);
+    return XH_OK;
+  });
+}
+
+int xh_trainer_pack_stats(xh_trainer *t, long *packed, long *unpacked, long *groups) {
+  return guard([&]() -> int {
+    if (!t || !packed || !unpacked || !groups) return fail(XH_ERR_INVALID, "null arg");
+    *packed = *unpacked = *groups = 0;
+    if (!t->pk_hdr || !t->pk_learned) return XH_OK;
+    int h[xh::sp8::kPkHdrInts];
+    HIPCHK(hipMemcpyAsync(h, t->pk_hdr, sizeof(h), hipMemcpyDeviceToHost, t->ctx->stream));
+    HIPCHK(hipStreamSynchronize(t->ctx->stream));
+    *packed = (long)h[xh::sp8::kPkNA] + h[xh::sp8::kPkNB];
+    *unpacked = (long)h[xh::sp8::kPkUA] + h[xh::sp8::kPkUB];
+    *groups = h[xh::sp8::kPkGroups];
     return XH_OK;
   });
 }

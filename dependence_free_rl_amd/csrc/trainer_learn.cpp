@@ -13,6 +13,7 @@
 #include <cstring>
 
 #include "../../include/xylo_hip.h"
+#include "spec8_pack_layout.h"
 #include "xh_host.h"
 #include "xh_kernels.h"
 #include "xh_trainer.h"
@@ -189,17 +190,41 @@ int check_items(const xh_trainer *t) {
   return XH_OK;
 }
 
+// The PPO / actor-critic epochs of the 64-bin 2-D [128,128] policy over the
+// packed batch (duplicate rows computed once): where the
+// plain policy_train_spec8_kernel would run -- no kernel override, no wide
+// slot, no ablation or phase trace.  XH_SP8_PACK=0 (read per learn()) keeps
+// the unpacked path.
+bool decide_pack(const xh_trainer *t) {
+  return pack_selected(t) && !batch_wide(t);
+}
+
+// the compaction pass: once per learn(), behind the final advantages
+int pack_batch(xh_trainer *t, xh::PolicyTrainArgs *pa) {
+  hipStream_t s = t->ctx->stream;
+  const xh::PackArgs ka{t->env, t->batch(), t->adv, t->pk, t->pk_hdr, t->pk_cls, t->pk_blk};
+  CHK(timed(t, "pack", [&]() { return xh::launch_spec8_pack(ka, s); }));
+  pa->pk = t->pk;
+  pa->pk_hdr = t->pk_hdr;
+  t->pk_learned = true;
+  return XH_OK;
+}
+
 // Epoch 0 on the rollout's forward outputs (policy_train_spec8_e0_kernel):
 // PPO with a later epoch to follow, the outputs valid, nothing that selects
 // or instruments the train kernel.  XH_E0_REUSE (read per learn()): 0 never,
-// unset / 1 when valid, 2 (tests) fail the learn() when epoch 0 cannot.
-int decide_e0_reuse(const xh_trainer *t, bool *use_e0) {
+// unset / 1 when valid and the learn() does not run packed, 2 (tests, A/B
+// runs) always, failing the learn() when epoch 0 cannot.
+int decide_e0_reuse(const xh_trainer *t, bool pack, bool *use_e0) {
   const xh_config &c = t->cfg;
   const char *m = std::getenv("XH_E0_REUSE");
   const int mode = m && *m ? std::atoi(m) : 1;
   const char *ov = std::getenv("XH_TRAIN_KERNEL"), *ab = std::getenv("XH_ABLATE");
   const bool wide = batch_wide(t);
-  *use_e0 = mode != 0 && t->e0_valid && t->e0_mask && t->e0_p &&
+  // (a packed learn(): its epoch 0 runs packed as well, a quarter of the
+  // groups against the e0 kernel's saved forward pass -- DESIGN.md §8 -- unless
+  // 2 asks for the e0 kernel)
+  *use_e0 = mode != 0 && (mode == 2 || !pack) && t->e0_valid && t->e0_mask && t->e0_p &&
             c.algo == XH_PPO && c.epochs >= 2 && !(ov && *ov) && !wide &&
             !(ab && std::atoi(ab)) &&
             !(xh::diag_build() && std::getenv("XH_PHASE_TRACE"));
@@ -339,6 +364,13 @@ int policy_epochs(xh_trainer *t, xh::PolicyTrainArgs &pa, bool use_e0) {
       CHK(timed(t, "policy_train", [&]() {
         return xh::launch_policy_train_spec8_e0(pa, ea, t->pslab_n, s);
       }));
+    } else if (pa.pk && !pa.trace) {
+      // the same kernel's packed build: it reports as the plain one
+      t->last_train.name = "policy_train_spec8_kernel";
+      t->last_train.math = xh::kMathSplitTrainF16Pair;
+      CHK(timed(t, "policy_train", [&]() {
+        return xh::launch_policy_train_spec8_pack(pa, t->pslab_n, s);
+      }));
     } else {
       CHK(timed(t, "policy_train", [&]() {
         return xh::launch_policy_train(pa, c.policy_h1, c.policy_h2, t->pslab_n,
@@ -372,12 +404,15 @@ int do_learn(xh_trainer *t) {
   CHK(check_items(t));
   const bool e0_at_entry = t->e0_valid;  // for the update diagnostics
   bool use_e0 = false;
-  CHK(decide_e0_reuse(t, &use_e0));
+  const bool pack = decide_pack(t);
+  CHK(decide_e0_reuse(t, pack, &use_e0));
   xh::MlpArgs vm{};
   bool vnet = false;
   CHK(value_step(t, &vm, &vnet));
   xh::PolicyTrainArgs pa{};
   CHK(advantages(t, vm, vnet, &pa));
+  t->pk_learned = false;
+  if (pack) CHK(pack_batch(t, &pa));
   CHK(policy_epochs(t, pa, use_e0));
   for (auto &cl : t->clip) cl.learned = cl.part != nullptr;
   if (t->upd.ring.history) CHK(upd_learn(t, e0_at_entry));

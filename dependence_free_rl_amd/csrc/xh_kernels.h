@@ -129,6 +129,11 @@ struct PolicyTrainArgs {
   // diagnostic build only (XH_PHASE_TRACE): per-wave cycle stamps at the
   // 8-wave train kernel's phase boundaries, [4 blocks][32 groups][8 waves][8]
   long long *trace;
+  // the packed batch of the 64-bin 2-D [128,128] epoch (spec8_pack_layout.h;
+  // launch_spec8_pack, once per learn()): both set = the PPO / actor-critic
+  // epoch runs policy_train_spec8_kernel's packed build over it
+  const uint8_t *pk;   // the groups' records
+  const int *pk_hdr;   // device header: env-steps and groups per class
 };
 constexpr int kTraceBlocks = 4, kTraceGroups = 32, kTraceSlots = 8;
 
@@ -592,6 +597,22 @@ hipError_t launch_policy_train_spec8_kl(const PolicyTrainArgs &a, int grid, hipS
 // (policy_spec8_e0_kernels.o); the trainer decides when they are valid
 hipError_t launch_policy_train_spec8_e0(const PolicyTrainArgs &a, const PolicyTrainE0Args &ea,
                                         int grid, hipStream_t s);
+// its packed build over the batch's distinct rows
+// (policy_spec8_pack_kernels.o; a.pk / a.pk_hdr from launch_spec8_pack)
+hipError_t launch_policy_train_spec8_pack(const PolicyTrainArgs &a, int grid, hipStream_t s);
+// the compaction pass (spec8_pack_kernels.hip, layout spec8_pack_layout.h):
+// classify, scan, write; integer work, no host synchronisation
+struct PackArgs {
+  EnvDesc env;
+  Batch b;
+  const float *adv;  // [T][N] the final advantages
+  uint8_t *pk;       // [pk_max_groups(T N)] group records
+  int *hdr;          // [kPkHdrInts]
+  uint8_t *cls;      // [T N] scratch: the env-steps' classes
+  int *blk;          // [pk_scratch_ints(T N)] scratch: per chunk of 64 env-steps
+                     // the classes' counts, then their offsets
+};
+hipError_t launch_spec8_pack(const PackArgs &a, hipStream_t s);
 // its earlier form, dW2 on the three-part bf16 split (the variant library
 // only: XH_TRAIN_KERNEL=spec8_3p)
 hipError_t launch_policy_train_spec8_3p(const PolicyTrainArgs &a, int grid, hipStream_t s);

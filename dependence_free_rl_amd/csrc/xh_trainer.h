@@ -10,6 +10,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <cstdlib>
 #include <cstring>
 #include <map>
 #include <string>
@@ -63,6 +64,14 @@ struct xh_trainer {
   uint32_t *e0_mask = nullptr;
   float *e0_p = nullptr;
   bool e0_valid = false;
+  // the packed batch of the 64-bin 2-D [128,128] PPO / actor-critic epochs
+  // (DESIGN.md §3.0e "duplicate rows", spec8_pack_layout.h), rebuilt by every
+  // learn() that runs packed: the group records, the device header, the
+  // pass's scratch (classes, per-chunk counts).  Null for any other trainer.
+  // pk_learned: the header is the last learn()'s (xh_trainer_pack_stats).
+  uint8_t *pk = nullptr, *pk_cls = nullptr;
+  int *pk_hdr = nullptr, *pk_blk = nullptr;
+  bool pk_learned = false;
   int pslab_stride = 0, vslab_stride = 0, pslab_n = 0, vslab_n = 0;
   float *pgrads = nullptr, *vgrad = nullptr;
   float *logits = nullptr, *probs = nullptr;
@@ -239,6 +248,25 @@ int timed(xh_trainer *t, const char *name, F &&launch) {
     t->events.push_back(ev);
   }
   return XH_OK;
+}
+
+// The 64-bin PPO / actor-critic epochs run over the packed batch (DESIGN.md
+// §3.0e, "duplicate rows") wherever the plain policy_train_spec8_kernel would
+// run: a trainer with the buffers, no kernel override, no ablation or phase
+// trace; XH_SP8_PACK=0 (read per rollout() / learn()) keeps the unpacked path.
+// (learn() adds: no wide slot.)
+inline bool pack_selected(const xh_trainer *t) {
+  const char *m = std::getenv("XH_SP8_PACK");
+  const char *ov = std::getenv("XH_TRAIN_KERNEL"), *ab = std::getenv("XH_ABLATE");
+  return t->pk && !(m && *m && std::atoi(m) == 0) && !(ov && *ov) &&
+         !(ab && std::atoi(ab)) && !(xh::diag_build() && std::getenv("XH_PHASE_TRACE"));
+}
+// The rollout writes epoch 0's records (relu masks, distributions: +0.05 ms
+// at config 3) only where something reads them: a learn() that does not run
+// packed, XH_E0_REUSE=2, or the update diagnostics' KL (e0_p).
+inline bool rollout_wants_e0(const xh_trainer *t) {
+  const char *m = std::getenv("XH_E0_REUSE");
+  return !pack_selected(t) || (m && std::atoi(m) == 2) || t->upd.ring.history;
 }
 
 // A slot of the batch learn() reads may hold a bin below -capacity (bins_wide)

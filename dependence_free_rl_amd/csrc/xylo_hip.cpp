@@ -16,6 +16,7 @@
 
 #include "../../include/xylo_hip.h"
 #include "spec8_e0_layout.h"
+#include "spec8_pack_layout.h"
 #include "xh_host.h"
 #include "xh_kernels.h"
 #include "xh_trainer.h"
@@ -183,8 +184,10 @@ int do_rollout(xh_trainer *t) {
   a.forced = t->use_forced ? t->forced : nullptr;
   a.qold_out = t->qold;  // KL-PPO only (nullptr otherwise)
   // PPO's epoch 0 reuses this window's masks and distributions
-  a.e0_p = t->e0_mask ? t->e0_p : nullptr;
-  a.e0_mask = t->e0_mask;
+  // (where a learn() reads them: rollout_wants_e0)
+  const bool e0w = t->e0_mask && rollout_wants_e0(t);
+  a.e0_p = e0w ? t->e0_p : nullptr;
+  a.e0_mask = e0w ? t->e0_mask : nullptr;
   t->e0_valid = false;
   // all T slots in one call (one launch where the kernel steps in registers);
   // only slot 0 can hold a wide state
@@ -356,6 +359,15 @@ int xh_trainer_create(xh_ctx *ctx, const xh_config *cfg, xh_trainer **out) {
         else
           A(&t->e0_p, T * N * (size_t)xh::sp8::kE0PBytes);
       }
+    }
+    if ((c.algo == XH_PPO || c.algo == XH_AC) && c.bins == 64 && c.dims == 2 &&
+        c.policy_h1 == 128 && c.policy_h2 == 128) {
+      // the packed batch (256 B per group: a quarter of the env-steps' count
+      // when every env-step packs, one group per env-step at worst)
+      A(&t->pk, xh::sp8::pk_max_groups(T * N) * (size_t)xh::sp8::kPkGroupBytes);
+      A(&t->pk_hdr, (size_t)xh::sp8::kPkHdrInts * 4);
+      A(&t->pk_cls, T * N);
+      A(&t->pk_blk, xh::sp8::pk_scratch_ints(T * N) * 4);
     }
     if (c.algo == XH_KLPPO) {
       A(&t->beta, 4);

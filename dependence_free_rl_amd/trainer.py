@@ -805,6 +805,16 @@ class Trainer:
         check(_lib.lib.xh_trainer_kernel_info(self.h, buf, len(buf)))
         return json.loads(buf.value.decode())
 
+    def pack_stats(self):
+        """How the last learn() ran its 64-bin policy epochs over the packed
+        batch (xh_trainer_pack_stats; synchronises -- tests and diagnostics):
+        {"packed": env-steps in 16-row segments, "unpacked": env-steps that
+        kept their 64 rows, "groups": 64-row groups per launch}."""
+        p, u, g = C.c_long(), C.c_long(), C.c_long()
+        check(_lib.lib.xh_trainer_pack_stats(self.h, C.byref(p), C.byref(u),
+                                             C.byref(g)))
+        return {"packed": p.value, "unpacked": u.value, "groups": g.value}
+
     def close(self):
         if self.h:
             check(_lib.lib.xh_trainer_destroy(self.h))

@@ -1392,6 +1392,16 @@ int xh_trainer_reset_timing(xh_trainer *t);
  * values, or null when unset. */
 int xh_trainer_kernel_info(xh_trainer *t, char *buf, size_t cap);
 
+/* Tests and diagnostics only (synchronises the stream): how the last learn()
+ * ran the 64-bin 2-D [128,128] PPO / actor-critic epochs over the packed batch
+ * (duplicate rows of an env-step computed once): env-steps that ran packed
+ * (at most 16 distinct bin states: a 16-row segment, four to a group),
+ * env-steps that ran unpacked in the same launches (a 64-row group each) and
+ * the groups each epoch's launch ran.  All three are 0 when the last learn()
+ * did not run packed (XH_SP8_PACK=0, another shape or algorithm, a kernel
+ * override, a wide slot) or none has run yet. */
+int xh_trainer_pack_stats(xh_trainer *t, long *packed, long *unpacked, long *groups);
+
 #ifdef __cplusplus
 }
 #endif

@@ -42,7 +42,8 @@ HDRS     := $(SRC)/xh_device.h $(SRC)/xh_kernels.h $(SRC)/xh_split.h \
             $(SRC)/xh_opt.h $(SRC)/xh_clip.h \
             $(SRC)/xh_diag.h $(SRC)/xh_sums.h $(SRC)/xh_seg.h $(SRC)/xh_vstore.h \
             $(SRC)/xh_digest.h $(SRC)/xh_state_blob.h $(SRC)/xh_trainer.h \
-            $(SRC)/xh_host.h $(SRC)/xh_ring.h include/xylo_hip.h
+            $(SRC)/xh_host.h $(SRC)/xh_ring.h $(SRC)/xh_logit_table.h \
+            include/xylo_hip.h
 
 # Drop-in C++20 layer (include/xylo_compat): the reference's unmodified
 # apps/bin_packing drivers (when the reference tree is present) and our own

@@ -22,6 +22,7 @@
 #include "spec8_e0_layout.h"
 #include "xh_device.h"
 #include "xh_kernels.h"
+#include "xh_logit_table.h"
 #include "xh_split.h"
 
 #include <cstdlib>
@@ -878,21 +879,77 @@ constexpr int roll_split_waves() { return S::B == 64 ? kRollWaves64 : 4; }
 template <class S>
 constexpr int roll_split_occ() { return S::B == 64 ? roll_occ(kRollWaves64) : 2; }
 
+// The logit table of the 64-bin 2-D shape (xh_logit_table.h, DESIGN.md
+// §3.0g): the partial logits (without b3) of every bin state in [-capacity,
+// capacity]^2 under each of the two items, by wave_logits_split itself on
+// synthetic rows -- call c carries states 32 c .. 32 c + 31 in both r-tiles,
+// r-tile 0 with item_a's folded bias and r-tile 1 with item_b's.  A row's
+// logit depends on its own MFMA column only and the half swap's sum is
+// commutative, so an entry holds the bits the forward gives that (state, item)
+// in any lane of any group.  Every wave of the block calls it after
+// stage_split_rollout and its barrier (the calls are dealt to the waves);
+// `out` holds lt::kEntries floats.
+template <class S>
+__device__ __forceinline__ void build_logit_table(const char *lds, float *out) {
+  static_assert(S::B == 64 && S::D == 2 && S::G == 1 && lt::kCap == kCapacity,
+                "the logit table: 64 bins, 2-D");
+  const float *lfr = reinterpret_cast<const float *>(lds + RollSplitLds<S>::F);
+  const float *const b1r[2] = {lfr + RollSplitLds<S>::B1F,
+                               lfr + RollSplitLds<S>::B1F + S::H1};
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, lr = lane & 31;
+  const int nw = blockDim.x >> 6;
+#pragma unroll 1
+  for (int c = w; c < lt::kCalls; c += nw) {
+    const int sn = lt::enum_state(c, lr);
+    const int s = sn < lt::kStates ? sn : lt::kStates - 1;
+    int b0, b1;
+    lt::state_bins(s, b0, b1);
+    RowRaw<S> cur;
+#pragma unroll
+    for (int rt = 0; rt < 2; ++rt) {
+      cur.bv[rt][0] = b0;
+      cur.bv[rt][1] = b1;
+      cur.iv[rt][0] = cur.iv[rt][1] = 0;  // folded into b1r: not read
+    }
+    float zl[2];
+    wave_logits_split<S>(lds, cur, b1r, zl);
+    if (lane < 32 && sn < lt::kStates) {
+      out[lt::entry(0, b0, b1)] = zl[0];
+      out[lt::entry(1, b0, b1)] = zl[1];
+    }
+  }
+}
+
+// Dynamic LDS of rollout_split_kernel: the staged parameters, then the table.
+template <class S, bool TAB>
+constexpr size_t roll_split_lds() {
+  return RollSplitLds<S>::bytes + (TAB ? sizeof(float) * lt::kEntries : 0);
+}
+
 // E0 (64 bins, one env per wave): every step's relu-mask record goes to
 // a.e0_mask as well (RolloutArgs; the distributions through a.qold_out).
-template <class S, bool E0 = false>
+// TAB (64 bins 2-D): the workgroup builds the logit table behind the staging,
+// and a step's logit is one LDS read indexed by the lane's bin state and item
+// instead of the forward over the group's rows.
+template <class S, bool E0 = false, bool TAB = false>
 __global__ __launch_bounds__(64 * roll_split_waves<S>(), roll_split_occ<S>()) void rollout_split_kernel(RolloutArgs a) {
   static_assert((S::B == 64 && S::NIT == 4 && S::NOT == 4) ||
                     (S::B == 32 && S::NIT == 2 && S::NOT == 2),
                 "split rollout: B=64 [128,128] or B=32 [64,64]");
   static_assert(!E0 || (S::B == 64 && S::G == 1 && S::H2 == sp8::kE0Outs),
                 "the epoch-0 records: one env of 64 bins per wave");
+  static_assert(!TAB || !E0, "the table carries no relu masks");
   extern __shared__ __attribute__((aligned(16))) float ldsf[];
   char *lds = reinterpret_cast<char *>(ldsf);
   stage_split_rollout<S>(a.params, a.env, lds);
   __syncthreads();
   const float *lfr = reinterpret_cast<const float *>(lds + RollSplitLds<S>::F);
   const float b3 = lfr[RollSplitLds<S>::B3];
+  const float *tab = reinterpret_cast<const float *>(lds + RollSplitLds<S>::bytes);
+  if constexpr (TAB) {
+    build_logit_table<S>(lds, reinterpret_cast<float *>(lds + RollSplitLds<S>::bytes));
+    __syncthreads();
+  }
   const float *b1fa = lfr + RollSplitLds<S>::B1F, *b1fb = b1fa + S::H1;
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, h = lane >> 5, lr = lane & 31;
   const int wpb = blockDim.x >> 6;
@@ -926,15 +983,24 @@ __global__ __launch_bounds__(64 * roll_split_waves<S>(), roll_split_occ<S>()) vo
     for (int t = a.t; t <= t_last; ++t) {
       // each r-tile's env's item -> its folded bias (item-table entries only)
       const float *b1r[2];
+      bool iar[2];
 #pragma unroll
       for (int rt = 0; rt < 2; ++rt) {
         bool ia = true;
 #pragma unroll
         for (int d = 0; d < S::D; ++d) ia &= cur.iv[rt][d] == a.env.item_a[d];
+        iar[rt] = ia;
         b1r[rt] = ia ? b1fa : b1fb;
       }
       float zl[2];
-      if constexpr (E0) {
+      if constexpr (TAB) {
+        // this lane's row: r-tile h (RolloutArgs::wide_seen keeps bins outside
+        // the table away from this build; the index is clamped all the same)
+        const int e = lt::entry((h ? iar[1] : iar[0]) ? 0 : 1,
+                                h ? cur.bv[1][0] : cur.bv[0][0],
+                                h ? cur.bv[1][1] : cur.bv[0][1]);
+        zl[0] = zl[1] = tab[min((unsigned)e, (unsigned)lt::kEntries - 1u)];
+      } else if constexpr (E0) {
         unsigned mbits[4];
         wave_logits_split<S, true>(lds, cur, b1r, zl, mbits);
         uint32_t *rec = a.e0_mask + ((size_t)t * a.b.N + env) * sp8::kE0Words;
@@ -2550,6 +2616,14 @@ static bool rollout_fetch_shifts(const RolloutArgs &a, int H1, int H2) {
          (B == 128 && H1 == 128 && H2 == 128);
 }
 
+// XH_ROLLOUT_TABLE=0, read per rollout, keeps the per-row forward where the
+// logit table serves (the 64-bin 2-D split rollout without the epoch-0
+// records and with no bin below -capacity about: RolloutArgs::wide_seen).
+static bool rollout_table() {
+  const char *e = std::getenv("XH_ROLLOUT_TABLE");
+  return !(e && *e && std::atoi(e) == 0);
+}
+
 // One launch: slot a.t (multi = false), or slots a.t .. a.t + a.nsteps - 1
 // by the register-stepping split kernel (multi = true).
 static hipError_t launch_rollout_one(const RolloutArgs &a, int H1, int H2,
@@ -2647,6 +2721,25 @@ static hipError_t launch_rollout_one(const RolloutArgs &a, int H1, int H2,
                                RollSplitLds<S>::bytes, s, a);                \
             return hipGetLastError();                                        \
           }                                                                  \
+          if constexpr (S::D == 2) {                                         \
+            /* the same launch shape: the table build keeps the forward's  */ \
+            /* registers (3 waves per SIMD), DESIGN.md §8                  */ \
+            if (rollout_table() && !a.wide_seen) {                           \
+              static bool tattr = false;                                     \
+              if (!tattr) {                                                  \
+                (void)hipFuncSetAttribute(                                   \
+                    (const void *)rollout_split_kernel<S, false, true>,      \
+                    hipFuncAttributeMaxDynamicSharedMemorySize,              \
+                    (int)roll_split_lds<S, true>());                         \
+                tattr = true;                                                \
+              }                                                              \
+              info->logit_table = true;                                      \
+              hipLaunchKernelGGL((rollout_split_kernel<S, false, true>),     \
+                                 dim3(wgr < wg ? wgr : wg), dim3(64 * kRW),  \
+                                 (roll_split_lds<S, true>()), s, a);         \
+              return hipGetLastError();                                      \
+            }                                                                \
+          }                                                                  \
         }                                                                    \
         hipLaunchKernelGGL(rollout_split_kernel<S>,                          \
                            dim3(wgr < wg ? wgr : wg), dim3(64 * kRW),        \
@@ -2692,6 +2785,7 @@ hipError_t launch_rollout_step(const RolloutArgs &a, int H1, int H2, int grid,
                                hipStream_t s, KernelInfo *info) {
   KernelInfo dummy;
   if (!info) info = &dummy;
+  info->logit_table = false;
   const int n = a.nsteps > 1 ? a.nsteps : 1;
   bool multi = false;
   if (a.src_slot > 0 && !rollout_fetch_shifts(a, H1, H2)) {

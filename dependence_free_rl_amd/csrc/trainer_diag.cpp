@@ -465,7 +465,10 @@ int xh_trainer_reset_timing(xh_trainer *t) {
 int xh_trainer_kernel_info(xh_trainer *t, char *buf, size_t cap) {
   return guard([&]() -> int {
     if (!t || !buf || cap == 0) return fail(XH_ERR_INVALID, "null arg");
-    const std::string js = "{\"rollout_step\": " + kernel_json(t->last_rollout) +
+    std::string roll = kernel_json(t->last_rollout);
+    roll.insert(roll.size() - 1, std::string(", \"logit_table\": ") +
+                                     (t->last_rollout.logit_table ? "true" : "false"));
+    const std::string js = "{\"rollout_step\": " + roll +
                            ", \"policy_train\": " + kernel_json(t->last_train) +
                            ", \"value\": \"" +
                            std::string(t->cfg.algo != XH_PG

@@ -72,6 +72,11 @@ struct RolloutArgs {
              // bound |bins / capacity| by 1) or an item outside the item
              // table (they fold the item into per-entry biases): the f32
              // kernels run that slot
+  int wide_seen;  // a slot 0 of this trainer has held a bin below -capacity.
+                  // Such a bin stays until an action takes it (the reset that
+                  // follows clears it), and only slot t is described by
+                  // `wide`: later slots and windows may still hold it, so the
+                  // logit table (xh_logit_table.h) is not used
   int src_slot;  // > 0 (with t == 0): slot 0 := slot src_slot first
                  // (replay_buffer::forget keeping the open trajectories), done
                  // by the register-stepping kernels as they fetch, else by
@@ -558,6 +563,9 @@ enum Math {
 struct KernelInfo {
   const char *name = nullptr;
   int math = kMathF32Mfma;
+  // launch_rollout_step: the logits came from the launch's logit table
+  // (rollout_split_kernel's table build) instead of a forward per row
+  bool logit_table = false;
 };
 hipError_t launch_rollout_step(const RolloutArgs &a, int H1, int H2, int grid,
                                hipStream_t s, KernelInfo *info = nullptr);

@@ -165,6 +165,10 @@ struct xh_trainer {
   // feature by |bins / capacity| <= 1, so a rollout step
   // or learn() that reads such a slot runs the f32-MFMA kernels instead.
   std::vector<char> bins_wide;
+  // bins_wide[0] has been set at a rollout: a bin below -capacity that no
+  // action takes survives into later slots and windows, which bins_wide does
+  // not follow (RolloutArgs::wide_seen)
+  bool wide_seen = false;
   // what the last rollout step / policy epoch launched (xh_trainer_kernel_info)
   xh::KernelInfo last_rollout, last_train;
   int timing = 0;  // 0 off, 1 every launch, XH_TIMING_TRAIN policy_train only

@@ -197,6 +197,8 @@ int do_rollout(xh_trainer *t) {
   // -capacity, or an item outside the item table (set_buffer; the split
   // rollouts fold the item into per-entry biases)
   a.wide = t->bins_wide[0] || !t->items_ok[0];
+  if (t->bins_wide[0]) t->wide_seen = true;
+  a.wide_seen = t->wide_seen;
   // diagnostics only (tests, health checks): off in the product path
   a.logits_out = t->cfg.record_last_step ? t->logits : nullptr;
   a.probs_out = t->cfg.record_last_step ? t->probs : nullptr;

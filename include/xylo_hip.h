@@ -1380,6 +1380,13 @@ int xh_trainer_reset_timing(xh_trainer *t);
  *   printed against) and adds "dw2_math": "f16_pair_per_feature_scale",
  *   "issued_math": "f16_pair_train", "issued_products_per_f32_product": 7/3
  *   and "issued_peak_tflops": 2500 / (7/3), what it actually issues.
+ *   The "rollout_step" entry also carries "logit_table": true when the last
+ *   rollout launch read its logits from the launch's table of (bin state,
+ *   item) logits instead of running the forward per row (rollout_split_kernel
+ *   at 64 bins, 2-D, [128,128]; off with XH_ROLLOUT_TABLE=0, for a launch
+ *   that writes PPO's epoch-0 records, and for a trainer whose slot 0 has
+ *   held a bin below -capacity); the same kernel name and arithmetic either
+ *   way, and the same bits.
  *   V ="vnet_bf16" (the Fin -> 64 -> 32 -> 1 value net on exact bf16
  *   splits: two forwards and one fused backward per update, B*D % 16 == 0,
  *   B*D + D < 416), "mlp3_fused" (the same net on the f32 fused kernels:

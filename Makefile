@@ -18,6 +18,7 @@ OBJS     := $(SRC)/policy_kernels.o $(SRC)/value_kernels.o \
             $(SRC)/policy_spec8_kernels.o $(SRC)/policy_spec8_kl_kernels.o \
             $(SRC)/policy_spec8_e0_kernels.o \
             $(SRC)/policy_spec8_pack_kernels.o $(SRC)/spec8_pack_kernels.o \
+            $(SRC)/policy_spec8_tab_kernels.o $(SRC)/spec8_table_kernels.o \
             $(SRC)/policy_spec4_kernels.o \
             $(SRC)/policy_split8wh_kernels.o $(SRC)/policy_split8wh_kl_kernels.o \
             $(SRC)/policy_split8x_kernels.o $(SRC)/policy_split8x_kl_kernels.o \
@@ -38,7 +39,7 @@ VARIANT_KERNELS := policy_split_kernels policy_split128_kernels \
 HDRS     := $(SRC)/xh_device.h $(SRC)/xh_kernels.h $(SRC)/xh_split.h \
             $(SRC)/xh_img16.h \
             $(SRC)/spec8_layout.h $(SRC)/spec8_e0_layout.h $(SRC)/spec8_l1_layout.h \
-            $(SRC)/spec8_pack_layout.h \
+            $(SRC)/spec8_pack_layout.h $(SRC)/spec8_table_layout.h \
             $(SRC)/xh_opt.h $(SRC)/xh_clip.h \
             $(SRC)/xh_diag.h $(SRC)/xh_sums.h $(SRC)/xh_seg.h $(SRC)/xh_vstore.h \
             $(SRC)/xh_digest.h $(SRC)/xh_state_blob.h $(SRC)/xh_trainer.h \
@@ -102,6 +103,10 @@ $(SRC)/policy_spec8_e0_kernels.o: $(SRC)/policy_spec8_kernels.hip $(HDRS)
 # once; the same kernel's packed build)
 $(SRC)/policy_spec8_pack_kernels.o: $(SRC)/policy_spec8_kernels.hip $(HDRS)
 	$(HIPCC) $(HIPFLAGS) $(FLAGS_policy_spec8_kernels) -DXH_SP8_PACK_TU=1 -c $< -o $@
+# the same kernel over the table batch, forward and backward (the epoch on the
+# table)
+$(SRC)/policy_spec8_tab_kernels.o: $(SRC)/policy_spec8_kernels.hip $(HDRS)
+	$(HIPCC) $(HIPFLAGS) $(FLAGS_policy_spec8_kernels) -DXH_SP8_TAB_TU=1 -c $< -o $@
 $(SRC)/policy_split4h_kl_kernels.o: $(SRC)/policy_split4h_kernels.hip $(HDRS)
 	$(HIPCC) $(HIPFLAGS) $(FLAGS_policy_split4h_kernels) -DXH_4H_KL_TU=1 \
 	    -mllvm -pragma-unroll-threshold=200000 -c $< -o $@

@@ -94,6 +94,7 @@
 #include "spec8_l1_layout.h"
 #include "spec8_layout.h"
 #include "spec8_pack_layout.h"
+#include "spec8_table_layout.h"
 #include "xh_device.h"
 #include "xh_img16.h"
 #include "xh_kernels.h"
@@ -204,7 +205,29 @@
 #if XH_SP8_PACK_TU && (XH_SP8_KL_TU || XH_SP8_E0_TU || XH_SP8_DW2_3P || XH_SP8_ABLATE)
 #error "the packed build is the plain PPO / actor-critic kernel's"
 #endif
-#if XH_SP8_KL_TU || XH_SP8_PACK_TU
+// XH_SP8_TAB_TU=1 (policy_spec8_tab_kernels.o): the same kernel over the TABLE
+// BATCH (spec8_table_layout.h, DESIGN.md §3.0e "the epoch on the table"): ten
+// static groups that hold each of the lt::kEntries (bin state, item) points
+// once, staged as the packed build stages its groups, in two instantiations:
+//   forward   layer 1, layer 2 and the w3 dot of each row; the rows' logits
+//             (partial sums + b3, the packed build's own expression) go to
+//             PolicyTrainTabArgs::logits.  No softmax, no backward, no slab.
+//   backward  the softmax stages are replaced by g = G[the row's entry]
+//             (PolicyTrainTabArgs::G: the sum of the loss gradient over the
+//             batch's rows in that state, spec8_table_kernels.hip); behind g
+//             the plain build line for line.  PolicyTrainArgs::g_bound is the
+//             bound on |G| here (the reduce's max_s |G_s|).
+// The grid is at most tb::kGroups workgroups.
+#ifndef XH_SP8_TAB_TU
+#define XH_SP8_TAB_TU 0
+#endif
+#if XH_SP8_TAB_TU && \
+    (XH_SP8_KL_TU || XH_SP8_E0_TU || XH_SP8_PACK_TU || XH_SP8_DW2_3P || XH_SP8_ABLATE)
+#error "the table build is the plain PPO / actor-critic kernel's"
+#endif
+// the builds whose groups are records of spec8_pack_layout.h
+#define SP8_PK (XH_SP8_PACK_TU || XH_SP8_TAB_TU)
+#if XH_SP8_KL_TU || SP8_PK
 #define SP8KLP(...) __VA_ARGS__
 #else
 #define SP8KLP(...)
@@ -355,7 +378,7 @@ constexpr int F_W3 = F_B2 + kH;    // [128] w3 / S2 (unscales the partial logits
 constexpr int F_Z = F_W3 + kH;     // [64 rows][4 matrix waves] partial logits
 constexpr int F_G = F_Z + 256;     // [2 slots][3][64] g, g x0, g x1 of a group
 constexpr int F_X = F_G + 384;     // [4 slots][2 dims][64 rows] bins / 8
-#if XH_SP8_PACK_TU
+#if SP8_PK
 // (packed build: a slot holds its group's four segment records [chosen row,
 // pold, adv, env-step], the group's "item is item_a" in place of segment 0's
 // env-step index)
@@ -374,7 +397,7 @@ constexpr int F_FU = F_FS + kH;    // [128] 2^-15 / s_i (the masks' 2^15 with it
 constexpr int F_Q = F_FU + kH;     // [4 slots][64 bins] old distribution q
 constexpr int F_KL = F_Q + 256;    // [4 matrix waves][32 lanes] KL sums (doubles)
 constexpr int F_END = F_KL + 256;
-#elif XH_SP8_PACK_TU
+#elif SP8_PK
 constexpr int F_CNT = F_FU + kH;   // [4 slots][64 rows] the rows' multiplicities
 constexpr int F_END = F_CNT + 256;
 #else
@@ -413,6 +436,10 @@ __global__ __launch_bounds__(kThreads, 2) void policy_train_spec8_e0_kernel(Poli
                                                                             PolicyTrainE0Args ea) {
 #elif XH_SP8_PACK_TU
 __global__ __launch_bounds__(kThreads, 2) void policy_train_spec8_pk_kernel(PolicyTrainArgs a) {
+#elif XH_SP8_TAB_TU
+template <bool kTabFwd>
+__global__ __launch_bounds__(kThreads, 2) void policy_train_spec8_tab_kernel(PolicyTrainArgs a,
+                                                                             PolicyTrainTabArgs ta) {
 #else
 __global__ __launch_bounds__(kThreads, 2) void policy_train_spec8_kernel(PolicyTrainArgs a) {
 #endif
@@ -435,6 +462,10 @@ __global__ __launch_bounds__(kThreads, 2) void policy_train_spec8_kernel(PolicyT
   const int pk_ga = __builtin_amdgcn_readfirstlane(a.pk_hdr[kPkGA]);
   const int pk_np = pk_ga + __builtin_amdgcn_readfirstlane(a.pk_hdr[kPkGB]);
   const int pk_ua = __builtin_amdgcn_readfirstlane(a.pk_hdr[kPkUA]);  // wide, item_a
+#elif XH_SP8_TAB_TU
+  // the table batch: item_a's groups, then item_b's, none wide
+  constexpr int ngroups = tb::kGroups, pk_ga = tb::kGroupsPerItem, pk_np = tb::kGroups,
+                pk_ua = 0;
 #else
   const int ngroups = a.b.T * a.b.N;
 #endif
@@ -445,7 +476,7 @@ __global__ __launch_bounds__(kThreads, 2) void policy_train_spec8_kernel(PolicyT
                      ? ((int)blockIdx.x & 7) * ((int)gridDim.x >> 3) + ((int)blockIdx.x >> 3)
                      : (int)blockIdx.x;
   const int J = b0 < ngroups ? (ngroups - b0 + (int)gridDim.x - 1) / (int)gridDim.x : 0;
-#if XH_SP8_PACK_TU
+#if SP8_PK
   if (J == 0) {  // (the grid is sized by env-steps: no group left for this one)
     float *z = a.slab + (size_t)blockIdx.x * a.slab_stride;
     for (int e = tid; e < a.slab_stride; e += kThreads) z[e] = 0.0f;
@@ -669,7 +700,7 @@ __global__ __launch_bounds__(kThreads, 2) void policy_train_spec8_kernel(PolicyT
       }
     };
 #endif
-#if XH_SP8_PACK_TU
+#if SP8_PK
     // (packed build: the group's record, spec8_pack_layout.h -- the 64 rows'
     // bins as above; lanes 0-15 the four segment records' dwords, lanes 16-31
     // the 64 counts, four bytes each; the item follows from the group's class)
@@ -893,7 +924,7 @@ __global__ __launch_bounds__(kThreads, 2) void policy_train_spec8_kernel(PolicyT
       float q0, q1;  // the old distribution of rows l31, 32 + l31 (pc, gc:
                      // the probability-space gradients; po: the row counts)
 #endif
-#if XH_SP8_PACK_TU
+#if SP8_PK
       // (packed build) the records [chosen row, pold, adv, -] of the segments
       // rows l31 and 32 + l31 lie in, the rows' counts, and the second row's
       // se / pc / gc (se, pc, gc: the first row's)
@@ -993,11 +1024,59 @@ __global__ __launch_bounds__(kThreads, 2) void policy_train_spec8_kernel(PolicyT
       }
     };
 #endif
+#if XH_SP8_TAB_TU
+    // the table build's stages 0 .. 5: a lane's rows l31 and 32 + l31 of group
+    // tindex(gi) carry the table entries tb::row_entry (-1: a tail row).
+    // forward: their logits -> ta.logits (matrix wave 0, lane half 0; not for
+    // a look-ahead group past the end, which repeats the last one); backward:
+    // g = ta.G[entry], loaded in stage 0 and used in stage 5.
+    auto tab_stage = [&](int gi, bool acc, int stage) {
+      const int rs = gi & 3;
+      const int g = (int)tindex(gi);
+      const int e0 = tb::row_entry(g, l31), e1 = tb::row_entry(g, 32 + l31);
+      switch (stage) {
+        case 0: {
+          if (kTabFwd) {
+            sm.b3 = lf[F_B3];
+            sm.z0 = lds4v(lf + F_Z + 4 * l31);
+            sm.z1 = lds4v(lf + F_Z + 4 * (32 + l31));
+          } else {
+            sm.ex0 = e0 >= 0 ? ta.G[e0] : 0.0f;
+            sm.ex1 = e1 >= 0 ? ta.G[e1] : 0.0f;
+            if (s == 0) {
+              const float *xr = lf + F_X + rs * 128 + opaque(l31);
+              sm.x = f32x4{xr[0], xr[32], xr[64], xr[96]};
+            }
+          }
+          break;
+        }
+        case 1:
+          if (kTabFwd && acc && s == 0 && h == 0) {
+            if (e0 >= 0)
+              ta.logits[e0] = ((sm.z0[0] + sm.z0[1]) + (sm.z0[2] + sm.z0[3])) + sm.b3;
+            if (e1 >= 0)
+              ta.logits[e1] = ((sm.z1[0] + sm.z1[1]) + (sm.z1[2] + sm.z1[3])) + sm.b3;
+          }
+          break;
+        case 5:
+          gz[0] = kTabFwd ? 0.0f : sm.ex0;
+          gz[1] = kTabFwd ? 0.0f : sm.ex1;
+          break;
+        default:
+          break;
+      }
+    };
+#endif
     auto softmax_stage = [&](int gi, int gpar, bool acc, int stage) {
       const int rs = gi & 3;
 #if XH_SP8_PACK_TU
       if (stage < 6) {
         pack_stage(gi, stage);
+        return;
+      }
+#elif XH_SP8_TAB_TU
+      if (stage < 6) {
+        tab_stage(gi, acc, stage);
         return;
       }
 #endif
@@ -1312,8 +1391,14 @@ __global__ __launch_bounds__(kThreads, 2) void policy_train_spec8_kernel(PolicyT
     partials_tail(c[0], 0);
     partials_tail(c[1], 1);
     __syncthreads();  // P3                       (vector: L1(1))
+#if XH_SP8_TAB_TU
+    // (forward: SM is the logits' store, stages 0 and 1 in slots 0 and 3)
+#pragma unroll
+    for (int k = 0; k < (kTabFwd ? 4 : 48); ++k) b_task(c, 0, 0, true, k);
+#else
 #pragma unroll
     for (int k = 0; k < 48; ++k) b_task(c, 0, 0, true, k);
+#endif
 #endif
     __syncthreads();  // P4
 #if XH_SP8_E0_TU
@@ -1405,6 +1490,12 @@ __global__ __launch_bounds__(kThreads, 2) void policy_train_spec8_kernel(PolicyT
       // masks in its MFMA slots
       if (s == 0) stage_store(raw, (j + 3) & 3 SP8KLP(, j + 3));
       const bool acc = j + 1 < J;
+#if XH_SP8_TAB_TU
+      if (kTabFwd) {  // no backward: group j+1's logits only
+#pragma unroll
+        for (int k = 0; k < 4; ++k) b_task(c, j + 1, 1 - par, acc, k);
+      } else
+#endif
       if (SP8_RUN(1 | 16))
         dw2(par, [&](int k) { b_task(c, j + 1, 1 - par, acc, k); });
       __syncthreads();
@@ -1428,6 +1519,9 @@ __global__ __launch_bounds__(kThreads, 2) void policy_train_spec8_kernel(PolicyT
       __syncthreads();
       if (s == 0 && l == 0) a.kl_part[blockIdx.x] = (kd[0] + kd[1]) + (kd[2] + kd[3]);
     }
+#endif
+#if XH_SP8_TAB_TU
+    if (kTabFwd) return;  // (no gradient, no slab; the vector waves return too)
 #endif
     // ---- write-out (every entry has exactly one producing lane)
 #if XH_SP8_DW2_3P
@@ -2000,6 +2094,14 @@ __global__ __launch_bounds__(kThreads, 2) void policy_train_spec8_kernel(PolicyT
 #else
     auto period = [&](int j, auto P) {
       constexpr int par = decltype(P)::value;
+#if XH_SP8_TAB_TU
+      if (kTabFwd) {  // no backward: the H1 image of group j+2 only
+        __syncthreads();  // A(j)
+        layer1(j + 2);
+        __syncthreads();  // B(j)
+        return;
+      }
+#endif
       if (SP8_RUN(2 | 4)) dh_gh(j, par, hk, dh);
       __syncthreads();  // A(j)
 #if SP8_DHB
@@ -2018,6 +2120,9 @@ __global__ __launch_bounds__(kThreads, 2) void policy_train_spec8_kernel(PolicyT
 
 #if XH_SP8_KL_TU
     __syncthreads();  // the matrix waves' KL sum
+#endif
+#if XH_SP8_TAB_TU
+    if (kTabFwd) return;
 #endif
     __syncthreads();  // the matrix waves' dW3 partials
     // ---- write-out: dW1 / db1 of feature fi (the two lane halves hold row
@@ -2085,6 +2190,28 @@ hipError_t launch_policy_train_spec8_pack(const PolicyTrainArgs &a, int grid, hi
   }
   hipLaunchKernelGGL(sp8::policy_train_spec8_pk_kernel, dim3(grid), dim3(sp8::kThreads),
                      sp8::kLds, s, a);
+  return hipGetLastError();
+}
+#elif XH_SP8_TAB_TU
+hipError_t launch_policy_train_spec8_tab(const PolicyTrainArgs &a, const PolicyTrainTabArgs &ta,
+                                         int grid, hipStream_t s) {
+  // (both instantiations run the prologue, which reads the bound)
+  if (!a.pk || !a.g_bound || grid < 1 || grid > tb::kGroups || (ta.forward ? !ta.logits : !ta.G))
+    return hipErrorInvalidValue;
+  static bool attr = false;
+  if (!attr) {
+    (void)hipFuncSetAttribute((const void *)sp8::policy_train_spec8_tab_kernel<true>,
+                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)sp8::kLds);
+    (void)hipFuncSetAttribute((const void *)sp8::policy_train_spec8_tab_kernel<false>,
+                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)sp8::kLds);
+    attr = true;
+  }
+  if (ta.forward)
+    hipLaunchKernelGGL(sp8::policy_train_spec8_tab_kernel<true>, dim3(grid), dim3(sp8::kThreads),
+                       sp8::kLds, s, a, ta);
+  else
+    hipLaunchKernelGGL(sp8::policy_train_spec8_tab_kernel<false>, dim3(grid),
+                       dim3(sp8::kThreads), sp8::kLds, s, a, ta);
   return hipGetLastError();
 }
 #elif XH_SP8_DW2_3P

@@ -32,7 +32,16 @@
 //                                  in the same launch.  Epoch 0 runs packed
 //                                  too (XH_E0_REUSE=2 keeps the e0 kernel).  A
 //                                  kernel override, a wide slot, ablation or a
-//                                  phase trace come through this file unpacked
+//                                  phase trace come through this file unpacked.
+//                                  A packed learn() of a trainer that has held
+//                                  no bin below -capacity runs its epochs ON
+//                                  THE TABLE (trainer_learn.cpp, decide_table;
+//                                  XH_TRAIN_TABLE=0 keeps the packed launches):
+//                                  the kernel's table build
+//                                  (policy_spec8_tab_kernels.o) forward and
+//                                  backward over the 578 (bin state, item)
+//                                  points, spec8_table_kernels.hip's streaming
+//                                  pass over the packed batch between them
 //   128 bins, 3-D, [128,128] (config 5)      policy_train_split8x_kernel
 //                                  (KL-PPO: policy_train_split8x_kl_kernel)
 //   32 bins, 1-D, [64,64] (config 2)         policy_train_split4h_kernel

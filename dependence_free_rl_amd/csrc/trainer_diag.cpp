@@ -13,6 +13,7 @@
 
 #include "../../include/xylo_hip.h"
 #include "spec8_pack_layout.h"
+#include "spec8_table_layout.h"
 #include "xh_host.h"
 #include "xh_kernels.h"
 #include "xh_trainer.h"
@@ -498,6 +499,22 @@ int xh_trainer_pack_stats(xh_trainer *t, long *packed, long *unpacked, long *gro
     *packed = (long)h[xh::sp8::kPkNA] + h[xh::sp8::kPkNB];
     *unpacked = (long)h[xh::sp8::kPkUA] + h[xh::sp8::kPkUB];
     *groups = h[xh::sp8::kPkGroups];
+    return XH_OK;
+  });
+}
+
+int xh_trainer_table_stats(xh_trainer *t, int *ran, long *out_of_domain, long *groups) {
+  return guard([&]() -> int {
+    if (!t || !ran || !out_of_domain || !groups) return fail(XH_ERR_INVALID, "null arg");
+    *ran = 0;
+    *out_of_domain = *groups = 0;
+    if (!t->tab_ood || !t->tab_learned) return XH_OK;
+    int ood = 0;
+    HIPCHK(hipMemcpyAsync(&ood, t->tab_ood, sizeof(ood), hipMemcpyDeviceToHost, t->ctx->stream));
+    HIPCHK(hipStreamSynchronize(t->ctx->stream));
+    *ran = 1;
+    *out_of_domain = ood;
+    *groups = xh::tb::kGroups;
     return XH_OK;
   });
 }

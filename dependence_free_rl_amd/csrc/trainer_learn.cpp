@@ -14,6 +14,7 @@
 
 #include "../../include/xylo_hip.h"
 #include "spec8_pack_layout.h"
+#include "spec8_table_layout.h"
 #include "xh_host.h"
 #include "xh_kernels.h"
 #include "xh_trainer.h"
@@ -199,6 +200,36 @@ bool decide_pack(const xh_trainer *t) {
   return pack_selected(t) && !batch_wide(t);
 }
 
+// The packed learn()'s epochs on the table ("the epoch on the
+// table"): the rollout table's own condition on top of decide_pack -- no slot
+// of this trainer has held a bin below -capacity, which has no table entry.
+// XH_TRAIN_TABLE=0 (read per learn()) keeps the packed launches.
+bool decide_table(const xh_trainer *t, bool pack) {
+  const char *m = std::getenv("XH_TRAIN_TABLE");
+  return pack && t->tab_pk && (t->cfg.algo == XH_PPO || t->cfg.algo == XH_AC) &&
+         !t->wide_seen && !batch_wide(t) && !(m && *m && std::atoi(m) == 0);
+}
+
+// One epoch on the table: the table batch's forward -> the entries' logits;
+// the streaming pass over the packed batch -> G and max |G|; the table batch's
+// backward weighted by G -> `grid` slabs.
+hipError_t table_epoch(xh_trainer *t, const xh::PolicyTrainArgs &pa, int grid, bool count,
+                       hipStream_t s) {
+  xh::PolicyTrainArgs ta = pa;
+  ta.pk = t->tab_pk;
+  hipError_t e = xh::launch_policy_train_spec8_tab(
+      ta, xh::PolicyTrainTabArgs{t->tab_logits, nullptr, 1}, grid, s);
+  if (e != hipSuccess) return e;
+  const xh::TableStreamArgs sa{pa.pk,       pa.pk_hdr,   t->tab_logits,
+                               pa.algo,     pa.clip_eps, t->tab_part,
+                               t->tab_G,    t->tab_gmax, count ? t->tab_ood : nullptr};
+  e = xh::launch_table_stream(sa, t->pslab_n, s);
+  if (e != hipSuccess) return e;
+  ta.g_bound = t->tab_gmax;
+  return xh::launch_policy_train_spec8_tab(ta, xh::PolicyTrainTabArgs{nullptr, t->tab_G, 0},
+                                           grid, s);
+}
+
 // the compaction pass: once per learn(), behind the final advantages
 int pack_batch(xh_trainer *t, xh::PolicyTrainArgs *pa) {
   hipStream_t s = t->ctx->stream;
@@ -334,7 +365,7 @@ int advantages(xh_trainer *t, xh::MlpArgs vm, bool vnet,
 
 // optimize_action: k policy steps (policy_gradient.h:297-307); KL-PPO adapts
 // beta from the job's mean KL after each of them.
-int policy_epochs(xh_trainer *t, xh::PolicyTrainArgs &pa, bool use_e0) {
+int policy_epochs(xh_trainer *t, xh::PolicyTrainArgs &pa, bool use_e0, bool table) {
   hipStream_t s = t->ctx->stream;
   const xh_config &c = t->cfg;
   pa.env = t->env;
@@ -356,14 +387,25 @@ int policy_epochs(xh_trainer *t, xh::PolicyTrainArgs &pa, bool use_e0) {
     pa.kl_part = t->kl_part;
     // end_list / n_end / n_open: built before the value step
   }
+  bool counted = false;  // the table's out-of-domain rows: once per learn()
   for (int e = 0; e < c.epochs; ++e) {
     float *g = t->pgrads + (size_t)e * t->np;
+    int nslab = t->pslab_n;
     if (e == 0 && use_e0 && !pa.wide && !pa.ablate && !pa.trace) {
       // (the later epochs' launches report the kernel: last_train)
       const xh::PolicyTrainE0Args ea{t->e0_p, t->e0_mask};
       CHK(timed(t, "policy_train", [&]() {
         return xh::launch_policy_train_spec8_e0(pa, ea, t->pslab_n, s);
       }));
+    } else if (pa.pk && !pa.trace && table) {
+      // the epoch on the table: its launches in one interval; the arithmetic
+      // behind g is the same kernel's, and it reports as the plain one
+      t->last_train.name = "policy_train_spec8_kernel";
+      t->last_train.math = xh::kMathSplitTrainF16Pair;
+      nslab = t->pslab_n < xh::tb::kGroups ? t->pslab_n : xh::tb::kGroups;
+      CHK(timed(t, "policy_train", [&]() { return table_epoch(t, pa, nslab, !counted, s); }));
+      counted = true;
+      t->tab_learned = true;
     } else if (pa.pk && !pa.trace) {
       // the same kernel's packed build: it reports as the plain one
       t->last_train.name = "policy_train_spec8_kernel";
@@ -379,7 +421,7 @@ int policy_epochs(xh_trainer *t, xh::PolicyTrainArgs &pa, bool use_e0) {
     }
     if (pa.trace) CHK(phase_trace_report(t, &pa));  // first epoch only
     // the optimizer step does not read beta: it may precede the KL update
-    CHK(reduce_and_step(t, XH_POLICY, e, t->pslab, t->pslab_n,
+    CHK(reduce_and_step(t, XH_POLICY, e, t->pslab, nslab,
                         t->pslab_stride, t->np, g, t->pp));
     if (kl) {  // mean KL over the job's rows -> beta for the next epoch
       CHK(timed(t, "kl", [&]() {
@@ -413,7 +455,10 @@ int do_learn(xh_trainer *t) {
   CHK(advantages(t, vm, vnet, &pa));
   t->pk_learned = false;
   if (pack) CHK(pack_batch(t, &pa));
-  CHK(policy_epochs(t, pa, use_e0));
+  t->tab_learned = false;
+  const bool table = decide_table(t, pack);
+  if (table) HIPCHK(hipMemsetAsync(t->tab_ood, 0, sizeof(int), t->ctx->stream));
+  CHK(policy_epochs(t, pa, use_e0, table));
   for (auto &cl : t->clip) cl.learned = cl.part != nullptr;
   if (t->upd.ring.history) CHK(upd_learn(t, e0_at_entry));
   if (t->stats.ring.history) CHK(stats_learn(t));

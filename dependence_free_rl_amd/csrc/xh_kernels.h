@@ -621,6 +621,37 @@ struct PackArgs {
                      // the classes' counts, then their offsets
 };
 hipError_t launch_spec8_pack(const PackArgs &a, hipStream_t s);
+// The epoch on the table (spec8_table_layout.h): the per-bin
+// net's activations depend on the table entry (bin state, item) alone and
+// every parameter gradient is linear in the rows' loss gradient g, so an epoch
+// is a forward over the table batch, one streaming pass over the packed batch
+// that sums g per entry, and a backward over the table batch weighted by the
+// sums.
+// the kernel's table build (policy_spec8_tab_kernels.o), a.pk = the table
+// batch, grid <= tb::kGroups; backward: a.g_bound = the bound on |G|
+struct PolicyTrainTabArgs {
+  float *logits;   // [lt::kEntries] forward: the entries' logits (out)
+  const float *G;  // [lt::kEntries] backward: the sums of g per entry
+  int forward;
+};
+hipError_t launch_policy_train_spec8_tab(const PolicyTrainArgs &a, const PolicyTrainTabArgs &ta,
+                                         int grid, hipStream_t s);
+// the streaming pass and its reduce (spec8_table_kernels.hip): per env-step
+// of the packed batch the count-weighted softmax over the table's logits and
+// the PPO / actor-critic loss gradient per distinct state, summed per entry;
+// no float atomic, every sum in a fixed order
+struct TableStreamArgs {
+  const uint8_t *pk;    // the packed batch (launch_spec8_pack)
+  const int *pk_hdr;
+  const float *logits;  // [lt::kEntries]
+  int algo;             // kPPO / kAC
+  float clip_eps;
+  double *part;         // [grid][lt::kEntries] scratch: the workgroups' sums
+  float *G;             // [lt::kEntries] out
+  float *gmax;          // out: max_s |G_s|
+  int *ood;             // += rows whose state lies outside the table (null: not counted)
+};
+hipError_t launch_table_stream(const TableStreamArgs &a, int grid, hipStream_t s);
 // its earlier form, dW2 on the three-part bf16 split (the variant library
 // only: XH_TRAIN_KERNEL=spec8_3p)
 hipError_t launch_policy_train_spec8_3p(const PolicyTrainArgs &a, int grid, hipStream_t s);

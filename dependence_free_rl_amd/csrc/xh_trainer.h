@@ -72,6 +72,17 @@ struct xh_trainer {
   uint8_t *pk = nullptr, *pk_cls = nullptr;
   int *pk_hdr = nullptr, *pk_blk = nullptr;
   bool pk_learned = false;
+  // the epoch on the table (spec8_table_layout.h), beside the
+  // packed batch: the static table batch (written once, at creation), the
+  // entries' logits, the per-entry sums G of the loss gradient with their
+  // bound max |G|, the streaming pass's per-workgroup sums, and the count of
+  // rows outside the table.  tab_learned: the last learn() ran its epochs on
+  // the table (xh_trainer_table_stats).
+  uint8_t *tab_pk = nullptr;
+  float *tab_logits = nullptr, *tab_G = nullptr, *tab_gmax = nullptr;
+  double *tab_part = nullptr;
+  int *tab_ood = nullptr;
+  bool tab_learned = false;
   int pslab_stride = 0, vslab_stride = 0, pslab_n = 0, vslab_n = 0;
   float *pgrads = nullptr, *vgrad = nullptr;
   float *logits = nullptr, *probs = nullptr;

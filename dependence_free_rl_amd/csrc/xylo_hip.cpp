@@ -17,6 +17,7 @@
 #include "../../include/xylo_hip.h"
 #include "spec8_e0_layout.h"
 #include "spec8_pack_layout.h"
+#include "spec8_table_layout.h"
 #include "xh_host.h"
 #include "xh_kernels.h"
 #include "xh_trainer.h"
@@ -370,6 +371,20 @@ int xh_trainer_create(xh_ctx *ctx, const xh_config *cfg, xh_trainer **out) {
       A(&t->pk_hdr, (size_t)xh::sp8::kPkHdrInts * 4);
       A(&t->pk_cls, T * N);
       A(&t->pk_blk, xh::sp8::pk_scratch_ints(T * N) * 4);
+      // the epoch on the table: the table batch, the logits, G and its bound,
+      // the streaming pass's sums per workgroup
+      A(&t->tab_pk, (size_t)xh::tb::kBytes);
+      A(&t->tab_logits, (size_t)xh::lt::kEntries * 4);
+      A(&t->tab_G, (size_t)xh::lt::kEntries * 4);
+      A(&t->tab_gmax, 4);
+      A(&t->tab_part, (size_t)t->pslab_n * xh::lt::kEntries * 8);
+      A(&t->tab_ood, 4);
+      if (st == XH_OK) {
+        std::vector<uint8_t> tbh((size_t)xh::tb::kBytes);
+        for (int g = 0; g < xh::tb::kGroups; ++g)
+          xh::tb::fill_group(g, tbh.data() + (size_t)g * xh::sp8::kPkGroupBytes);
+        st = copy_ok(copy_to_device(t->tab_pk, tbh.data(), tbh.size(), ctx->stream));
+      }
     }
     if (c.algo == XH_KLPPO) {
       A(&t->beta, 4);

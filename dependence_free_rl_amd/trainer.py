@@ -815,6 +815,16 @@ class Trainer:
                                              C.byref(g)))
         return {"packed": p.value, "unpacked": u.value, "groups": g.value}
 
+    def table_stats(self):
+        """Whether the last learn() ran its packed epochs on the table of
+        (bin state, item) points (xh_trainer_table_stats; synchronises -- tests
+        and diagnostics): {"ran": bool, "out_of_domain": rows of the packed
+        batch outside the table, "groups": groups of the table batch}."""
+        r, o, g = C.c_int(), C.c_long(), C.c_long()
+        check(_lib.lib.xh_trainer_table_stats(self.h, C.byref(r), C.byref(o),
+                                              C.byref(g)))
+        return {"ran": bool(r.value), "out_of_domain": o.value, "groups": g.value}
+
     def close(self):
         if self.h:
             check(_lib.lib.xh_trainer_destroy(self.h))

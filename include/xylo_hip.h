@@ -1409,6 +1409,17 @@ int xh_trainer_kernel_info(xh_trainer *t, char *buf, size_t cap);
  * override, a wide slot) or none has run yet. */
 int xh_trainer_pack_stats(xh_trainer *t, long *packed, long *unpacked, long *groups);
 
+/* Tests and diagnostics only (synchronises the stream): whether the last
+ * learn() ran its packed epochs ON THE TABLE -- a forward over the 578 (bin
+ * state, item) points, one streaming pass over the packed batch that sums the
+ * loss gradient per point, a backward over the 578 points -- (*ran = 1), the
+ * rows of its packed batch whose state lay outside the table (clamped to the
+ * nearest entry; 0 wherever the gate holds) and the groups of the table batch
+ * each table launch ran.  All three are 0 when it did not (XH_TRAIN_TABLE=0,
+ * no packed learn(), KL-PPO, a slot of this trainer has held a bin below
+ * -capacity) or none has run yet. */
+int xh_trainer_table_stats(xh_trainer *t, int *ran, long *out_of_domain, long *groups);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,7 +12,8 @@ HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -Wall \
 OBJS     := $(SRC)/policy_kernels.o $(SRC)/value_kernels.o \
             $(SRC)/env_kernels.o $(SRC)/kl_kernels.o \
             $(SRC)/heuristic_kernels.o $(SRC)/dense_kernels.o \
-            $(SRC)/pg_kernels.o $(SRC)/venv_kernels.o $(SRC)/venv_learn_kernels.o \
+            $(SRC)/pg_kernels.o $(SRC)/venv_kernels.o $(SRC)/venv_gen_kernels.o \
+            $(SRC)/venv_learn_kernels.o \
             $(SRC)/venv_loss_kernels.o $(SRC)/venv_episode_kernels.o \
             $(SRC)/value_net_kernels.o \
             $(SRC)/policy_spec8_kernels.o $(SRC)/policy_spec8_kl_kernels.o \
@@ -83,6 +84,12 @@ FLAGS_policy_spec4_kernels := -mllvm -amdgpu-mfma-vgpr-form -fno-slp-vectorize
 
 $(SRC)/%.o: $(SRC)/%.hip $(HDRS)
 	$(HIPCC) $(HIPFLAGS) $(FLAGS_$*) -c $< -o $@
+
+# the venv kernels' general instantiations (xh_item_set: K items, per-dim
+# capacities), an object of their own so that the two sets of act kernels
+# compile side by side
+$(SRC)/venv_gen_kernels.o: $(SRC)/venv_kernels.hip $(HDRS)
+	$(HIPCC) $(HIPFLAGS) -DXH_VENV_GEN_TU=1 -c $< -o $@
 
 # the KL-PPO builds of the 64-, 128- and 32-bin train kernels (their own objects:
 # the full unroll of their task lambdas needs a threshold the other builds

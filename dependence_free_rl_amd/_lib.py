@@ -132,6 +132,24 @@ class VenvLossExt(C.Structure):
         ("ext_stats", C.c_void_p)]
 
 
+ITEMS_MAX = 16
+
+
+class ItemSet(C.Structure):
+    """Mirror of xh_item_set."""
+    _fields_ = [
+        ("num_items", C.c_int), ("capacity", C.c_int * 4),
+        ("item", (C.c_int * 4) * ITEMS_MAX),
+        ("weight", C.c_double * ITEMS_MAX)]
+
+
+# calls an A/B library from before them (XH_LIB_PATH) may lack; the wrappers
+# that need one raise
+_AB_OPTIONAL = ("xh_trainer_table_stats", "xh_item_set_default",
+                "xh_item_set_thresholds", "xh_venv_create_ex",
+                "xh_venv_set_item_set", "xh_venv_get_item_set")
+
+
 def _load():
     if not os.path.exists(LIB_PATH):
         raise ImportError(
@@ -183,6 +201,13 @@ def _load():
         "xh_trainer_set_env_state": (i, [vp, i, i, vp, vp]),
         "xh_venv_create": (i, [vp, i, i, i, C.c_uint32, i, i, i,
                                C.POINTER(vp)]),
+        "xh_item_set_default": (None, [C.POINTER(ItemSet), i]),
+        "xh_item_set_thresholds": (i, [C.POINTER(ItemSet), i,
+                                       C.POINTER(C.c_double)]),
+        "xh_venv_create_ex": (i, [vp, i, i, i, C.c_uint32, i, i, i,
+                                  C.POINTER(ItemSet), C.POINTER(vp)]),
+        "xh_venv_set_item_set": (i, [vp, C.POINTER(ItemSet)]),
+        "xh_venv_get_item_set": (i, [vp, C.POINTER(ItemSet)]),
         "xh_venv_destroy": (i, [vp]),
         "xh_venv_bytes": (sz, [vp, i]),
         "xh_venv_device_ptr": (vp, [vp, i]),
@@ -269,8 +294,8 @@ def _load():
     }
     for name, (res, args) in sig.items():
         f = getattr(lib, name, None)
-        if f is None and name == "xh_trainer_table_stats" and os.environ.get("XH_LIB_PATH"):
-            continue  # an A/B library from before the call (Trainer.table_stats raises)
+        if f is None and name in _AB_OPTIONAL and os.environ.get("XH_LIB_PATH"):
+            continue  # an A/B library from before the call
         if f is None:
             raise AttributeError("%s: no symbol %s" % (lib._name, name))
         f.restype = res
@@ -299,7 +324,10 @@ tensor_copy = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
 for _name, _mirror in (("xh_config", Config), ("xh_eval", Eval),
                        ("xh_layer", Layer), ("xh_venv_adv", VenvAdv),
                        ("xh_venv_loss", VenvLoss),
-                       ("xh_venv_loss_ext", VenvLossExt)):
+                       ("xh_venv_loss_ext", VenvLossExt),
+                       ("xh_item_set", ItemSet)):
+    if _name == "xh_item_set" and not hasattr(lib, "xh_venv_create_ex"):
+        continue  # an A/B library from before item sets
     if lib.xh_struct_size(_name.encode()) != C.sizeof(_mirror):
         raise ImportError("ctypes mirror of %s is out of date (%d vs %d bytes)"
                           % (_name, C.sizeof(_mirror),

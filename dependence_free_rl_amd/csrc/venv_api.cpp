@@ -52,6 +52,14 @@ struct xh_venv {
   int rec_steps = 0, rec_pos = 0;
   array rec[kRecArrays];
   bool mask_on = false;  // xh_venv_set_action_mask
+  // the item set in use (xh_venv_get_item_set): the default set until
+  // xh_venv_create_ex / xh_venv_set_item_set gives one.  `general`: one was
+  // given, and every launch runs the general kernels on `table`, which goes
+  // with the launch's arguments -- so a switch is ordered on the stream
+  bool general = false;
+  xh_item_set items{};
+  xh::VenvItemTable table{};
+  const xh::VenvItemTable *tab() const { return general ? &table : nullptr; }
   // xh_venv_legal's own [N][W] output, allocated at its first use
   uint32_t *legal_buf = nullptr;
   // scratch of xh_venv_record_ends / xh_venv_advantages, allocated at their
@@ -108,6 +116,85 @@ struct xh_venv {
 };
 
 namespace {
+
+// ---- item sets ----
+// XH_OK, or XH_ERR_INVALID with the first rule of include/xylo_hip.h the set
+// breaks; touches nothing
+int item_set_check(const xh_item_set *s, int D) {
+  if (!s) return fail(XH_ERR_INVALID, "item set: null");
+  if (D < 1 || D > 3) return fail(XH_ERR_INVALID, "item set: dims %d (1..3)", D);
+  const int K = s->num_items;
+  if (K < 1 || K > XH_ITEMS_MAX)
+    return fail(XH_ERR_INVALID, "item set: %d items (1..%d)", K, XH_ITEMS_MAX);
+  for (int d = 0; d < D; ++d)
+    if (s->capacity[d] < 1 || s->capacity[d] > 64)
+      return fail(XH_ERR_INVALID, "item set: capacity %d of dim %d (1..64)",
+                  s->capacity[d], d);
+  double sum = 0.0;
+  for (int k = 0; k < K; ++k) {
+    bool any = false;
+    for (int d = 0; d < D; ++d) {
+      if (s->item[k][d] < 0 || s->item[k][d] > s->capacity[d])
+        return fail(XH_ERR_INVALID, "item set: item %d is %d in dim %d "
+                    "(0..%d, the capacity)", k, s->item[k][d], d,
+                    s->capacity[d]);
+      any |= s->item[k][d] > 0;
+    }
+    if (!any)
+      return fail(XH_ERR_INVALID, "item set: item %d is zero in every dim (its "
+                  "episodes would never end)", k);
+    if (!(s->weight[k] >= 0.0) || !std::isfinite(s->weight[k]))
+      return fail(XH_ERR_INVALID, "item set: weight %g of item %d (finite, "
+                  ">= 0)", s->weight[k], k);
+    sum += s->weight[k];
+  }
+  if (!(sum > 0.0) || !std::isfinite(sum))
+    return fail(XH_ERR_INVALID, "item set: the weights sum to %g", sum);
+  return XH_OK;
+}
+
+// the K thresholds of a checked set (include/xylo_hip.h: the draw)
+void item_set_thresholds(const xh_item_set &s, double *c) {
+  const int K = s.num_items;
+  double W = 0.0;
+  for (int k = 0; k < K; ++k) W += s.weight[k];
+  double acc = 0.0;
+  int last = 0;  // the last item of positive weight
+  for (int k = 0; k < K; ++k) {
+    acc += s.weight[k] / W;
+    c[k] = acc;
+    if (s.weight[k] > 0.0) last = k;
+  }
+  for (int k = last; k < K; ++k) c[k] = 1.0;
+}
+
+// the kernels' table of a checked set
+xh::VenvItemTable item_set_table(const xh_item_set &s, int D) {
+  xh::VenvItemTable t{};
+  double c[XH_ITEMS_MAX];
+  item_set_thresholds(s, c);
+  for (int k = 0; k < xh::kVenvItemsMax; ++k) {
+    t.thr[k] = k < s.num_items ? c[k] : 1.0;
+    uint32_t w = 0;
+    for (int d = 0; d < D && k < s.num_items; ++d)
+      w |= (uint32_t)(s.item[k][d] & 0xff) << (8 * d);
+    t.shape[k] = w;
+  }
+  for (int d = 0; d < 4; ++d) t.cap[d] = d < D ? s.capacity[d] : 1;
+  return t;
+}
+
+// a copy with everything past K and past D zeroed (what get_item_set returns)
+xh_item_set item_set_clean(const xh_item_set &s, int D) {
+  xh_item_set o{};
+  o.num_items = s.num_items;
+  for (int d = 0; d < D; ++d) o.capacity[d] = s.capacity[d];
+  for (int k = 0; k < s.num_items; ++k) {
+    for (int d = 0; d < D; ++d) o.item[k][d] = s.item[k][d];
+    o.weight[k] = s.weight[k];
+  }
+  return o;
+}
 
 // An array allocated (zeroed on the stream) at its first use; the slot stays
 // NULL when that fails.  XH_VENV_POLICY / PCHOICE are such, so a venv that
@@ -259,7 +346,8 @@ int venv_launch(xh_venv *v, int op, int mode, bool use_mask, bool obs) {
   a.obs = obs ? (float *)v->buf[XH_VENV_OBS] : nullptr;
   if (op == xh::kVenvObserve) a.obs = (float *)v->buf[XH_VENV_OBS];
   if (mode == 0) a.reward = nullptr;
-  CHK(venv_timed(v, [&] { return xh::launch_venv(a, op, v->ctx->stream); }));
+  CHK(venv_timed(
+      v, [&] { return xh::launch_venv(a, op, v->ctx->stream, v->tab()); }));
   if (op == xh::kVenvStep && v->ep.ring.history) ++v->ep.calls;
   return XH_OK;
 }
@@ -547,9 +635,41 @@ int venv_policy_loss(xh_venv *v, const xh_venv_loss *p, bool masked,
 
 extern "C" {
 
+void xh_item_set_default(xh_item_set *s, int dims) {
+  if (!s) return;
+  *s = xh_item_set{};
+  if (dims < 1 || dims > 3) return;
+  const xh::EnvDesc env = make_env(8, dims);
+  s->num_items = 2;
+  for (int d = 0; d < dims; ++d) {
+    s->capacity[d] = kBinCapacity;
+    s->item[0][d] = env.item_a[d];
+    s->item[1][d] = env.item_b[d];
+  }
+  s->weight[0] = env.p_a;
+  s->weight[1] = 0.6;
+}
+
+int xh_item_set_thresholds(const xh_item_set *s, int dims, double *out) {
+  return guard([&]() -> int {
+    if (!out) return fail(XH_ERR_INVALID, "item set: null out");
+    CHK(item_set_check(s, dims));
+    item_set_thresholds(*s, out);
+    return XH_OK;
+  });
+}
+
 int xh_venv_create(xh_ctx *ctx, int num_envs, int bins, int dims,
                    uint32_t rng_state, int env_offset, int num_envs_global,
                    int policy_draws, xh_venv **out) {
+  return xh_venv_create_ex(ctx, num_envs, bins, dims, rng_state, env_offset,
+                           num_envs_global, policy_draws, nullptr, out);
+}
+
+int xh_venv_create_ex(xh_ctx *ctx, int num_envs, int bins, int dims,
+                      uint32_t rng_state, int env_offset, int num_envs_global,
+                      int policy_draws, const xh_item_set *items,
+                      xh_venv **out) {
   return guard([&]() -> int {
     if (!ctx || !out) return fail(XH_ERR_INVALID, "null arg");
     if (!xh::venv_shape_supported(bins, dims))
@@ -561,10 +681,18 @@ int xh_venv_create(xh_ctx *ctx, int num_envs, int bins, int dims,
                   env_offset, num_envs_global);
     if (policy_draws < 0 || policy_draws > 64)
       return fail(XH_ERR_INVALID, "venv: policy_draws %d", policy_draws);
+    if (items) CHK(item_set_check(items, dims));
     HIPCHK(hipSetDevice(ctx->device));
     auto *v = new xh_venv;
     v->ctx = ctx;
     v->env = make_env(bins, dims);
+    if (items) {
+      v->general = true;
+      v->items = item_set_clean(*items, dims);
+      v->table = item_set_table(v->items, dims);
+    } else {
+      xh_item_set_default(&v->items, dims);
+    }
     v->N = num_envs;
     v->Ng = num_envs_global;
     v->offset = env_offset;
@@ -590,7 +718,7 @@ int xh_venv_create(xh_ctx *ctx, int num_envs, int bins, int dims,
       uint32_t x0 = rng_state % 2147483647u;
       const hipError_t e = xh::launch_venv_init(v->args(), x0 ? x0 : 1u,
                                                 env_offset, num_envs_global,
-                                                (int)k, ctx->stream);
+                                                (int)k, ctx->stream, v->tab());
       if (e != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess)
         st = fail(XH_ERR_HIP, "venv init: %s", hipGetErrorString(e));
     }
@@ -598,6 +726,32 @@ int xh_venv_create(xh_ctx *ctx, int num_envs, int bins, int dims,
     ++ctx->trainers;
     if (st != XH_OK) return fail_after(st, [&] { xh_venv_destroy(v); });
     *out = v;
+    return XH_OK;
+  });
+}
+
+int xh_venv_set_item_set(xh_venv *v, const xh_item_set *s) {
+  return venv_call(v, [&]() -> int {
+    const int D = v->env.D;
+    CHK(item_set_check(s, D));
+    for (int d = 0; d < D; ++d)
+      if (s->capacity[d] != v->items.capacity[d])
+        return fail(XH_ERR_INVALID, "venv item set: capacity %d of dim %d, the "
+                    "venv's is %d (the stored bins are in its units)",
+                    s->capacity[d], d, v->items.capacity[d]);
+    // the table goes with each launch's arguments: the launches already on
+    // the stream keep theirs, the next one draws from this set
+    v->items = item_set_clean(*s, D);
+    v->table = item_set_table(v->items, D);
+    v->general = true;
+    return XH_OK;
+  });
+}
+
+int xh_venv_get_item_set(const xh_venv *v, xh_item_set *out) {
+  return guard([&]() -> int {
+    if (!v || !out) return fail(XH_ERR_INVALID, "null arg");
+    *out = v->items;
     return XH_OK;
   });
 }
@@ -663,9 +817,9 @@ int xh_venv_set(xh_venv *v, int which, const void *host, size_t bytes) {
       // any int8 value up to the capacity: the venv computes in int / f32
       // (an apply to a game-over env keeps subtracting, bin_packing.h:53-63)
       for (size_t i = 0; i < bytes; ++i)
-        if (b[i] > kBinCapacity)
+        if (b[i] > v->items.capacity[i % v->env.D])
           return fail(XH_ERR_INVALID, "venv: bin value %d above the capacity %d",
-                      b[i], kBinCapacity);
+                      b[i], v->items.capacity[i % v->env.D]);
     }
     HIPCHK(hipSetDevice(v->ctx->device));
     if (const int st = venv_ensure(v, which)) return st;
@@ -747,7 +901,7 @@ int xh_venv_act(xh_venv *v, const float *policy_dev, int kind, int mode,
     }
     a.legal = v->mask_on ? 1 : 0;
     const int st = venv_timed(
-        v, [&] { return xh::launch_venv_act(a, v->ctx->stream); });
+        v, [&] { return xh::launch_venv_act(a, v->ctx->stream, v->tab()); });
     if (st == XH_OK && v->rec_steps > 0) ++v->rec_pos;
     if (st == XH_OK && v->ep.ring.history) ++v->ep.calls;
     return st;
@@ -936,8 +1090,10 @@ int xh_venv_record_obs(xh_venv *v, int view, const int32_t *rows_dev,
     a.count = count;
     a.obs = obs_dev;
     a.err = v->err;
-    return venv_timed(
-        v, [&] { return xh::launch_venv_record_obs(a, v->ctx->stream); });
+    return venv_timed(v, [&] {
+      return xh::launch_venv_record_obs(a, v->ctx->stream,
+                                        v->general ? v->table.cap : nullptr);
+    });
   });
 }
 

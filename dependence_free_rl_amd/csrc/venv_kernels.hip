@@ -15,6 +15,10 @@
 // episode statistics on: the env's running length, venv_ep_count).
 // venv_act_kernel (xh_venv_act) picks the action from the caller's policy
 // row first -- react's sampling -- and writes the trajectory record.
+// The instance (item shapes, their probabilities, the capacity) is make_env's
+// at compile time, or -- the general instantiations, with a VenvItemTable as
+// a second kernel argument -- an xh_item_set's: K <= 16 shapes drawn by a
+// K-way threshold search on the same canonical(x), a capacity per dim.
 #include "xh_device.h"
 #include "xh_kernels.h"
 #include "xh_seg.h"
@@ -66,13 +70,52 @@ __device__ __forceinline__ void venv_item(const EnvDesc &E, uint32_t &x,
     ip[d] = d < E.D ? (int8_t)(first ? E.item_a[d] : E.item_b[d]) : 0;
 }
 
-template <int B, int D>
+// The problem instance a kernel runs on: its trailing arguments, the pack IT.
+// Empty: the reference's -- make_env's two items drawn by venv_item, kCapacity
+// in every dim, all of it compile-time; these instantiations have the
+// arguments and the code they had before the general ones existed.  One
+// VenvItemTable (xh_kernels.h; xh_item_set): K <= 16 shapes and per-dim
+// capacities as the kernel's second argument -- it arrives in scalar
+// registers, the same for every lane.  The helpers below are overloaded on it.
+__device__ __forceinline__ int venv_cap(int) { return kCapacity; }
+__device__ __forceinline__ int venv_cap(int d, const VenvItemTable &t) {
+  return t.cap[d];
+}
+// the observation's divisor; entries are float(x) / float(cap), an IEEE f32
+// division in the general form (at a capacity that is no power of two a
+// reciprocal multiply gives other bits)
+template <class... IT>
+__device__ __forceinline__ float venv_capf(int d, const IT &...t) {
+  return (float)venv_cap(d, t...);
+}
+
+// get_item.  General: the K-way form of venv_item's u < p_a on the same
+// canonical(x) (two engine draws): the first k with u < thr[k].  thr is
+// non-decreasing and 1.0 from its last used entry on, so walking all 16
+// entries and taking shape[k + 1] while u >= thr[k] ends on that k: 15 double
+// compares and selects on scalar operands, no loads, no branch, whatever K is.
+__device__ __forceinline__ void venv_draw(const EnvDesc &E, uint32_t &x,
+                                          int8_t *ip) {
+  venv_item(E, x, ip);
+}
+__device__ __forceinline__ void venv_draw(const EnvDesc &, uint32_t &x,
+                                          int8_t *ip, const VenvItemTable &t) {
+  const double u = canonical(x);
+  uint32_t w = t.shape[0];
+#pragma unroll
+  for (int k = 0; k + 1 < kVenvItemsMax; ++k)
+    w = u < t.thr[k] ? w : t.shape[k + 1];
+#pragma unroll
+  for (int d = 0; d < 4; ++d) ip[d] = (int8_t)((w >> (8 * d)) & 0xff);
+}
+
+template <int B, int D, class... IT>
 __device__ __forceinline__ void venv_obs_row(const int8_t *bp, const int8_t *ip,
-                                             float *o) {
+                                             float *o, const IT &...t) {
 #pragma unroll
   for (int d = 0; d < D; ++d) {
-    o[d] = (float)bp[d] / (float)kCapacity;
-    o[D + d] = (float)ip[d] / (float)kCapacity;
+    o[d] = (float)bp[d] / venv_capf(d, t...);
+    o[D + d] = (float)ip[d] / venv_capf(d, t...);
   }
 }
 
@@ -125,8 +168,8 @@ __device__ __forceinline__ void venv_ep_count(const VenvArgs &a, int env,
   if (fl < 0) a.ep_first[env] = len;
 }
 
-template <int B, int D, bool EP>
-__global__ __launch_bounds__(256) void venv_step_kernel(VenvArgs a) {
+template <int B, int D, bool EP, class... IT>
+__global__ __launch_bounds__(256) void venv_step_kernel(VenvArgs a, IT... t) {
   using S = VStepShape<B, D>;
   const int lane = threadIdx.x & 63;
   const int wave = (xcd_block() * (int)blockDim.x + (int)threadIdx.x) >> 6;
@@ -204,7 +247,7 @@ __global__ __launch_bounds__(256) void venv_step_kernel(VenvArgs a) {
 #pragma unroll
       for (int d = 0; d < D; ++d) {
         const int j = k * D + d;
-        ow[j >> 2] |= (uint32_t)((reset ? kCapacity : nb[k][d]) & 0xff) << (8 * (j & 3));
+        ow[j >> 2] |= (uint32_t)((reset ? venv_cap(d, t...) : nb[k][d]) & 0xff) << (8 * (j & 3));
       }
     uint32_t *op = reinterpret_cast<uint32_t *>(
         __builtin_assume_aligned(bp + li * S::BPL * D, S::ALIGN));
@@ -216,8 +259,8 @@ __global__ __launch_bounds__(256) void venv_step_kernel(VenvArgs a) {
   int8_t nit[4];
 #pragma unroll
   for (int d = 0; d < 4; ++d) nit[d] = d < D ? (int8_t)item[d] : 0;
-  if (!chosen_over) venv_item(a.env, x, nit);  // apply's get_item
-  if (reset) venv_item(a.env, x, nit);         // reset's get_item
+  if (!chosen_over) venv_draw(a.env, x, nit, t...);  // apply's get_item
+  if (reset) venv_draw(a.env, x, nit, t...);         // reset's get_item
   if (a.mode == 1) x = mstd_mulmod(x, a.jump_mul);
   if (li == 0) {
     *reinterpret_cast<unsigned *>(ip) = (unsigned)(uint8_t)nit[0] |
@@ -236,8 +279,8 @@ __global__ __launch_bounds__(256) void venv_step_kernel(VenvArgs a) {
       float *o = a.obs + ((size_t)env * B + bin) * 2 * D;
 #pragma unroll
       for (int d = 0; d < D; ++d) {
-        o[d] = (float)(reset ? kCapacity : nb[k][d]) / (float)kCapacity;
-        o[D + d] = (float)nit[d] / (float)kCapacity;
+        o[d] = (float)(reset ? venv_cap(d, t...) : nb[k][d]) / venv_capf(d, t...);
+        o[D + d] = (float)nit[d] / venv_capf(d, t...);
       }
     }
   }
@@ -421,8 +464,9 @@ __global__ __launch_bounds__(256) void venv_legal_kernel(VenvArgs a,
 // row.  The words it masked with go to a.rec_legal's slot (where not null),
 // also for a refused env: they are a function of the state before the step.
 // The other instantiation holds none of this.
-template <int B, int D, bool RD, bool MASK, bool EP>
-__global__ __launch_bounds__(256) void venv_act_kernel(VenvActArgs a) {
+template <int B, int D, bool RD, bool MASK, bool EP, class... IT>
+__global__ __launch_bounds__(256) void venv_act_kernel(VenvActArgs a,
+                                                       IT... t) {
   using S = VStepShape<B, D>;
   static_assert(S::BPL % 4 == 0, "the lane's floats as 16-byte loads");
   static_assert(!RD || (S::BPL == VLossShape<B>::BPL && S::EPW ==
@@ -639,7 +683,7 @@ __global__ __launch_bounds__(256) void venv_act_kernel(VenvActArgs a) {
 #pragma unroll
       for (int d = 0; d < D; ++d) {
         const int j = k * D + d;
-        nb[k][d] = reset ? kCapacity : nb[k][d];
+        nb[k][d] = reset ? venv_cap(d, t...) : nb[k][d];
         ow[j >> 2] |= (uint32_t)(nb[k][d] & 0xff) << (8 * (j & 3));
       }
     uint32_t *op = reinterpret_cast<uint32_t *>(
@@ -652,8 +696,8 @@ __global__ __launch_bounds__(256) void venv_act_kernel(VenvActArgs a) {
   int8_t nit[4];
 #pragma unroll
   for (int d = 0; d < 4; ++d) nit[d] = d < D ? (int8_t)item[d] : 0;
-  if (!chosen_over) venv_item(a.v.env, x, nit);  // apply's get_item
-  if (reset) venv_item(a.v.env, x, nit);         // reset's get_item
+  if (!chosen_over) venv_draw(a.v.env, x, nit, t...);  // apply's get_item
+  if (reset) venv_draw(a.v.env, x, nit, t...);         // reset's get_item
   x = mstd_mulmod(x, a.v.jump_mul);
   if (li == 0) {
     const float rew = over ? 0.0f : 1.0f;
@@ -680,16 +724,16 @@ __global__ __launch_bounds__(256) void venv_act_kernel(VenvActArgs a) {
       float *o = a.v.obs + ((size_t)env * B + li * S::BPL + k) * 2 * D;
 #pragma unroll
       for (int d = 0; d < D; ++d) {
-        o[d] = (float)nb[k][d] / (float)kCapacity;
-        o[D + d] = (float)nit[d] / (float)kCapacity;
+        o[d] = (float)nb[k][d] / venv_capf(d, t...);
+        o[D + d] = (float)nit[d] / venv_capf(d, t...);
       }
     }
   }
 }
 
 // environment::reset for every (masked) env: bins at capacity, get_item.
-template <int B, int D>
-__global__ __launch_bounds__(256) void venv_reset_kernel(VenvArgs a) {
+template <int B, int D, class... IT>
+__global__ __launch_bounds__(256) void venv_reset_kernel(VenvArgs a, IT... t) {
   using S = VShape<B, D>;
   const int lane = threadIdx.x & 63;
   const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
@@ -700,10 +744,11 @@ __global__ __launch_bounds__(256) void venv_reset_kernel(VenvArgs a) {
 #pragma unroll
   for (int k = 0; k < S::BPL; ++k)
 #pragma unroll
-    for (int d = 0; d < D; ++d) bp[(k * 64 + li) * D + d] = (int8_t)kCapacity;
+    for (int d = 0; d < D; ++d)
+      bp[(k * 64 + li) * D + d] = (int8_t)venv_cap(d, t...);
   if (li == 0) {
     uint32_t x = a.rng[env];
-    venv_item(a.env, x, a.items + (size_t)env * 4);
+    venv_draw(a.env, x, a.items + (size_t)env * 4, t...);
     a.rng[env] = x;
     // the abandoned episode is not counted
     if (a.ep_running) a.ep_running[env] = 0;
@@ -711,8 +756,9 @@ __global__ __launch_bounds__(256) void venv_reset_kernel(VenvArgs a) {
 }
 
 // observation::to_vector of every env: obs [N][B][2D] f32.
-template <int B, int D>
-__global__ __launch_bounds__(256) void venv_observe_kernel(VenvArgs a) {
+template <int B, int D, class... IT>
+__global__ __launch_bounds__(256) void venv_observe_kernel(VenvArgs a,
+                                                           IT... t) {
   using S = VShape<B, D>;
   const int lane = threadIdx.x & 63;
   const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
@@ -724,22 +770,25 @@ __global__ __launch_bounds__(256) void venv_observe_kernel(VenvArgs a) {
 #pragma unroll
   for (int k = 0; k < S::BPL; ++k) {
     const int bin = k * 64 + li;
-    venv_obs_row<B, D>(bp + bin * D, ip, a.obs + ((size_t)env * B + bin) * 2 * D);
+    venv_obs_row<B, D>(bp + bin * D, ip,
+                       a.obs + ((size_t)env * B + bin) * 2 * D, t...);
   }
 }
 
 // Construction (bin_packing.h:50-52): env g (global) draws its item at engine
 // position 2g (envs constructed one after another), then its stream moves to
 // its first step position 2 Ng + k g (k = draws per env per step).
+template <class... IT>
 __global__ void venv_init_kernel(VenvArgs a, uint32_t x0, int env_offset,
-                                 int n_global, int k) {
+                                 int n_global, int k, IT... t) {
   const int BD = a.env.B * a.env.D;
   for (int env = blockIdx.x * blockDim.x + threadIdx.x; env < a.N;
        env += gridDim.x * blockDim.x) {
     const uint64_t g = (uint64_t)env_offset + env;
     uint32_t x = mstd_jump(x0, 2 * g);
-    for (int i = 0; i < BD; ++i) a.bins[(size_t)env * BD + i] = (int8_t)kCapacity;
-    venv_item(a.env, x, a.items + (size_t)env * 4);
+    for (int i = 0; i < BD; ++i)
+      a.bins[(size_t)env * BD + i] = (int8_t)venv_cap(i % a.env.D, t...);
+    venv_draw(a.env, x, a.items + (size_t)env * 4, t...);
     const uint64_t target = 2ull * n_global + (uint64_t)k * g;
     a.rng[env] = mstd_jump(x, target - (2 * g + 2));
   }
@@ -750,12 +799,22 @@ __global__ void venv_init_kernel(VenvArgs a, uint32_t x0, int env_offset,
   X(8, 1) X(8, 2) X(8, 3) X(16, 1) X(16, 2) X(16, 3) X(32, 1) X(32, 2)      \
   X(32, 3) X(64, 1) X(64, 2) X(64, 3) X(128, 1) X(128, 2) X(128, 3)
 
+// A kernel exists in the object whose launcher names it: the builtin ones in
+// venv_kernels.o, the general ones in venv_gen_kernels.o (this file with
+// -DXH_VENV_GEN_TU=1, so the two sets of act instantiations compile side by
+// side).  This object's launches, generic in the pack: t is nothing, or the
+// item table.
+#ifndef XH_VENV_GEN_TU
+#define XH_VENV_GEN_TU 0
+#endif
+#if !XH_VENV_GEN_TU
 bool venv_shape_supported(int B, int D) {
 #define X(XB, XD) if (B == XB && D == XD) return true;
   XH_VENV_SHAPES(X)
 #undef X
   return false;
 }
+#endif
 
 static dim3 venv_grid(int N, int B) {
   const int epw = B >= 64 ? 1 : 64 / B;
@@ -769,23 +828,25 @@ static dim3 venv_step_grid(int N, int B) {
   return dim3((unsigned)((waves + 3) / 4));
 }
 
-hipError_t launch_venv(const VenvArgs &a, int op, hipStream_t s) {
+template <class... IT>
+static hipError_t venv_launch_inst(const VenvArgs &a, int op, hipStream_t s,
+                                   const IT &...t) {
   const int B = a.env.B, D = a.env.D;
   if (a.N <= 0) return hipSuccess;
 #define X(XB, XD)                                                            \
   if (B == XB && D == XD) {                                                  \
     if (op == kVenvStep && a.ep_running)                                     \
-      hipLaunchKernelGGL((venv_step_kernel<XB, XD, true>),                   \
-                         venv_step_grid(a.N, B), dim3(256), 0, s, a);        \
+      hipLaunchKernelGGL((venv_step_kernel<XB, XD, true, IT...>),            \
+                         venv_step_grid(a.N, B), dim3(256), 0, s, a, t...);  \
     else if (op == kVenvStep)                                                \
-      hipLaunchKernelGGL((venv_step_kernel<XB, XD, false>),                  \
-                         venv_step_grid(a.N, B), dim3(256), 0, s, a);        \
+      hipLaunchKernelGGL((venv_step_kernel<XB, XD, false, IT...>),           \
+                         venv_step_grid(a.N, B), dim3(256), 0, s, a, t...);  \
     else if (op == kVenvReset)                                               \
-      hipLaunchKernelGGL((venv_reset_kernel<XB, XD>), venv_grid(a.N, B),     \
-                         dim3(256), 0, s, a);                                \
+      hipLaunchKernelGGL((venv_reset_kernel<XB, XD, IT...>),                 \
+                         venv_grid(a.N, B), dim3(256), 0, s, a, t...);       \
     else                                                                     \
-      hipLaunchKernelGGL((venv_observe_kernel<XB, XD>), venv_grid(a.N, B),   \
-                         dim3(256), 0, s, a);                                \
+      hipLaunchKernelGGL((venv_observe_kernel<XB, XD, IT...>),               \
+                         venv_grid(a.N, B), dim3(256), 0, s, a, t...);       \
     return hipGetLastError();                                                \
   }
   XH_VENV_SHAPES(X)
@@ -795,43 +856,78 @@ hipError_t launch_venv(const VenvArgs &a, int op, hipStream_t s) {
 
 // RD where the call records its distributions, MASK where it masks, EP where
 // it counts episodes
-template <int B, int D, bool RD, bool MASK>
-static void vact_launch_ep(const VenvActArgs &a, hipStream_t s) {
+template <int B, int D, bool RD, bool MASK, class... IT>
+static void vact_launch_ep(const VenvActArgs &a, hipStream_t s,
+                           const IT &...t) {
   const dim3 grid = venv_step_grid(a.v.N, B);
   if (a.v.ep_running)
-    hipLaunchKernelGGL((venv_act_kernel<B, D, RD, MASK, true>), grid,
-                       dim3(256), 0, s, a);
+    hipLaunchKernelGGL((venv_act_kernel<B, D, RD, MASK, true, IT...>), grid,
+                       dim3(256), 0, s, a, t...);
   else
-    hipLaunchKernelGGL((venv_act_kernel<B, D, RD, MASK, false>), grid,
-                       dim3(256), 0, s, a);
+    hipLaunchKernelGGL((venv_act_kernel<B, D, RD, MASK, false, IT...>), grid,
+                       dim3(256), 0, s, a, t...);
 }
 
-template <int B, int D>
-static void vact_launch(const VenvActArgs &a, hipStream_t s) {
+template <int B, int D, class... IT>
+static void vact_launch(const VenvActArgs &a, hipStream_t s, const IT &...t) {
   if (a.legal) {
     if (a.rec_distrib)
-      vact_launch_ep<B, D, true, true>(a, s);
+      vact_launch_ep<B, D, true, true>(a, s, t...);
     else
-      vact_launch_ep<B, D, false, true>(a, s);
+      vact_launch_ep<B, D, false, true>(a, s, t...);
   } else {
     if (a.rec_distrib)
-      vact_launch_ep<B, D, true, false>(a, s);
+      vact_launch_ep<B, D, true, false>(a, s, t...);
     else
-      vact_launch_ep<B, D, false, false>(a, s);
+      vact_launch_ep<B, D, false, false>(a, s, t...);
   }
 }
 
-hipError_t launch_venv_act(const VenvActArgs &a, hipStream_t s) {
+template <class... IT>
+static hipError_t venv_act_launch_inst(const VenvActArgs &a, hipStream_t s,
+                                       const IT &...t) {
   const int B = a.v.env.B, D = a.v.env.D;
   if (a.v.N <= 0) return hipSuccess;
 #define X(XB, XD)                                                            \
   if (B == XB && D == XD) {                                                  \
-    vact_launch<XB, XD>(a, s);                                               \
+    vact_launch<XB, XD>(a, s, t...);                                         \
     return hipGetLastError();                                                \
   }
   XH_VENV_SHAPES(X)
 #undef X
   return hipErrorInvalidValue;
+}
+
+#if XH_VENV_GEN_TU
+hipError_t launch_venv_gen(const VenvArgs &a, int op, hipStream_t s,
+                           const VenvItemTable &items) {
+  return venv_launch_inst(a, op, s, items);
+}
+
+hipError_t launch_venv_act_gen(const VenvActArgs &a, hipStream_t s,
+                               const VenvItemTable &items) {
+  return venv_act_launch_inst(a, s, items);
+}
+
+hipError_t launch_venv_init_gen(const VenvArgs &a, uint32_t x0, int env_offset,
+                                int n_global, int k, hipStream_t s,
+                                const VenvItemTable &items) {
+  hipLaunchKernelGGL((venv_init_kernel<VenvItemTable>),
+                     dim3((a.N + 255) / 256), dim3(256), 0, s, a, x0,
+                     env_offset, n_global, k, items);
+  return hipGetLastError();
+}
+#else
+hipError_t launch_venv(const VenvArgs &a, int op, hipStream_t s,
+                       const VenvItemTable *items) {
+  if (items) return launch_venv_gen(a, op, s, *items);
+  return venv_launch_inst(a, op, s);
+}
+
+hipError_t launch_venv_act(const VenvActArgs &a, hipStream_t s,
+                           const VenvItemTable *items) {
+  if (items) return launch_venv_act_gen(a, s, *items);
+  return venv_act_launch_inst(a, s);
 }
 
 hipError_t launch_venv_legal(const VenvArgs &a, uint32_t *out, hipStream_t s) {
@@ -849,10 +945,14 @@ hipError_t launch_venv_legal(const VenvArgs &a, uint32_t *out, hipStream_t s) {
 }
 
 hipError_t launch_venv_init(const VenvArgs &a, uint32_t x0, int env_offset,
-                            int n_global, int k, hipStream_t s) {
-  hipLaunchKernelGGL(venv_init_kernel, dim3((a.N + 255) / 256), dim3(256), 0, s,
-                     a, x0, env_offset, n_global, k);
+                            int n_global, int k, hipStream_t s,
+                            const VenvItemTable *items) {
+  if (items)
+    return launch_venv_init_gen(a, x0, env_offset, n_global, k, s, *items);
+  hipLaunchKernelGGL((venv_init_kernel<>), dim3((a.N + 255) / 256), dim3(256),
+                     0, s, a, x0, env_offset, n_global, k);
   return hipGetLastError();
 }
+#endif
 
 }  // namespace xh

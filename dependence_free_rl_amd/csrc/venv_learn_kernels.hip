@@ -57,8 +57,21 @@ struct VObsShape {
 // past the last row, and rows whose index is outside the view, load row 0's
 // words (in range whenever count > 0 rows exist) and nothing is stored for
 // them.
-template <int B, int D>
-__global__ __launch_bounds__(256) void venv_record_obs_kernel(VenvObsArgs a) {
+//
+// CAP, the kernel's trailing arguments: nothing -- capacity kCapacity, the
+// arguments and the code of before general item sets -- or one VObsCaps, a
+// set's per-dim capacities: IEEE f32 divisions by float(cap[d]).
+struct VObsCaps {
+  int32_t cap[4];
+};
+__device__ __forceinline__ float vobs_capf(int) { return (float)kCapacity; }
+__device__ __forceinline__ float vobs_capf(int d, const VObsCaps &c) {
+  return (float)c.cap[d];
+}
+
+template <int B, int D, class... CAP>
+__global__ __launch_bounds__(256) void venv_record_obs_kernel(VenvObsArgs a,
+                                                              CAP... c) {
   using S = VObsShape<B, D>;
   static_assert(S::NF % 4 == 0, "the lane's floats as 16-byte stores");
   const int lane = threadIdx.x & 63;
@@ -105,8 +118,8 @@ __global__ __launch_bounds__(256) void venv_record_obs_kernel(VenvObsArgs a) {
       const int i = k * D + d;
       int v = (int)(signed char)((wv[i >> 2] >> (8 * (i & 3))) & 0xff);
       v = bin == sub ? v - item[d] : v;
-      f[k * 2 * D + d] = (float)v / (float)kCapacity;
-      f[k * 2 * D + D + d] = (float)item[d] / (float)kCapacity;
+      f[k * 2 * D + d] = (float)v / vobs_capf(d, c...);
+      f[k * 2 * D + D + d] = (float)item[d] / vobs_capf(d, c...);
     }
   }
   constexpr int F4 = S::NF / 4;
@@ -238,7 +251,10 @@ __global__ __launch_bounds__(64) void venv_adv_counts_kernel(const int *end_part
   X(8, 1) X(8, 2) X(8, 3) X(16, 1) X(16, 2) X(16, 3) X(32, 1) X(32, 2)      \
   X(32, 3) X(64, 1) X(64, 2) X(64, 3) X(128, 1) X(128, 2) X(128, 3)
 
-hipError_t launch_venv_record_obs(const VenvObsArgs &a, hipStream_t s) {
+hipError_t launch_venv_record_obs(const VenvObsArgs &a, hipStream_t s,
+                                  const int32_t *cap) {
+  VObsCaps c{{1, 1, 1, 1}};
+  for (int d = 0; cap && d < a.D && d < 4; ++d) c.cap[d] = cap[d];
   if (a.count <= 0) return hipSuccess;
   // NEXT needs a recorded transition (an out-of-range lane reads row 0's)
   if (a.N <= 0 || a.P < (a.next ? 1 : 0)) return hipErrorInvalidValue;
@@ -248,8 +264,12 @@ hipError_t launch_venv_record_obs(const VenvObsArgs &a, hipStream_t s) {
                        VObsShape<XB, XD>::RPW;                                \
     const long blocks = (waves + 3) / 4;                                      \
     if (blocks > 0x7fffffffl) return hipErrorInvalidValue;                    \
-    hipLaunchKernelGGL((venv_record_obs_kernel<XB, XD>),                      \
-                       dim3((unsigned)blocks), dim3(256), 0, s, a);           \
+    if (cap)                                                                  \
+      hipLaunchKernelGGL((venv_record_obs_kernel<XB, XD, VObsCaps>),          \
+                         dim3((unsigned)blocks), dim3(256), 0, s, a, c);      \
+    else                                                                      \
+      hipLaunchKernelGGL((venv_record_obs_kernel<XB, XD>),                    \
+                         dim3((unsigned)blocks), dim3(256), 0, s, a);         \
     return hipGetLastError();                                                 \
   }
   XH_VOBS_SHAPES(X)

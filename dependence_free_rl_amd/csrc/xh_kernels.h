@@ -403,14 +403,39 @@ struct VenvActArgs {
 // the packed legal set: W = max(1, B / 32) uint32 words per env, bit b % 32
 // of word b / 32 is bin b
 inline int venv_legal_words(int B) { return B >= 32 ? B / 32 : 1; }
+// A general item set (xh_item_set, xh_venv_create_ex / xh_venv_set_item_set):
+// the general kernels' second argument, so it travels in the kernel arguments
+// (uniform loads, no device table to keep in step with the stream) and the
+// builtin kernels' arguments are what they were.  thr[k] = c_k, the K-way
+// draw's thresholds, 1.0 from the last item of positive weight on (and past
+// K); shape[k] = item k's int8 x 4 as
+// the ITEMS word, 0 past K; cap[d] the capacity of dim d, 1 past D.
+constexpr int kVenvItemsMax = 16;
+struct VenvItemTable {
+  double thr[kVenvItemsMax];
+  uint32_t shape[kVenvItemsMax];
+  int32_t cap[4];
+};
 bool venv_shape_supported(int B, int D);
-hipError_t launch_venv(const VenvArgs &a, int op, hipStream_t s);
-hipError_t launch_venv_act(const VenvActArgs &a, hipStream_t s);
+// items == nullptr: the builtin instantiations (make_env's two items, capacity
+// kCapacity); otherwise the general ones (venv_gen_kernels.o)
+hipError_t launch_venv(const VenvArgs &a, int op, hipStream_t s,
+                       const VenvItemTable *items = nullptr);
+hipError_t launch_venv_act(const VenvActArgs &a, hipStream_t s,
+                           const VenvItemTable *items = nullptr);
+hipError_t launch_venv_gen(const VenvArgs &a, int op, hipStream_t s,
+                           const VenvItemTable &items);
+hipError_t launch_venv_act_gen(const VenvActArgs &a, hipStream_t s,
+                               const VenvItemTable &items);
 // xh_venv_legal: out [N][W], the legal set (all bins where it is empty) of
 // every env's current state; reads a.bins / a.items only
 hipError_t launch_venv_legal(const VenvArgs &a, uint32_t *out, hipStream_t s);
 hipError_t launch_venv_init(const VenvArgs &a, uint32_t x0, int env_offset,
-                            int n_global, int k, hipStream_t s);
+                            int n_global, int k, hipStream_t s,
+                            const VenvItemTable *items = nullptr);
+hipError_t launch_venv_init_gen(const VenvArgs &a, uint32_t x0, int env_offset,
+                                int n_global, int k, hipStream_t s,
+                                const VenvItemTable &items);
 
 // Episode statistics of a venv (venv_episode_kernels.hip).
 // running 0, first -1, the accumulators cleared
@@ -448,7 +473,10 @@ struct VenvObsArgs {
   float *obs;                 // [count][B][2D], 16-byte aligned
   int *err;                   // bit 4: an index outside the view's rows
 };
-hipError_t launch_venv_record_obs(const VenvObsArgs &a, hipStream_t s);
+// cap == nullptr: capacity kCapacity; otherwise the D capacities of a general
+// item set (the general instantiation: IEEE f32 divisions by them)
+hipError_t launch_venv_record_obs(const VenvObsArgs &a, hipStream_t s,
+                                  const int32_t *cap = nullptr);
 // GAE, TD(0) targets and lambda returns of a window with explicit rewards:
 // gae_kernel's and value_targets_kernel's arithmetic, one env per lane.
 struct VenvGaeArgs {

@@ -28,6 +28,12 @@ env's episode lengths on the device, env.episode_row() appends one row of sums
 to a device ring, and env.episode_stats() / episode_curve() /
 first_episode_lengths() read them back.
 
+The problem instance is the reference's (two items, capacity 8) unless the
+VecEnv is given its own: VecEnv(..., items=[(3, 1), (2, 2), (1, 4)],
+weights=[2, 1, 1], capacity=(5, 7)) draws from up to 16 shapes with per-dim
+capacities, from the same stream positions, and env.set_item_set(items,
+weights) switches the mix during training (a curriculum).
+
 Mirrors xylo::environment<A,S>::apply / view / reset (rl.h:163-170) with the
 id ranging over the batch, bp::environment (bin_packing.h:46-85) and
 xylo::agent::step (rl.h:325-349).  State lives in HBM; numpy arrays here are
@@ -90,19 +96,103 @@ def _beta_ptr(beta, name="beta"):
     return int(beta)
 
 
+def _item_set(items, weights, capacity, dims):
+    """An _lib.ItemSet of `items` ([K][dims] ints), `weights` ([K], default
+    uniform) and `capacity` ([dims] or one int, default 8).  Shapes only are
+    checked here; the library checks the values."""
+    it = np.asarray(items)
+    if it.ndim == 1 and dims == 1:
+        it = it.reshape(-1, 1)
+    if it.ndim != 2 or it.shape[1] != dims:
+        raise ValueError("items: shape %s, expected [K][%d]" % (it.shape, dims))
+    K = it.shape[0]
+    if not 1 <= K <= _lib.ITEMS_MAX:
+        raise ValueError("items: %d items (1..%d)" % (K, _lib.ITEMS_MAX))
+    if not np.all(it == np.floor(it)):
+        raise ValueError("items: the shapes are integers")
+    w = np.ones(K) if weights is None else np.asarray(weights, np.float64)
+    if w.shape != (K,):
+        raise ValueError("weights: shape %s, expected (%d,)" % (w.shape, K))
+    cap = np.broadcast_to(np.asarray(8 if capacity is None else capacity),
+                          (dims,))
+    s = _lib.ItemSet()
+    s.num_items = K
+    for d in range(dims):
+        s.capacity[d] = int(cap[d])
+    for k in range(K):
+        for d in range(dims):
+            s.item[k][d] = int(it[k, d])
+        s.weight[k] = float(w[k])
+    return s
+
+
+def _item_set_dict(s, dims):
+    K = s.num_items
+    th = (C.c_double * _lib.ITEMS_MAX)()
+    check(_lib.lib.xh_item_set_thresholds(C.byref(s), dims, th))
+    return {"items": np.array([[s.item[k][d] for d in range(dims)]
+                               for k in range(K)], np.int32),
+            "weights": np.array([s.weight[k] for k in range(K)], np.float64),
+            "capacity": np.array([s.capacity[d] for d in range(dims)],
+                                 np.int32),
+            "thresholds": np.array(th[:K], np.float64)}
+
+
+def item_set_thresholds(items, weights=None, capacity=None):
+    """The K thresholds c_k of the item draw (xh_item_set_thresholds; host
+    only): the item is the first k with u < c_k, u the env's canonical draw.
+    float64 [K]; the last one is exactly 1.0."""
+    it = np.asarray(items)
+    dims = 1 if it.ndim == 1 else it.shape[1]
+    return _item_set_dict(_item_set(items, weights, capacity, dims),
+                          dims)["thresholds"]
+
+
 class VecEnv:
     """xh_venv: N envs of B bins x D dims stepped by one kernel per call."""
 
     def __init__(self, ctx, num_envs, bins=64, dims=2, rng_state=1,
-                 env_offset=0, num_envs_global=None, policy_draws=2):
+                 env_offset=0, num_envs_global=None, policy_draws=2, *,
+                 items=None, weights=None, capacity=None):
+        """items None: the reference's instance (xh_venv_create).  Otherwise
+        the venv's own (xh_venv_create_ex): items [K][dims] ints, K <= 16,
+        weights [K] (default uniform), capacity [dims] or one int (default
+        8)."""
         self.ctx = ctx
         self.N, self.B, self.D = num_envs, bins, dims
         self.h = C.c_void_p()
         self._dev = {}  # device scratch: name -> (address, bytes)
         self._ep_history = 0  # the episode ring's rows (set_episode_stats)
-        check(_lib.lib.xh_venv_create(ctx.h, num_envs, bins, dims, rng_state,
-                                      env_offset, num_envs_global or num_envs,
-                                      policy_draws, C.byref(self.h)))
+        if items is None:
+            if weights is not None or capacity is not None:
+                raise ValueError("VecEnv: weights and capacity go with items")
+            check(_lib.lib.xh_venv_create(
+                ctx.h, num_envs, bins, dims, rng_state, env_offset,
+                num_envs_global or num_envs, policy_draws, C.byref(self.h)))
+        else:
+            s = _item_set(items, weights, capacity, dims)
+            check(_lib.lib.xh_venv_create_ex(
+                ctx.h, num_envs, bins, dims, rng_state, env_offset,
+                num_envs_global or num_envs, policy_draws, C.byref(s),
+                C.byref(self.h)))
+
+    # ---- the problem instance ---------------------------------------------
+    def set_item_set(self, items, weights=None):
+        """Switch the item mix (xh_venv_set_item_set), e.g. the next stage of
+        a curriculum: ordered on the stream, in effect from the next draw; the
+        items the envs hold stay and no stream position moves.  The capacity
+        stays the venv's."""
+        cap = self.item_set()["capacity"]
+        s = _item_set(items, weights, cap, self.D)
+        check(_lib.lib.xh_venv_set_item_set(self.h, C.byref(s)))
+
+    def item_set(self):
+        """The set in use (xh_venv_get_item_set) as a dict: items int32
+        [K][D], weights float64 [K], capacity int32 [D] and thresholds float64
+        [K] (item_set_thresholds)."""
+        s = _lib.ItemSet()
+        check(_lib.lib.xh_venv_get_item_set(self.h, C.byref(s)))
+        return _item_set_dict(s, self.D)
 
     def _spec(self, which):
         N, B, D = self.N, self.B, self.D

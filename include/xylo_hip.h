@@ -635,6 +635,11 @@ int xh_digest_host(const void *data, size_t bytes, uint64_t *out);
  * stream where it stands (with Ng = 1 every call sequence is exactly the
  * single-env reference engine).
  *
+ * The problem instance -- the item shapes, their probabilities and the bins'
+ * capacity -- is the reference's unless the venv is given an xh_item_set
+ * (xh_venv_create_ex / xh_venv_set_item_set below): up to XH_ITEMS_MAX shapes
+ * with weights and a capacity per dim, drawn from the same stream positions.
+ *
  * Calls are asynchronous on the context's stream; an out-of-range action
  * leaves its env untouched and is reported by the next xh_venv_synchronize
  * (or get) as XH_ERR_INVALID. */
@@ -652,6 +657,65 @@ size_t xh_venv_bytes(const xh_venv *v, int which);
 void *xh_venv_device_ptr(xh_venv *v, int which);
 int xh_venv_get(xh_venv *v, int which, void *host, size_t bytes);
 int xh_venv_set(xh_venv *v, int which, const void *host, size_t bytes);
+/* Item sets and bin capacity.  xh_venv_create runs the reference's instance:
+ * two items drawn bernoulli(0.4) -- (4) / (1), (4,2) / (1,2), (4,2,2) /
+ * (1,2,1) at D = 1, 2, 3 -- and capacity 8 in every dim.  An xh_item_set
+ * describes another: K shapes with weights, and a capacity per dim.
+ *
+ * The draw is the K-way form of bernoulli's u < p on the same u =
+ * generate_canonical<double> (two engine draws, so every stream position of
+ * the section above stays what it is): the item is the first k with u < c_k.
+ * The thresholds are computed on the host in double: W = the sequential sum
+ * of the weights, c_k = c_(k-1) + w_k / W with c_(-1) = 0, and c_k = 1.0
+ * exactly from the last item of positive weight on (so c_(K-1) = 1.0, and
+ * trailing zero weights cannot pick up the last rounding error).  A zero-weight
+ * item is never drawn.  Weights {0.4, 0.6} give c = {0.4, 1.0}: the default set
+ * draws bit for bit what bernoulli(0.4) draws.  xh_item_set_thresholds writes
+ * those K doubles (host only, no device).
+ *
+ * Capacity is per dim: a reset fills bins[b][d] = capacity[d], and OBS (and
+ * xh_venv_record_obs) is float(bins[b][d]) / float(capacity[d]) and
+ * float(item[d]) / float(capacity[d]), IEEE f32 divisions (at capacity 8 the
+ * bits of the builtin instance).  The upper limit 64 keeps two consecutive
+ * xh_venv_apply calls on one bin inside int8; beyond that (applies to an env
+ * that is over and is never reset) a bin wraps, as it does at capacity 8.
+ * xh_venv_set(XH_VENV_BINS) refuses a value above its dim's capacity.
+ *
+ * A set is valid when K is in 1..XH_ITEMS_MAX, every capacity[d < D] in 1..64,
+ * every item[k][d < D] in 0..capacity[d] with at least one entry above 0 (an
+ * all-zero item's episodes would never end), and every weight is finite and
+ * >= 0 with a sum above 0.  Entries past D and past K are ignored.  Anything
+ * else is XH_ERR_INVALID, and nothing is allocated or changed.
+ *
+ * xh_venv_create_ex: items == NULL is xh_venv_create exactly (the same
+ * kernels, launches and bits).  Any non-NULL set runs the general kernels,
+ * also when it equals the default set.
+ * xh_venv_set_item_set switches the set (a curriculum): ordered on the
+ * context's stream like every call, it takes effect from the next draw; the
+ * items the envs hold stay and no stream position moves.  The capacity must
+ * equal the venv's (XH_ERR_INVALID otherwise: the stored bins are in its
+ * units).  On a venv created without a set it switches that venv to the
+ * general kernels.  xh_venv_get_item_set returns the set in use (the default
+ * set for a venv created without one).
+ * The trainer, xh_config, the evaluators and xh_heuristic_evaluate keep the
+ * reference's instance. */
+enum { XH_ITEMS_MAX = 16 };
+typedef struct {
+  int num_items;                 /* K, 1..XH_ITEMS_MAX                      */
+  int capacity[4];               /* per dimension, first D used, 1..64      */
+  int item[XH_ITEMS_MAX][4];     /* shapes, first D entries used            */
+  double weight[XH_ITEMS_MAX];   /* >= 0, finite, sum > 0                   */
+} xh_item_set;                   /* xh_struct_size("xh_item_set")           */
+/* make_env's two items, weights 0.4 / 0.6, capacity 8 (dims outside 1..3: an
+ * all-zero, invalid set) */
+void xh_item_set_default(xh_item_set *s, int dims);
+int xh_item_set_thresholds(const xh_item_set *s, int dims, double *out /*[K]*/);
+int xh_venv_create_ex(xh_ctx *ctx, int num_envs, int bins, int dims,
+                      uint32_t rng_state, int env_offset, int num_envs_global,
+                      int policy_draws, const xh_item_set *items,
+                      xh_venv **out);
+int xh_venv_set_item_set(xh_venv *v, const xh_item_set *s);
+int xh_venv_get_item_set(const xh_venv *v, xh_item_set *out);
 /* agent::step minus react for every env: skip the policy's draws,
  * environment::apply(ACTIONS[e]), REWARD / DONE, reset on game over;
  * write_obs != 0 also writes OBS of the resulting states. */

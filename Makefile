@@ -20,6 +20,7 @@ OBJS     := $(SRC)/policy_kernels.o $(SRC)/value_kernels.o \
             $(SRC)/policy_spec8_e0_kernels.o \
             $(SRC)/policy_spec8_pack_kernels.o $(SRC)/spec8_pack_kernels.o \
             $(SRC)/policy_spec8_tab_kernels.o $(SRC)/spec8_table_kernels.o \
+            $(SRC)/table_mm_kernels.o \
             $(SRC)/policy_spec4_kernels.o \
             $(SRC)/policy_split8wh_kernels.o $(SRC)/policy_split8wh_kl_kernels.o \
             $(SRC)/policy_split8x_kernels.o $(SRC)/policy_split8x_kl_kernels.o \
@@ -41,6 +42,7 @@ HDRS     := $(SRC)/xh_device.h $(SRC)/xh_kernels.h $(SRC)/xh_split.h \
             $(SRC)/xh_img16.h \
             $(SRC)/spec8_layout.h $(SRC)/spec8_e0_layout.h $(SRC)/spec8_l1_layout.h \
             $(SRC)/spec8_pack_layout.h $(SRC)/spec8_table_layout.h \
+            $(SRC)/table_tile_layout.h \
             $(SRC)/xh_opt.h $(SRC)/xh_clip.h \
             $(SRC)/xh_diag.h $(SRC)/xh_sums.h $(SRC)/xh_seg.h $(SRC)/xh_vstore.h \
             $(SRC)/xh_digest.h $(SRC)/xh_state_blob.h $(SRC)/xh_trainer.h \

@@ -6,8 +6,10 @@
 // alone, and every parameter gradient is linear in the rows' loss gradient g at
 // fixed activations, so the backward pass needs of the batch only
 //   G_s = sum over the rows with entry s of g_row.
-// Two launches per epoch, between the table build's forward and backward
-// (policy_spec8_kernels.hip, XH_SP8_TAB_TU):
+// Between the table's forward and backward: the stream, and -- only with the
+// former table launches (policy_spec8_kernels.hip, XH_SP8_TAB_TU;
+// XH_TRAIN_TABLE=spec8), since table_bwd_kernel (table_mm_kernels.hip) sums
+// `part` itself in the same order -- the reduce:
 //   stream  one wave per group of the packed batch, lane = row: the logit of
 //           the row's entry from the table (LDS), the count-weighted softmax
 //           of the row's segment (an env-step; a wide group: all 64 rows), the
@@ -171,11 +173,12 @@ __global__ __launch_bounds__(64 * kTrSlices) void table_reduce_kernel(TableStrea
 
 }  // namespace sp8
 
-hipError_t launch_table_stream(const TableStreamArgs &a, int grid, hipStream_t s) {
+hipError_t launch_table_stream(const TableStreamArgs &a, int grid, hipStream_t s, bool reduce) {
   if (!a.pk || !a.pk_hdr || !a.logits || !a.part || !a.G || !a.gmax || grid < 1 ||
       (a.algo != kPPO && a.algo != kAC))
     return hipErrorInvalidValue;
   hipLaunchKernelGGL(sp8::table_stream_kernel, dim3(grid), dim3(64 * sp8::kTsWaves), 0, s, a);
+  if (!reduce) return hipGetLastError();  // (table_bwd_kernel sums `part` itself)
   const int blocks = (lt::kEntries + sp8::kTrEntries - 1) / sp8::kTrEntries;
   hipLaunchKernelGGL(sp8::table_reduce_kernel, dim3(blocks), dim3(64 * sp8::kTrSlices), 0, s, a,
                      grid);

@@ -37,11 +37,13 @@
 //                                  no bin below -capacity runs its epochs ON
 //                                  THE TABLE (trainer_learn.cpp, decide_table;
 //                                  XH_TRAIN_TABLE=0 keeps the packed launches):
-//                                  the kernel's table build
-//                                  (policy_spec8_tab_kernels.o) forward and
-//                                  backward over the 578 (bin state, item)
-//                                  points, spec8_table_kernels.hip's streaming
-//                                  pass over the packed batch between them
+//                                  table_mm_kernels.hip's forward and backward
+//                                  over the 578 (bin state, item) points on the
+//                                  exact f32 MFMA, spec8_table_kernels.hip's
+//                                  streaming pass over the packed batch between
+//                                  them (XH_TRAIN_TABLE=spec8: the kernel's own
+//                                  table build, policy_spec8_tab_kernels.o, and
+//                                  the stream's reduce, the former launches)
 //   128 bins, 3-D, [128,128] (config 5)      policy_train_split8x_kernel
 //                                  (KL-PPO: policy_train_split8x_kl_kernel)
 //   32 bins, 1-D, [64,64] (config 2)         policy_train_split4h_kernel

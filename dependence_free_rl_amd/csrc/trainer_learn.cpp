@@ -15,6 +15,7 @@
 #include "../../include/xylo_hip.h"
 #include "spec8_pack_layout.h"
 #include "spec8_table_layout.h"
+#include "table_tile_layout.h"
 #include "xh_host.h"
 #include "xh_kernels.h"
 #include "xh_trainer.h"
@@ -203,16 +204,69 @@ bool decide_pack(const xh_trainer *t) {
 // The packed learn()'s epochs on the table ("the epoch on the
 // table"): the rollout table's own condition on top of decide_pack -- no slot
 // of this trainer has held a bin below -capacity, which has no table entry.
-// XH_TRAIN_TABLE=0 (read per learn()) keeps the packed launches.
-bool decide_table(const xh_trainer *t, bool pack) {
+// XH_TRAIN_TABLE (read per learn()): 0 keeps the packed launches; spec8 keeps
+// the table's former launches (the spec8 kernel's table build, forward and
+// backward, with the stream's reduce between them); unset or anything else:
+// the lean table kernels (table_mm_kernels.hip).
+enum TableMode { kTabOff = 0, kTabSpec8, kTabMm };
+TableMode decide_table(const xh_trainer *t, bool pack) {
   const char *m = std::getenv("XH_TRAIN_TABLE");
-  return pack && t->tab_pk && (t->cfg.algo == XH_PPO || t->cfg.algo == XH_AC) &&
-         !t->wide_seen && !batch_wide(t) && !(m && *m && std::atoi(m) == 0);
+  const bool spec8 = m && std::strcmp(m, "spec8") == 0;
+  const bool on = pack && t->tab_pk && (t->cfg.algo == XH_PPO || t->cfg.algo == XH_AC) &&
+                  !t->wide_seen && !batch_wide(t) && !(m && *m && !spec8 && std::atoi(m) == 0);
+  return !on ? kTabOff : spec8 ? kTabSpec8 : kTabMm;
 }
 
-// One epoch on the table: the table batch's forward -> the entries' logits;
-// the streaming pass over the packed batch -> G and max |G|; the table batch's
-// backward weighted by G -> `grid` slabs.
+// The launches epoch e of a learn() runs: epoch 0 on the rollout's outputs, the
+// epoch on the table, the packed build, or the selected plain kernel.  One
+// predicate for policy_epochs and for advantages(), which skips the bound on
+// |g| when no launch of the learn() reads it.
+enum EpochPath { kEpE0, kEpTable, kEpPack, kEpPlain };
+EpochPath epoch_path(int e, bool use_e0, bool wide, int ablate, bool trace, bool pk,
+                     TableMode table) {
+  if (e == 0 && use_e0 && !wide && !ablate && !trace) return kEpE0;
+  if (pk && !trace && table != kTabOff) return kEpTable;
+  if (pk && !trace) return kEpPack;
+  return kEpPlain;
+}
+
+// Every epoch of this learn() runs the lean table kernels, which take no bound
+// (XH_ABLATE / XH_PHASE_TRACE as phase_trace_begin will read them).
+bool bound_unread(const xh_trainer *t, bool use_e0, bool pack, TableMode table) {
+  if (table != kTabMm) return false;
+  const char *ab = std::getenv("XH_ABLATE");
+  const int ablate = ab ? std::atoi(ab) : 0;
+  const bool trace = xh::diag_build() && std::getenv("XH_PHASE_TRACE");
+  const bool wide = batch_wide(t);
+  for (int e = 0; e < t->cfg.epochs; ++e)
+    if (epoch_path(e, use_e0, wide, ablate, trace, pack, table) != kEpTable) return false;
+  return true;
+}
+
+// One epoch on the table, the lean kernels: the tiles' forward -> the entries'
+// logits and H2; the streaming pass over the packed batch -> its workgroups'
+// sums; the tiles' backward, which sums them into G -> tt::kTiles slabs in
+// tab_slab.  zero_ood: the forward also zeroes the out-of-domain counter.
+hipError_t table_epoch_mm(xh_trainer *t, const xh::PolicyTrainArgs &pa, bool count,
+                          bool zero_ood, hipStream_t s) {
+  hipError_t e = xh::launch_table_fwd(
+      xh::TableFwdArgs{pa.env, pa.params, t->tab_logits, t->tab_h2,
+                       zero_ood ? t->tab_ood : nullptr}, s);
+  if (e != hipSuccess) return e;
+  const xh::TableStreamArgs sa{pa.pk,       pa.pk_hdr,   t->tab_logits,
+                               pa.algo,     pa.clip_eps, t->tab_part,
+                               t->tab_G,    t->tab_gmax, count ? t->tab_ood : nullptr};
+  e = xh::launch_table_stream(sa, t->pslab_n, s, false);
+  if (e != hipSuccess) return e;
+  return xh::launch_table_bwd(
+      xh::TableBwdArgs{pa.env, pa.params, t->tab_h2, t->tab_part, t->pslab_n, t->tab_G,
+                       t->tab_slab, t->pslab_stride}, s);
+}
+
+// One epoch on the table, the former launches (XH_TRAIN_TABLE=spec8): the table
+// batch's forward -> the entries' logits; the streaming pass over the packed
+// batch and its reduce -> G and max |G|; the table batch's backward weighted by
+// G -> `grid` slabs.
 hipError_t table_epoch(xh_trainer *t, const xh::PolicyTrainArgs &pa, int grid, bool count,
                        hipStream_t s) {
   xh::PolicyTrainArgs ta = pa;
@@ -321,9 +375,10 @@ int value_step(xh_trainer *t, xh::MlpArgs *vm_out, bool *vnet_out) {
 
 // calculate_advantage (policy_gradient.h:220-281) on post-update values;
 // GAE zeroes V(terminal), the targets above used V(E_t).  Then the opt-in
-// normalisation and, for PPO / AC, the bound on |g| in pa->g_bound.
+// normalisation and, for PPO / AC, the bound on |g| in pa->g_bound -- unless
+// no launch of this learn() reads it (need_bound false: bound_unread).
 int advantages(xh_trainer *t, xh::MlpArgs vm, bool vnet,
-               xh::PolicyTrainArgs *pa) {
+               xh::PolicyTrainArgs *pa, bool need_bound) {
   hipStream_t s = t->ctx->stream;
   const xh_config &c = t->cfg;
   const int NS = (int)((t->T() + 1) * t->N()), NT = (int)(t->T() * t->N());
@@ -351,7 +406,7 @@ int advantages(xh_trainer *t, xh::MlpArgs vm, bool vnet,
                                       (double)t->T() * c.num_envs_global, s);
     }));
   }
-  if (c.algo == XH_PPO || c.algo == XH_AC) {
+  if ((c.algo == XH_PPO || c.algo == XH_AC) && need_bound) {
     // the bound on |g| the 64-bin train kernel scales dW2's operand by: from
     // the final advantages and p_old, the same in all k epochs
     CHK(timed(t, "value", [&]() {
@@ -365,7 +420,8 @@ int advantages(xh_trainer *t, xh::MlpArgs vm, bool vnet,
 
 // optimize_action: k policy steps (policy_gradient.h:297-307); KL-PPO adapts
 // beta from the job's mean KL after each of them.
-int policy_epochs(xh_trainer *t, xh::PolicyTrainArgs &pa, bool use_e0, bool table) {
+int policy_epochs(xh_trainer *t, xh::PolicyTrainArgs &pa, bool use_e0, TableMode table,
+                  bool ood_zeroed) {
   hipStream_t s = t->ctx->stream;
   const xh_config &c = t->cfg;
   pa.env = t->env;
@@ -391,22 +447,34 @@ int policy_epochs(xh_trainer *t, xh::PolicyTrainArgs &pa, bool use_e0, bool tabl
   for (int e = 0; e < c.epochs; ++e) {
     float *g = t->pgrads + (size_t)e * t->np;
     int nslab = t->pslab_n;
-    if (e == 0 && use_e0 && !pa.wide && !pa.ablate && !pa.trace) {
+    const float *slab = t->pslab;
+    const EpochPath path = epoch_path(e, use_e0, pa.wide, pa.ablate, pa.trace != nullptr,
+                                      pa.pk != nullptr, table);
+    if (path == kEpE0) {
       // (the later epochs' launches report the kernel: last_train)
       const xh::PolicyTrainE0Args ea{t->e0_p, t->e0_mask};
       CHK(timed(t, "policy_train", [&]() {
         return xh::launch_policy_train_spec8_e0(pa, ea, t->pslab_n, s);
       }));
-    } else if (pa.pk && !pa.trace && table) {
+    } else if (path == kEpTable) {
       // the epoch on the table: its launches in one interval; the arithmetic
       // behind g is the same kernel's, and it reports as the plain one
       t->last_train.name = "policy_train_spec8_kernel";
       t->last_train.math = xh::kMathSplitTrainF16Pair;
-      nslab = t->pslab_n < xh::tb::kGroups ? t->pslab_n : xh::tb::kGroups;
-      CHK(timed(t, "policy_train", [&]() { return table_epoch(t, pa, nslab, !counted, s); }));
+      if (table == kTabMm) {
+        // the tiles' own slabs, whatever the train grid
+        nslab = xh::tt::kTiles;
+        slab = t->tab_slab;
+        CHK(timed(t, "policy_train", [&]() {
+          return table_epoch_mm(t, pa, !counted, !counted && !ood_zeroed, s);
+        }));
+      } else {
+        nslab = t->pslab_n < xh::tb::kGroups ? t->pslab_n : xh::tb::kGroups;
+        CHK(timed(t, "policy_train", [&]() { return table_epoch(t, pa, nslab, !counted, s); }));
+      }
       counted = true;
       t->tab_learned = true;
-    } else if (pa.pk && !pa.trace) {
+    } else if (path == kEpPack) {
       // the same kernel's packed build: it reports as the plain one
       t->last_train.name = "policy_train_spec8_kernel";
       t->last_train.math = xh::kMathSplitTrainF16Pair;
@@ -421,7 +489,7 @@ int policy_epochs(xh_trainer *t, xh::PolicyTrainArgs &pa, bool use_e0, bool tabl
     }
     if (pa.trace) CHK(phase_trace_report(t, &pa));  // first epoch only
     // the optimizer step does not read beta: it may precede the KL update
-    CHK(reduce_and_step(t, XH_POLICY, e, t->pslab, nslab,
+    CHK(reduce_and_step(t, XH_POLICY, e, slab, nslab,
                         t->pslab_stride, t->np, g, t->pp));
     if (kl) {  // mean KL over the job's rows -> beta for the next epoch
       CHK(timed(t, "kl", [&]() {
@@ -452,13 +520,17 @@ int do_learn(xh_trainer *t) {
   bool vnet = false;
   CHK(value_step(t, &vm, &vnet));
   xh::PolicyTrainArgs pa{};
-  CHK(advantages(t, vm, vnet, &pa));
+  const TableMode table = decide_table(t, pack);
+  const bool lean = bound_unread(t, use_e0, pack, table);
+  CHK(advantages(t, vm, vnet, &pa, !lean));
   t->pk_learned = false;
   if (pack) CHK(pack_batch(t, &pa));
   t->tab_learned = false;
-  const bool table = decide_table(t, pack);
-  if (table) HIPCHK(hipMemsetAsync(t->tab_ood, 0, sizeof(int), t->ctx->stream));
-  CHK(policy_epochs(t, pa, use_e0, table));
+  // the out-of-domain counter: zeroed by the first table forward where the
+  // lean kernels run epoch 0, by a memset otherwise
+  if (table != kTabOff && !lean)
+    HIPCHK(hipMemsetAsync(t->tab_ood, 0, sizeof(int), t->ctx->stream));
+  CHK(policy_epochs(t, pa, use_e0, table, !lean));
   for (auto &cl : t->clip) cl.learned = cl.part != nullptr;
   if (t->upd.ring.history) CHK(upd_learn(t, e0_at_entry));
   if (t->stats.ring.history) CHK(stats_learn(t));

@@ -652,10 +652,11 @@ hipError_t launch_spec8_pack(const PackArgs &a, hipStream_t s);
 // The epoch on the table (spec8_table_layout.h): the per-bin
 // net's activations depend on the table entry (bin state, item) alone and
 // every parameter gradient is linear in the rows' loss gradient g, so an epoch
-// is a forward over the table batch, one streaming pass over the packed batch
-// that sums g per entry, and a backward over the table batch weighted by the
-// sums.
-// the kernel's table build (policy_spec8_tab_kernels.o), a.pk = the table
+// is a forward over the table, one streaming pass over the packed batch that
+// sums g per entry, and a backward over the table weighted by the sums.  The
+// table's two launches are table_mm_kernels.hip's (TableFwdArgs / TableBwdArgs
+// below); XH_TRAIN_TABLE=spec8 keeps the former ones:
+// the spec8 kernel's table build (policy_spec8_tab_kernels.o), a.pk = the table
 // batch, grid <= tb::kGroups; backward: a.g_bound = the bound on |G|
 struct PolicyTrainTabArgs {
   float *logits;   // [lt::kEntries] forward: the entries' logits (out)
@@ -675,11 +676,38 @@ struct TableStreamArgs {
   int algo;             // kPPO / kAC
   float clip_eps;
   double *part;         // [grid][lt::kEntries] scratch: the workgroups' sums
-  float *G;             // [lt::kEntries] out
-  float *gmax;          // out: max_s |G_s|
+  float *G;             // [lt::kEntries] out (the reduce's)
+  float *gmax;          // out: max_s |G_s| (the reduce's; the stream zeroes it)
   int *ood;             // += rows whose state lies outside the table (null: not counted)
 };
-hipError_t launch_table_stream(const TableStreamArgs &a, int grid, hipStream_t s);
+// reduce = false: the stream alone, `part` left for table_bwd_kernel, which
+// forms G itself; G is not written and *gmax is unused
+hipError_t launch_table_stream(const TableStreamArgs &a, int grid, hipStream_t s,
+                               bool reduce = true);
+// The table's forward and backward on the exact f32 MFMA (table_mm_kernels.hip;
+// tiles: table_tile_layout.h), tt::kTiles workgroups each, whatever the stream's
+// grid: forward -> the entries' logits and H2; backward: G from the stream's
+// `part` (table_reduce_kernel's order), the backward products, one slab per
+// tile in the slab layout.  No scale, no bound on |G|.
+struct TableFwdArgs {
+  EnvDesc env;
+  const float *params;
+  float *logits;   // [lt::kEntries] out
+  float *h2;       // [tt::kRows][128] out: relu(layer 2), f32
+  int *zero_ood;   // non-null: workgroup 0 zeroes it (the stream's counter)
+};
+struct TableBwdArgs {
+  EnvDesc env;
+  const float *params;
+  const float *h2;     // the forward's
+  const double *part;  // [nparts][lt::kEntries] the stream's
+  int nparts;          // the stream's grid, >= 1
+  float *G;            // [lt::kEntries] out
+  float *slab;         // [tt::kTiles][slab_stride] out
+  int slab_stride;
+};
+hipError_t launch_table_fwd(const TableFwdArgs &a, hipStream_t s);
+hipError_t launch_table_bwd(const TableBwdArgs &a, hipStream_t s);
 // its earlier form, dW2 on the three-part bf16 split (the variant library
 // only: XH_TRAIN_KERNEL=spec8_3p)
 hipError_t launch_policy_train_spec8_3p(const PolicyTrainArgs &a, int grid, hipStream_t s);

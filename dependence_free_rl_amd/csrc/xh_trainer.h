@@ -77,9 +77,13 @@ struct xh_trainer {
   // entries' logits, the per-entry sums G of the loss gradient with their
   // bound max |G|, the streaming pass's per-workgroup sums, and the count of
   // rows outside the table.  tab_learned: the last learn() ran its epochs on
-  // the table (xh_trainer_table_stats).
+  // the table (xh_trainer_table_stats).  The lean table kernels
+  // (table_mm_kernels.hip; tiles: table_tile_layout.h) read neither the table
+  // batch nor the bound; they keep the forward's H2 in tab_h2 and write their
+  // slabs, one per tile whatever the train grid, to tab_slab.
   uint8_t *tab_pk = nullptr;
   float *tab_logits = nullptr, *tab_G = nullptr, *tab_gmax = nullptr;
+  float *tab_h2 = nullptr, *tab_slab = nullptr;
   double *tab_part = nullptr;
   int *tab_ood = nullptr;
   bool tab_learned = false;

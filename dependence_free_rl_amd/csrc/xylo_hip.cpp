@@ -18,6 +18,7 @@
 #include "spec8_e0_layout.h"
 #include "spec8_pack_layout.h"
 #include "spec8_table_layout.h"
+#include "table_tile_layout.h"
 #include "xh_host.h"
 #include "xh_kernels.h"
 #include "xh_trainer.h"
@@ -379,6 +380,9 @@ int xh_trainer_create(xh_ctx *ctx, const xh_config *cfg, xh_trainer **out) {
       A(&t->tab_gmax, 4);
       A(&t->tab_part, (size_t)t->pslab_n * xh::lt::kEntries * 8);
       A(&t->tab_ood, 4);
+      // the lean table kernels' H2 (tail rows included) and their own slabs
+      A(&t->tab_h2, (size_t)xh::tt::kRows * c.policy_h2 * 4);
+      A(&t->tab_slab, (size_t)xh::tt::kTiles * t->pslab_stride * 4);
       if (st == XH_OK) {
         std::vector<uint8_t> tbh((size_t)xh::tb::kBytes);
         for (int g = 0; g < xh::tb::kGroups; ++g)

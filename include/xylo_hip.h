@@ -1479,7 +1479,8 @@ int xh_trainer_pack_stats(xh_trainer *t, long *packed, long *unpacked, long *gro
  * loss gradient per point, a backward over the 578 points -- (*ran = 1), the
  * rows of its packed batch whose state lay outside the table (clamped to the
  * nearest entry; 0 wherever the gate holds) and the groups of the table batch
- * each table launch ran.  All three are 0 when it did not (XH_TRAIN_TABLE=0,
+ * (10, also where the table's launches run on their own 16-entry tiles and
+ * read no table batch).  All three are 0 when it did not (XH_TRAIN_TABLE=0,
  * no packed learn(), KL-PPO, a slot of this trainer has held a bin below
  * -capacity) or none has run yet. */
 int xh_trainer_table_stats(xh_trainer *t, int *ran, long *out_of_domain, long *groups);

@@ -13,6 +13,7 @@ OBJS     := $(SRC)/policy_kernels.o $(SRC)/value_kernels.o \
             $(SRC)/env_kernels.o $(SRC)/kl_kernels.o \
             $(SRC)/heuristic_kernels.o $(SRC)/dense_kernels.o \
             $(SRC)/pg_kernels.o $(SRC)/venv_kernels.o $(SRC)/venv_gen_kernels.o \
+            $(SRC)/venv_heur_kernels.o $(SRC)/venv_heur_gen_kernels.o \
             $(SRC)/venv_learn_kernels.o \
             $(SRC)/venv_loss_kernels.o $(SRC)/venv_episode_kernels.o \
             $(SRC)/value_net_kernels.o \
@@ -47,6 +48,7 @@ HDRS     := $(SRC)/xh_device.h $(SRC)/xh_kernels.h $(SRC)/xh_split.h \
             $(SRC)/xh_diag.h $(SRC)/xh_sums.h $(SRC)/xh_seg.h $(SRC)/xh_vstore.h \
             $(SRC)/xh_digest.h $(SRC)/xh_state_blob.h $(SRC)/xh_trainer.h \
             $(SRC)/xh_host.h $(SRC)/xh_ring.h $(SRC)/xh_logit_table.h \
+            $(SRC)/xh_venv_device.h $(SRC)/xh_venv_sample.inc \
             include/xylo_hip.h
 
 # Drop-in C++20 layer (include/xylo_compat): the reference's unmodified
@@ -91,6 +93,9 @@ $(SRC)/%.o: $(SRC)/%.hip $(HDRS)
 # capacities), an object of their own so that the two sets of act kernels
 # compile side by side
 $(SRC)/venv_gen_kernels.o: $(SRC)/venv_kernels.hip $(HDRS)
+	$(HIPCC) $(HIPFLAGS) -DXH_VENV_GEN_TU=1 -c $< -o $@
+# ... and the heuristic act's (xh_venv_act_heuristic), the same way
+$(SRC)/venv_heur_gen_kernels.o: $(SRC)/venv_heur_kernels.hip $(HDRS)
 	$(HIPCC) $(HIPFLAGS) -DXH_VENV_GEN_TU=1 -c $< -o $@
 
 # the KL-PPO builds of the 64-, 128- and 32-bin train kernels (their own objects:

@@ -41,10 +41,10 @@ from ._lib import (VEP_CALLS, VEP_COUNT, VEP_ENVS_FINISHED,  # noqa: F401
                    VEP_LEN_MAX, VEP_LEN_MIN, VEP_LEN_SQSUM, VEP_LEN_SUM,
                    VEP_ROW, VEP_RUNNING_MAX, VEP_RUNNING_SUM, VEPS_COUNT,
                    VEPS_FIRST, VEPS_RUNNING)
-from .venv import (VecEnv, item_set_thresholds, legal_words,  # noqa: F401
-                   pack_legal, unpack_legal)
+from .venv import (VecEnv, heuristic_baseline,  # noqa: F401
+                   item_set_thresholds, legal_words, pack_legal, unpack_legal)
 
 __all__ = ["Context", "Trainer", "POLICY", "VALUE", "init_policy", "init_value",
            "init_full_policy", "clip_grad_norm", "describe_state", "digest",
            "heuristic_evaluate", "XhError", "runtime_info", "device_count", "VecEnv",
-           "item_set_thresholds"]
+           "item_set_thresholds", "heuristic_baseline"]

@@ -215,6 +215,7 @@ def _load():
         "xh_venv_set": (i, [vp, i, vp, sz]),
         "xh_venv_step": (i, [vp, i]),
         "xh_venv_act": (i, [vp, vp, i, i, i]),
+        "xh_venv_act_heuristic": (i, [vp, i, i]),
         "xh_venv_set_record": (i, [vp, i, i]),
         "xh_venv_record_pos": (i, [vp, C.POINTER(C.c_int)]),
         "xh_venv_record_rewind": (i, [vp]),

@@ -338,6 +338,46 @@ int venv_timed(xh_venv *v, F &&launch) {
   return XH_OK;
 }
 
+// ---- what xh_venv_act and xh_venv_act_heuristic share ----
+// the record has a free slot; the device is current and PCHOICE exists
+int venv_act_ready(xh_venv *v, const char *what) {
+  if (v->rec_steps > 0 && v->rec_pos >= v->rec_steps)
+    return fail(XH_ERR_STATE, "%s: the record's %d slots are full "
+                "(xh_venv_record_rewind)", what, v->rec_steps);
+  HIPCHK(hipSetDevice(v->ctx->device));
+  return venv_ensure(v, XH_VENV_PCHOICE);
+}
+
+// an act launch's arguments but for its policy: agent::step's, the outputs,
+// the record's slot at the cursor and the mask's switch
+xh::VenvActArgs venv_act_args(const xh_venv *v, bool write_obs) {
+  xh::VenvActArgs a{};
+  a.v = v->args();
+  a.v.mode = 1;
+  a.v.obs = write_obs ? (float *)v->buf[XH_VENV_OBS] : nullptr;
+  a.action = (int32_t *)v->buf[XH_VENV_ACTIONS];
+  a.pchoice = (float *)v->buf[XH_VENV_PCHOICE];
+  if (v->rec_steps > 0) {
+    a.rec_action = v->rec_as<int32_t>(XH_VREC_ACTION);
+    a.rec_pchoice = v->rec_as<float>(XH_VREC_PCHOICE);
+    a.rec_reward = v->rec_as<float>(XH_VREC_REWARD);
+    a.rec_done = v->rec_as<uint8_t>(XH_VREC_DONE);
+    a.rec_bins = v->rec_as<int8_t>(XH_VREC_BINS);
+    a.rec_items = v->rec_as<int8_t>(XH_VREC_ITEMS);
+    a.slot = v->rec_pos;
+    a.rec_legal = v->rec_as<uint32_t>(kRecLegal);
+  }
+  a.legal = v->mask_on ? 1 : 0;
+  return a;
+}
+
+// after the launch: the cursor and the episode statistics' call count
+int venv_act_done(xh_venv *v, int st) {
+  if (st == XH_OK && v->rec_steps > 0) ++v->rec_pos;
+  if (st == XH_OK && v->ep.ring.history) ++v->ep.calls;
+  return st;
+}
+
 int venv_launch(xh_venv *v, int op, int mode, bool use_mask, bool obs) {
   HIPCHK(hipSetDevice(v->ctx->device));
   xh::VenvArgs a = v->args();
@@ -872,39 +912,42 @@ int xh_venv_act(xh_venv *v, const float *policy_dev, int kind, int mode,
     if (reinterpret_cast<uintptr_t>(policy_dev) & 15)
       return fail(XH_ERR_INVALID, "venv act: the policy rows must be 16-byte "
                   "aligned (the kernel reads them as 16-byte loads)");
-    if (v->rec_steps > 0 && v->rec_pos >= v->rec_steps)
-      return fail(XH_ERR_STATE, "venv act: the record's %d slots are full "
-                  "(xh_venv_record_rewind)", v->rec_steps);
-    HIPCHK(hipSetDevice(v->ctx->device));
+    CHK(venv_act_ready(v, "venv act"));
     if (!policy_dev)
       if (const int st = venv_ensure(v, XH_VENV_POLICY)) return st;
-    if (const int st = venv_ensure(v, XH_VENV_PCHOICE)) return st;
-    xh::VenvActArgs a{};
-    a.v = v->args();
-    a.v.mode = 1;
-    a.v.obs = write_obs ? (float *)v->buf[XH_VENV_OBS] : nullptr;
+    xh::VenvActArgs a = venv_act_args(v, write_obs != 0);
     a.policy = policy_dev ? policy_dev : (const float *)v->buf[XH_VENV_POLICY];
-    a.action = (int32_t *)v->buf[XH_VENV_ACTIONS];
-    a.pchoice = (float *)v->buf[XH_VENV_PCHOICE];
     a.logits = kind == XH_ACT_LOGITS;
     a.argmax = mode == XH_ACT_ARGMAX;
-    if (v->rec_steps > 0) {
-      a.rec_action = v->rec_as<int32_t>(XH_VREC_ACTION);
-      a.rec_pchoice = v->rec_as<float>(XH_VREC_PCHOICE);
-      a.rec_reward = v->rec_as<float>(XH_VREC_REWARD);
-      a.rec_done = v->rec_as<uint8_t>(XH_VREC_DONE);
-      a.rec_bins = v->rec_as<int8_t>(XH_VREC_BINS);
-      a.rec_items = v->rec_as<int8_t>(XH_VREC_ITEMS);
-      a.slot = v->rec_pos;
-      a.rec_distrib = v->rec_as<float>(kRecDistrib);
-      a.rec_legal = v->rec_as<uint32_t>(kRecLegal);
-    }
-    a.legal = v->mask_on ? 1 : 0;
-    const int st = venv_timed(
-        v, [&] { return xh::launch_venv_act(a, v->ctx->stream, v->tab()); });
-    if (st == XH_OK && v->rec_steps > 0) ++v->rec_pos;
-    if (st == XH_OK && v->ep.ring.history) ++v->ep.calls;
-    return st;
+    a.rec_distrib = v->rec_as<float>(kRecDistrib);
+    return venv_act_done(v, venv_timed(v, [&] {
+      return xh::launch_venv_act(a, v->ctx->stream, v->tab());
+    }));
+  });
+}
+
+int xh_venv_act_heuristic(xh_venv *v, int heuristic, int write_obs) {
+  return venv_call(v, [&]() -> int {
+    if (heuristic != XH_HEUR_RANDOM && heuristic != XH_HEUR_FIRSTFIT &&
+        heuristic != XH_HEUR_BESTFIT && heuristic != XH_HEUR_MINWASTE)
+      return fail(XH_ERR_INVALID, "venv act heuristic: heuristic %d "
+                  "(XH_HEUR_RANDOM / FIRSTFIT / BESTFIT / MINWASTE)",
+                  heuristic);
+    if (heuristic == XH_HEUR_RANDOM && v->policy_draws != 2)
+      return fail(XH_ERR_INVALID, "venv act heuristic: the random pick takes "
+                  "two draws per env and step, the venv was created with "
+                  "policy_draws %d", v->policy_draws);
+    if (v->rec[kRecDistrib].ptr)
+      return fail(XH_ERR_STATE, "venv act heuristic: the distribution record "
+                  "is on and a heuristic has no distribution to record "
+                  "(xh_venv_set_record_distrib(v, 0))");
+    CHK(venv_act_ready(v, "venv act heuristic"));
+    xh::VenvHeurArgs h{};
+    h.a = venv_act_args(v, write_obs != 0);
+    h.heur = heuristic;
+    return venv_act_done(v, venv_timed(v, [&] {
+      return xh::launch_venv_heur(h, v->ctx->stream, v->tab());
+    }));
   });
 }
 

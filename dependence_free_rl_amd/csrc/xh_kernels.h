@@ -427,6 +427,18 @@ hipError_t launch_venv_gen(const VenvArgs &a, int op, hipStream_t s,
                            const VenvItemTable &items);
 hipError_t launch_venv_act_gen(const VenvActArgs &a, hipStream_t s,
                                const VenvItemTable &items);
+// xh_venv_act_heuristic (venv_heur_kernel, venv_heur_kernels.hip): the act
+// launch with the row formed in registers from the env's own state.  a.policy,
+// a.logits, a.argmax and a.rec_distrib are not read; heur is a Heuristic, the
+// same for every lane.  items as in launch_venv_act.
+struct VenvHeurArgs {
+  VenvActArgs a;
+  int heur;
+};
+hipError_t launch_venv_heur(const VenvHeurArgs &h, hipStream_t s,
+                            const VenvItemTable *items = nullptr);
+hipError_t launch_venv_heur_gen(const VenvHeurArgs &h, hipStream_t s,
+                                const VenvItemTable &items);
 // xh_venv_legal: out [N][W], the legal set (all bins where it is empty) of
 // every env's current state; reads a.bins / a.items only
 hipError_t launch_venv_legal(const VenvArgs &a, uint32_t *out, hipStream_t s);

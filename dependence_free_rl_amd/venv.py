@@ -34,6 +34,11 @@ weights=[2, 1, 1], capacity=(5, 7)) draws from up to 16 shapes with per-dim
 capacities, from the same stream positions, and env.set_item_set(items,
 weights) switches the mix during training (a curriculum).
 
+A baseline on the same instance: env.act_heuristic("firstfit") -- or "random",
+"bestfit", "minwaste", the reference's heuristic agents -- is an act() whose
+pick is the heuristic's, in one launch, and heuristic_baseline(ctx, kind, ...)
+plays every env's first episode with it and returns the lengths' statistics.
+
 Mirrors xylo::environment<A,S>::apply / view / reset (rl.h:163-170) with the
 id ranging over the batch, bp::environment (bin_packing.h:46-85) and
 xylo::agent::step (rl.h:325-349).  State lives in HBM; numpy arrays here are
@@ -246,6 +251,24 @@ class VecEnv:
             self.set(VENV_POLICY, policy)
         check(_lib.lib.xh_venv_act(self.h, ptr, _KINDS[kind], _MODES[mode],
                                    1 if write_obs else 0))
+        if fetch:
+            return (self.get(VENV_ACTIONS), self.get(VENV_PCHOICE),
+                    self.get(VENV_REWARD), self.get(VENV_DONE))
+        return None
+
+    def act_heuristic(self, kind, write_obs=False, fetch=False):
+        """One of the reference's heuristic agents as the act of every env, in
+        one launch (xh_venv_act_heuristic): kind "random" | "firstfit" |
+        "bestfit" | "minwaste", scored on the venv's own item set and
+        capacities; then everything act() does after its pick (the record, the
+        mask's words, the episode statistics, OBS if write_obs).  "random"
+        needs policy_draws == 2; the others draw nothing.  Returns (actions,
+        pchoice, reward, done) if fetch."""
+        if kind not in _lib.HEURISTICS:
+            raise ValueError("act_heuristic: kind %r (one of %s)"
+                             % (kind, ", ".join(sorted(_lib.HEURISTICS))))
+        check(_lib.lib.xh_venv_act_heuristic(self.h, _lib.HEURISTICS[kind],
+                                             1 if write_obs else 0))
         if fetch:
             return (self.get(VENV_ACTIONS), self.get(VENV_PCHOICE),
                     self.get(VENV_REWARD), self.get(VENV_DONE))
@@ -816,3 +839,44 @@ class VecEnv:
             self.close()
         except Exception:
             pass
+
+
+def heuristic_baseline(ctx, kind, bins, dims, num_envs, items=None,
+                       weights=None, capacity=None, rng_state=1,
+                       max_steps=100000, row_every=64):
+    """What a heuristic agent scores on an instance: a fresh VecEnv on it
+    (policy_draws 2 for "random", 0 otherwise) with episode statistics on,
+    driven by act_heuristic(kind) until every env has finished its first
+    episode or max_steps steps were taken.  One episode_row() and one
+    synchronising read every row_every steps; no per-step host traffic.
+
+    Returns a dict over the envs' first episodes (one per env, the unbiased
+    sample): "episodes" (the envs that finished one), "len_mean", "len_min",
+    "len_max", "return_mean" / "return_min" / "return_max" (an episode's
+    return is its length - 1; all NaN while episodes == 0),
+    "steps" (launches made) and "finished" (episodes == num_envs)."""
+    if row_every < 1 or max_steps < 1:
+        raise ValueError("heuristic_baseline: row_every and max_steps >= 1")
+    env = VecEnv(ctx, num_envs, bins=bins, dims=dims, rng_state=rng_state,
+                 policy_draws=2 if kind == "random" else 0, items=items,
+                 weights=weights, capacity=capacity)
+    try:
+        env.set_episode_stats(2)
+        steps, done = 0, False
+        while steps < max_steps and not done:
+            for _ in range(min(row_every, max_steps - steps)):
+                env.act_heuristic(kind)
+                steps += 1
+            env.episode_row()
+            row = env.episode_stats(count=1)[0]
+            done = int(row[_lib.VEP_ENVS_FINISHED]) == num_envs
+        first = env.first_episode_lengths().astype(np.int64)
+    finally:
+        env.close()
+    k = int(first.size)
+    nan = float("nan")
+    mean = float(first.sum()) / k if k else nan
+    lo, hi = (int(first.min()), int(first.max())) if k else (nan, nan)
+    return {"kind": kind, "episodes": k, "len_mean": mean, "len_min": lo,
+            "len_max": hi, "return_mean": mean - 1.0, "return_min": lo - 1,
+            "return_max": hi - 1, "steps": steps, "finished": k == num_envs}

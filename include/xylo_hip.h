@@ -698,7 +698,8 @@ int xh_venv_set(xh_venv *v, int which, const void *host, size_t bytes);
  * general kernels.  xh_venv_get_item_set returns the set in use (the default
  * set for a venv created without one).
  * The trainer, xh_config, the evaluators and xh_heuristic_evaluate keep the
- * reference's instance. */
+ * reference's instance; the venv's own heuristics (xh_venv_act_heuristic)
+ * run on the venv's set and capacities. */
 enum { XH_ITEMS_MAX = 16 };
 typedef struct {
   int num_items;                 /* K, 1..XH_ITEMS_MAX                      */
@@ -752,6 +753,53 @@ enum { XH_ACT_PROBS = 0, XH_ACT_LOGITS = 1 };
 enum { XH_ACT_SAMPLE = 0, XH_ACT_ARGMAX = 1 };
 int xh_venv_act(xh_venv *v, const float *policy_dev, int kind, int mode,
                 int write_obs);
+/* The reference's heuristic agents as an act of the venv: per env, pick a bin
+ * by heuristic XH_HEUR_RANDOM / FIRSTFIT / BESTFIT / MINWASTE (random_policy
+ * rl.h:305-316, firstfit_agent.cc, bestfit_agent.cc, minwaste_agent.cc) from
+ * the env's own state, then do what xh_venv_act does after its pick -- one
+ * launch, asynchronous on the context's stream, on every venv shape and on
+ * the venv's own item set and capacities.  No policy row is read.
+ *
+ * Scores of bin b, with fits = bins[b][d] >= item[d] for every d < D (the
+ * reference's policies, generalised to D dims, a capacity per dim and items
+ * with zero entries):
+ *   FIRSTFIT  fits ? 1.0f : 0.0f.
+ *   BESTFIT   -1.0f where the bin does not fit; otherwise the f32 sum over d =
+ *     0 .. D-1, in that order, of term_d = item[d] == 0 ? +0.0f :
+ *     float(item[d]) / float(bins[b][d]), a correctly rounded IEEE f32
+ *     division.  (The zero-entry rule is this library's: an xh_item_set allows
+ *     item[k][d] == 0, where the reference's expression would form 0 / 0.)
+ *   MINWASTE  -1.0f where the bin does not fit; otherwise, with r_d =
+ *     bins[b][d] - item[d]: 0.0f when exactly one d has r_d == capacity[d] / 2
+ *     (integer division) and every other d has r_d == 0, else 1.0f.
+ * The pick of these three is the first maximum, ties to the lowest bin
+ * (from_vector_deterministic); they draw nothing and skip the venv's
+ * policy_draws as XH_ACT_ARGMAX does; PCHOICE[e] = 1.0f.
+ * RANDOM is, bit for bit, xh_venv_act(XH_ACT_PROBS, XH_ACT_SAMPLE) on a row
+ * whose B entries are all (float)(1.0 / B): two draws from the env's stream,
+ * PCHOICE that entry's bits; XH_ERR_INVALID unless the venv has policy_draws
+ * == 2.
+ * No env can be refused: there is no caller row.
+ *
+ * After the pick everything is xh_venv_act's: ACTIONS, apply, REWARD / DONE,
+ * reset on game over, the jump over the other envs' draws, OBS if write_obs
+ * != 0, the record's slot at the cursor (action, p_old, reward, done and the
+ * state before the step; XH_ERR_STATE on a full record) and the episode
+ * counters while episode statistics are on.
+ *
+ * With the action mask on (xh_venv_set_action_mask) the call writes eff(e)
+ * into the legal-word record as xh_venv_act does.  The three deterministic
+ * picks are unchanged by it: in each of them every fitting bin scores above
+ * every bin that does not fit (1 > 0; a sum of terms >= 0 with one > 0, or 0
+ * or 1, > -1), so where legal(e) is not empty the first maximum lies in it,
+ * and where it is empty eff(e) is all B bins.  RANDOM becomes uniform over
+ * eff(e): the premasked constant row (+0.0f outside eff(e)) through the same
+ * sampler, so PCHOICE stays (float)(1.0 / B).
+ * With a distribution record on (xh_venv_set_record_distrib) the call returns
+ * XH_ERR_STATE and launches nothing: a heuristic has no distribution to
+ * record.  A heuristic outside the enum is XH_ERR_INVALID. */
+int xh_venv_act_heuristic(xh_venv *v, int heuristic /* XH_HEUR_* */,
+                          int write_obs);
 /* The trajectory record, written by xh_venv_act's own launch (no further
  * launch, no host synchronisation).  steps = T > 0 allocates T slots
  * (zero-filled, cursor 0, replacing an earlier record); steps = 0 turns the

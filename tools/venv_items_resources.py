@@ -2,7 +2,7 @@
 """Register, scratch and code-size figures of the venv step / act kernels,
 from the code object's metadata (cross-compiled; no device needed).
 
-    tools/venv_items_resources.py [--general] [TREE ...]
+    tools/venv_items_resources.py [--general] [--heur] [TREE ...]
 
 For every TREE (default: this one) compiles TREE/dependence_free_rl_amd/csrc/
 venv_kernels.hip for the device only, reads each kernel's .vgpr_count,
@@ -12,7 +12,12 @@ its code bytes from the symbol table, and prints one JSON line per kernel
 it also prints whether the builtin kernels' figures are equal, kernel by
 kernel; --general lists the general instantiations (venv_gen_kernels.o)
 instead -- the check DESIGN.md 8 records for the general item sets, whose
-builtin instantiations are meant to be the parent's code.
+builtin instantiations are meant to be the parent's code.  --heur reads
+venv_heur_kernels.hip (venv_heur_kernel, xh_venv_act_heuristic) instead of
+venv_kernels.hip and, beside each kernel, prints the act kernel of the same
+shape, mask and episode switches (no distribution record) from
+venv_kernels.hip: the heuristic kernel is to need no scratch and no more
+VGPRs than it.
 """
 import json
 import os
@@ -26,14 +31,14 @@ READELF = os.environ.get("READELF", "/opt/rocm/lib/llvm/bin/llvm-readelf")
 ARCH = os.environ.get("ARCH", "gfx950")
 
 
-def kernels(tree, defines=()):
+def kernels(tree, defines=(), unit="venv_kernels.hip"):
     src = os.path.join(tree, "dependence_free_rl_amd", "csrc")
     with tempfile.TemporaryDirectory() as tmp:
         obj = os.path.join(tmp, "venv_kernels.co")
         subprocess.run(
             [HIPCC, "--offload-arch=" + ARCH, "-O3", "-std=c++17",
              "--cuda-device-only", "--no-gpu-bundle-output",
-             "-I" + os.path.join(tree, "include"), "-I" + src, *defines, "-c", os.path.join(src, "venv_kernels.hip"),
+             "-I" + os.path.join(tree, "include"), "-I" + src, *defines, "-c", os.path.join(src, unit),
              "-o", obj], check=True)
         notes = subprocess.run([READELF, "--notes", obj], check=True,
                                capture_output=True, text=True).stdout
@@ -63,11 +68,38 @@ def demangle(names):
     return dict(zip(names, got))
 
 
+def heur(tree, defines):
+    """venv_heur_kernel's figures beside the act kernel's of the same shape."""
+    tab = kernels(tree, defines, "venv_heur_kernels.hip")
+    act = kernels(tree, defines)
+    act = {demangle([n])[n]: v for n, v in act.items()}
+    pretty = demangle(sorted(tab))
+    bad = []
+    for n in sorted(tab, key=pretty.get):
+        name = pretty[n]
+        m = re.match(r"void xh::venv_heur_kernel<(\d+), (\d+), (\w+), (\w+)"
+                     r"(.*)>\(xh::VenvHeurArgs(.*)\)", name)
+        if not m:
+            continue
+        twin = "void xh::venv_act_kernel<%s, %s, false, %s, %s%s>" \
+               "(xh::VenvActArgs%s)" % m.groups()
+        a = act[twin]
+        print(json.dumps({"kernel": name, **tab[n], "act_vgpr": a["vgpr"],
+                          "act_code_bytes": a["code_bytes"]}))
+        if tab[n]["scratch"] or tab[n]["vgpr"] > a["vgpr"]:
+            bad.append(name)
+    print(json.dumps({"heur_kernels": len(tab), "scratch_or_more_vgprs": bad}))
+    return 1 if bad else 0
+
+
 def main():
     general = "--general" in sys.argv[1:]
     defines = ("-DXH_VENV_GEN_TU=1",) if general else ()
     here = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    trees = [t for t in sys.argv[1:] if t != "--general"] or [here]
+    trees = [t for t in sys.argv[1:] if t not in ("--general", "--heur")] \
+        or [here]
+    if "--heur" in sys.argv[1:]:
+        return heur(trees[0], defines)
     tables = []
     for t in trees:  # keyed by the demangled name
         tab = kernels(t, defines)

@@ -43,8 +43,12 @@ from ._lib import (VEP_CALLS, VEP_COUNT, VEP_ENVS_FINISHED,  # noqa: F401
                    VEPS_FIRST, VEPS_RUNNING)
 from .venv import (VecEnv, heuristic_baseline,  # noqa: F401
                    item_set_thresholds, legal_words, pack_legal, unpack_legal)
+from ._lib import (NET_GRAD, NET_M, NET_PARAMS, NET_POLICY,  # noqa: F401
+                   NET_POLICY_LAYERS, NET_V, NET_VALUE)
+from .nets import PolicyNet, ValueNet  # noqa: F401
 
 __all__ = ["Context", "Trainer", "POLICY", "VALUE", "init_policy", "init_value",
            "init_full_policy", "clip_grad_norm", "describe_state", "digest",
            "heuristic_evaluate", "XhError", "runtime_info", "device_count", "VecEnv",
-           "item_set_thresholds", "heuristic_baseline"]
+           "item_set_thresholds", "heuristic_baseline", "PolicyNet",
+           "ValueNet"]

@@ -43,6 +43,9 @@ VKL_KL_SUM, VKL_ROWS, VKL_KL_SQSUM, VKL_COUNT = range(4)
  VEP_RUNNING_SUM, VEP_RUNNING_MAX, VEP_COUNT) = range(13)
 VEPS_RUNNING, VEPS_FIRST, VEPS_COUNT = range(3)
 COPY_H2D, COPY_D2H, COPY_D2D = 0, 1, 2
+# device-resident nets (xh_net_*): the kinds and a net's arrays
+NET_POLICY, NET_VALUE, NET_POLICY_LAYERS = 0, 1, 2
+NET_PARAMS, NET_GRAD, NET_M, NET_V, NET_COUNT = range(5)
 (BUF_BINS, BUF_ITEMS, BUF_ACTION, BUF_POLD, BUF_DONE, BUF_RNG, BUF_V_STATE,
  BUF_V_TERM, BUF_TARGETS, BUF_ADV, BUF_VALUE_GRAD, BUF_POLICY_GRADS,
  BUF_LOGITS, BUF_PROBS, BUF_V_STATE0, BUF_QOLD, BUF_KL, BUF_LEN) = range(18)
@@ -147,7 +150,12 @@ class ItemSet(C.Structure):
 # that need one raise
 _AB_OPTIONAL = ("xh_trainer_table_stats", "xh_item_set_default",
                 "xh_item_set_thresholds", "xh_venv_create_ex",
-                "xh_venv_set_item_set", "xh_venv_get_item_set")
+                "xh_venv_set_item_set", "xh_venv_get_item_set",
+                "xh_net_create", "xh_net_destroy", "xh_net_num_params",
+                "xh_net_get", "xh_net_set", "xh_net_device_ptr",
+                "xh_net_get_step", "xh_net_set_step", "xh_net_forward",
+                "xh_net_backward", "xh_net_set_optimizer", "xh_net_step",
+                "xh_net_set_grid_cap", "xh_net_info")
 
 
 def _load():
@@ -274,6 +282,21 @@ def _load():
                                   C.POINTER(C.c_double),
                                   C.POINTER(C.c_float)]),
         "xh_trainer_forget": (i, [vp]),
+        "xh_net_create": (i, [vp, i, i, i, i, i, C.POINTER(vp)]),
+        "xh_net_destroy": (i, [vp]),
+        "xh_net_num_params": (sz, [vp]),
+        "xh_net_get": (i, [vp, i, vp, sz]),
+        "xh_net_set": (i, [vp, i, vp, sz]),
+        "xh_net_device_ptr": (vp, [vp, i]),
+        "xh_net_get_step": (i, [vp, C.POINTER(C.c_long)]),
+        "xh_net_set_step": (i, [vp, C.c_long]),
+        "xh_net_forward": (i, [vp, vp, C.c_long, vp]),
+        "xh_net_backward": (i, [vp, vp, C.c_long, vp, i]),
+        "xh_net_set_optimizer": (i, [vp, i, C.c_float, C.c_float, C.c_float,
+                                     C.c_float]),
+        "xh_net_step": (i, [vp, C.c_float, vp]),
+        "xh_net_set_grid_cap": (i, [vp, i]),
+        "xh_net_info": (i, [vp, C.c_char_p, sz]),
         "xh_trainer_set_record_last_step": (i, [vp, i]),
         "xh_trainer_set_stats": (i, [vp, i]),
         "xh_trainer_stats_count": (i, [vp, C.POINTER(C.c_long)]),

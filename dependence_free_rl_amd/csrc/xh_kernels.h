@@ -565,6 +565,26 @@ hipError_t launch_venv_ext_reduce(const double *part, int nparts,
                                   int accumulate, double *ext_stats,
                                   hipStream_t s);
 
+// The per-bin policy net of a venv learner (xh_net, net_kernels.hip): the
+// conv1d_1 chain F0 -> H1 -> relu -> H2 -> relu -> 1 over the R = rows * B flat
+// per-bin rows of an observation block, fused; tiles of 64 flat rows, `grid`
+// persistent workgroups (1 <= grid <= net_policy_tiles(R)).
+struct NetPolicyArgs {
+  int F0, H1, H2;
+  const float *params;  // PolicyLayout
+  const float *obs;     // [R][F0]
+  long R;
+  float *logits;        // forward: [R] (out)
+  const float *dout;    // backward: [R] dL/dlogit
+  float *slab;          // backward: [grid][slab_stride] (out), PolicyLayout
+  int slab_stride;
+};
+bool net_policy_shape_supported(int F0, int H1, int H2);
+long net_policy_tiles(long R);
+int net_policy_lds_bytes(int F0, int H1, int H2, int backward);
+hipError_t launch_net_policy_fwd(const NetPolicyArgs &a, int grid, hipStream_t s);
+hipError_t launch_net_policy_bwd(const NetPolicyArgs &a, int grid, hipStream_t s);
+
 // 1 when the kernels were built with the phase-ablation switches
 // (make diag, -DXH_DIAG_ABLATE=1), 0 in the product library.
 int diag_build();

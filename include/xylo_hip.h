@@ -1391,6 +1391,74 @@ int xh_clip_grad_norm(xh_ctx *ctx, float *grad, size_t n, float max_norm,
  * batch): the batch's final states become the next rollout's start states. */
 int xh_trainer_forget(xh_trainer *t);
 
+/* ------------------------------------ device-resident nets (xh_net) ---- */
+/* The reference's two networks as device objects a venv learner calls: the
+ * policy is the per-bin conv1d_1 chain 2D -> h1 -> relu -> h2 -> relu -> 1
+ * (kind XH_NET_POLICY), the value net the full-layer MLP 2BD -> h1 -> relu ->
+ * h2 -> relu -> 1 (XH_NET_VALUE), both in the flat model::parameters() layout
+ * a trainer of the same shape uses, so parameters move between an
+ * xh_trainer, a weights file and a net unchanged.  A net lives on a context
+ * and is not bound to a venv: the item set and the capacities reach it only
+ * through the observations.
+ *
+ * Shapes: bins in {8, 16, 32, 64, 128}, dims in {1, 2, 3}; policy widths
+ * (h1, h2) in {(128,128), (128,64), (64,64), (64,32)}, value widths >= 1;
+ * anything else is XH_ERR_INVALID at create.
+ *
+ * obs_dev: [rows][bins][2 dims] f32, what XH_VENV_OBS and xh_venv_record_obs
+ * write.  Policy out_dev: [rows][bins] logits (no softmax: xh_venv_act with
+ * XH_ACT_LOGITS and the loss head own it); value out_dev: [rows].  dout_dev
+ * has out's shape and may be the block the loss head wrote in place.
+ * xh_net_backward writes the parameter gradient of sum(dout * out) into
+ * XH_NET_GRAD: accumulate = 0 overwrites, accumulate = 1 adds this call's
+ * reduced sum to what is there (one f32 add per entry).  Layer 0 gets no data
+ * gradient.  The policy runs fused (net_policy_fwd_kernel /
+ * net_policy_bwd_kernel: exact f32 MFMA, per-workgroup slabs summed in a
+ * fixed order, no floating-point atomics, the same bits from run to run); the
+ * value net runs the layer launches of xh_model_forward / xh_model_gradient.
+ * XH_NET_POLICY_LAYERS is the policy run through those layer launches as well
+ * (conv1d_1 / relu / conv1d_1 / relu / conv1d_1 over rows * bins points, any
+ * widths >= 1): every activation is materialised, rows * bins * (2 h1 + 2 h2)
+ * floats of scratch and as much again for the backward.  It is the
+ * comparator the fused kernels are measured against (tools/venv_net_time.py),
+ * not a path to train on.
+ *
+ * xh_net_step: global-norm clipping when max_norm > 0 (the launches of
+ * xh_trainer_set_grad_clip with r = 1; {norm, (double)scale} go to
+ * clip_log_dev where that is not NULL), then the optimizer set by
+ * xh_net_set_optimizer (sgd, lr 0 until then) on XH_NET_GRAD; max_norm = 0:
+ * the optimizer launch alone, clip_log_dev untouched.  The step counter t
+ * counts the steps taken (adam's bias correction uses t + 1);
+ * xh_net_set_optimizer zeroes the moments and t.
+ *
+ * forward, backward and step are asynchronous on the context's stream and
+ * neither synchronise nor allocate, except that the first call with more rows
+ * than any before grows the net's scratch (one synchronisation then).
+ * xh_net_get / xh_net_set copy n = xh_net_num_params floats and wait.
+ * xh_net_set_grid_cap: test only, at most `cap` workgroups per policy launch
+ * (0: the default).  xh_net_info: a JSON object {"kind", "kernels", "grid",
+ * "grid_cap", "lds", "slabs"} describing the last forward / backward. */
+typedef struct xh_net xh_net;
+enum { XH_NET_POLICY = 0, XH_NET_VALUE = 1, XH_NET_POLICY_LAYERS = 2 };
+enum { XH_NET_PARAMS = 0, XH_NET_GRAD, XH_NET_M, XH_NET_V, XH_NET_COUNT };
+int xh_net_create(xh_ctx *ctx, int kind, int bins, int dims, int h1, int h2,
+                  xh_net **out);
+int xh_net_destroy(xh_net *n);
+size_t xh_net_num_params(const xh_net *n);
+int xh_net_get(xh_net *n, int which, float *host, size_t count);
+int xh_net_set(xh_net *n, int which, const float *host, size_t count);
+float *xh_net_device_ptr(xh_net *n, int which);
+int xh_net_get_step(xh_net *n, long *t);
+int xh_net_set_step(xh_net *n, long t);
+int xh_net_forward(xh_net *n, const float *obs_dev, long rows, float *out_dev);
+int xh_net_backward(xh_net *n, const float *obs_dev, long rows,
+                    const float *dout_dev, int accumulate);
+int xh_net_set_optimizer(xh_net *n, int kind, float lr, float weight_decay,
+                         float beta1, float beta2);
+int xh_net_step(xh_net *n, float max_norm, double *clip_log_dev);
+int xh_net_set_grid_cap(xh_net *n, int cap);
+int xh_net_info(xh_net *n, char *buf, size_t cap);
+
 /* ---------------------------------------------------------- tensor ---- */
 /* xylo/tensor.{h,cc} on the device, for the drop-in tensor type
  * (include/xylo_compat/xylo/tensor.h): tensors created with on_device = true

@@ -14,7 +14,7 @@ OBJS     := $(SRC)/policy_kernels.o $(SRC)/value_kernels.o \
             $(SRC)/heuristic_kernels.o $(SRC)/dense_kernels.o \
             $(SRC)/pg_kernels.o $(SRC)/venv_kernels.o $(SRC)/venv_gen_kernels.o \
             $(SRC)/venv_heur_kernels.o $(SRC)/venv_heur_gen_kernels.o \
-            $(SRC)/venv_learn_kernels.o \
+            $(SRC)/venv_learn_kernels.o $(SRC)/venv_table_kernels.o \
             $(SRC)/venv_loss_kernels.o $(SRC)/venv_episode_kernels.o \
             $(SRC)/value_net_kernels.o \
             $(SRC)/policy_spec8_kernels.o $(SRC)/policy_spec8_kl_kernels.o \
@@ -49,6 +49,7 @@ HDRS     := $(SRC)/xh_device.h $(SRC)/xh_kernels.h $(SRC)/xh_split.h \
             $(SRC)/xh_digest.h $(SRC)/xh_state_blob.h $(SRC)/xh_trainer.h \
             $(SRC)/xh_host.h $(SRC)/xh_ring.h $(SRC)/xh_logit_table.h \
             $(SRC)/xh_venv_device.h $(SRC)/xh_venv_sample.inc \
+            $(SRC)/xh_venv_table.h \
             include/xylo_hip.h
 
 # Drop-in C++20 layer (include/xylo_compat): the reference's unmodified

@@ -41,8 +41,10 @@ from ._lib import (VEP_CALLS, VEP_COUNT, VEP_ENVS_FINISHED,  # noqa: F401
                    VEP_LEN_MAX, VEP_LEN_MIN, VEP_LEN_SQSUM, VEP_LEN_SUM,
                    VEP_ROW, VEP_RUNNING_MAX, VEP_RUNNING_SUM, VEPS_COUNT,
                    VEPS_FIRST, VEPS_RUNNING)
+from ._lib import VTAB_MAX_ENTRIES, VenvTableInfo  # noqa: F401
 from .venv import (VecEnv, heuristic_baseline,  # noqa: F401
-                   item_set_thresholds, legal_words, pack_legal, unpack_legal)
+                   item_set_table_info, item_set_thresholds, legal_words,
+                   pack_legal, unpack_legal)
 from ._lib import (NET_GRAD, NET_M, NET_PARAMS, NET_POLICY,  # noqa: F401
                    NET_POLICY_LAYERS, NET_V, NET_VALUE)
 from .nets import PolicyNet, ValueNet  # noqa: F401
@@ -51,4 +53,5 @@ __all__ = ["Context", "Trainer", "POLICY", "VALUE", "init_policy", "init_value",
            "init_full_policy", "clip_grad_norm", "describe_state", "digest",
            "heuristic_evaluate", "XhError", "runtime_info", "device_count", "VecEnv",
            "item_set_thresholds", "heuristic_baseline", "PolicyNet",
-           "ValueNet"]
+           "ValueNet", "item_set_table_info", "VenvTableInfo",
+           "VTAB_MAX_ENTRIES"]

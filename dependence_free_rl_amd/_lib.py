@@ -146,6 +146,16 @@ class ItemSet(C.Structure):
         ("weight", C.c_double * ITEMS_MAX)]
 
 
+VTAB_MAX_ENTRIES = 16384
+
+
+class VenvTableInfo(C.Structure):
+    """Mirror of struct xh_venv_table_info."""
+    _fields_ = [
+        ("entries", C.c_int), ("states", C.c_int), ("items", C.c_int),
+        ("rows", C.c_int), ("side", C.c_int * 4)]
+
+
 # calls an A/B library from before them (XH_LIB_PATH) may lack; the wrappers
 # that need one raise
 _AB_OPTIONAL = ("xh_trainer_table_stats", "xh_item_set_default",
@@ -155,7 +165,10 @@ _AB_OPTIONAL = ("xh_trainer_table_stats", "xh_item_set_default",
                 "xh_net_get", "xh_net_set", "xh_net_device_ptr",
                 "xh_net_get_step", "xh_net_set_step", "xh_net_forward",
                 "xh_net_backward", "xh_net_set_optimizer", "xh_net_step",
-                "xh_net_set_grid_cap", "xh_net_info")
+                "xh_net_set_grid_cap", "xh_net_info",
+                "xh_item_set_table_info", "xh_venv_table_info",
+                "xh_venv_table_obs", "xh_venv_act_table",
+                "xh_venv_table_gather", "xh_venv_table_grad")
 
 
 def _load():
@@ -224,6 +237,13 @@ def _load():
         "xh_venv_step": (i, [vp, i]),
         "xh_venv_act": (i, [vp, vp, i, i, i]),
         "xh_venv_act_heuristic": (i, [vp, i, i]),
+        "xh_item_set_table_info": (i, [C.POINTER(ItemSet), i, i,
+                                       C.POINTER(VenvTableInfo)]),
+        "xh_venv_table_info": (i, [vp, C.POINTER(VenvTableInfo)]),
+        "xh_venv_table_obs": (i, [vp, vp]),
+        "xh_venv_act_table": (i, [vp, vp, i, i]),
+        "xh_venv_table_gather": (i, [vp, vp, vp, C.c_long, C.c_long, vp]),
+        "xh_venv_table_grad": (i, [vp, vp, C.c_long, C.c_long, vp, vp, i]),
         "xh_venv_set_record": (i, [vp, i, i]),
         "xh_venv_record_pos": (i, [vp, C.POINTER(C.c_int)]),
         "xh_venv_record_rewind": (i, [vp]),
@@ -349,9 +369,12 @@ for _name, _mirror in (("xh_config", Config), ("xh_eval", Eval),
                        ("xh_layer", Layer), ("xh_venv_adv", VenvAdv),
                        ("xh_venv_loss", VenvLoss),
                        ("xh_venv_loss_ext", VenvLossExt),
-                       ("xh_item_set", ItemSet)):
+                       ("xh_item_set", ItemSet),
+                       ("xh_venv_table_info", VenvTableInfo)):
     if _name == "xh_item_set" and not hasattr(lib, "xh_venv_create_ex"):
         continue  # an A/B library from before item sets
+    if _name == "xh_venv_table_info" and not hasattr(lib, "xh_venv_act_table"):
+        continue  # an A/B library from before logit tables
     if lib.xh_struct_size(_name.encode()) != C.sizeof(_mirror):
         raise ImportError("ctypes mirror of %s is out of date (%d vs %d bytes)"
                           % (_name, C.sizeof(_mirror),

@@ -66,6 +66,8 @@ size_t xh_struct_size(const char *name) {
   if (!std::strcmp(name, "xh_venv_loss_ext")) return sizeof(xh_venv_loss_ext);
   if (!std::strcmp(name, "xh_vep_row")) return XH_VEP_COUNT * sizeof(double);
   if (!std::strcmp(name, "xh_item_set")) return sizeof(xh_item_set);
+  if (!std::strcmp(name, "xh_venv_table_info"))
+    return sizeof(struct xh_venv_table_info);
   return 0;
 }
 

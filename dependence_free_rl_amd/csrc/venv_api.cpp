@@ -4,8 +4,10 @@
 // the trajectory record with its optional distributions and legal words, the
 // learner's side of a recorded window (record_obs / record_ends / advantages,
 // venv_learn_kernels.hip) and the loss head (policy_loss / kl_beta,
-// venv_loss_kernels.hip) and the opt-in episode statistics (set_episode_stats /
-// episode_row, venv_episode_kernels.hip).  A venv holds a reference on its
+// venv_loss_kernels.hip), the opt-in episode statistics (set_episode_stats /
+// episode_row, venv_episode_kernels.hip) and the logit tables (table_info /
+// table_obs / act_table / table_gather / table_grad, venv_table_kernels.hip,
+// xh_venv_table.h).  A venv holds a reference on its
 // context and never touches a trainer.
 #include <hip/hip_runtime.h>
 
@@ -19,6 +21,7 @@
 #include "../../include/xylo_hip.h"
 #include "xh_host.h"
 #include "xh_kernels.h"
+#include "xh_venv_table.h"
 
 using namespace xh::host;
 
@@ -77,6 +80,9 @@ struct xh_venv {
   // ... and xh_venv_policy_loss_ex's ext_stats partials [kVenvLossMaxBlocks]
   // [XH_VEXT_COUNT], at the first call that asks for ext_stats
   double *ext_part = nullptr;
+  // xh_venv_table_grad's scratch, allocated at its first use: the maximum's
+  // bit pattern (16 bytes) and XH_VTAB_MAX_ENTRIES int64 sums
+  void *tab_scratch = nullptr;
   // xh_venv_set_episode_stats (opt-in; everything null / 0 while off): the
   // per-env blocks the step / act / apply launches count into, the row
   // kernel's workgroup partials, and the device ring of XH_VEP_COUNT doubles
@@ -285,6 +291,14 @@ int venv_check_err(xh_venv *v) {
   if (!err) return XH_OK;
   HIPCHK(hipMemsetAsync(v->err, 0, 4, v->ctx->stream));
   HIPCHK(hipStreamSynchronize(v->ctx->stream));
+  if (err & 8)
+    return fail(XH_ERR_INVALID, "venv table: a state outside the table's "
+                "domain (a bin outside [0, capacity], or an item that is none "
+                "of the set's shapes) or a NaN / infinity in dout; those envs, "
+                "output rows or g_dev were left untouched%s%s%s",
+                err & 4 ? ", and a row index was outside its rows" : "",
+                err & 2 ? ", and a policy row was refused" : "",
+                err & 1 ? ", and an action was out of range" : "");
   if (err & 4)
     return fail(XH_ERR_INVALID, "venv: xh_venv_record_obs or "
                 "xh_venv_policy_loss met a row index outside its rows (the "
@@ -671,6 +685,65 @@ int venv_policy_loss(xh_venv *v, const xh_venv_loss *p, bool masked,
   });
 }
 
+// ---- logit tables ----
+// the domain of a checked set; XH_ERR_INVALID, naming E, past the limit
+int table_domain(const xh_item_set &s, int D, xh::VenvTabDomain *m) {
+  const xh::vt::Domain d = xh::vt::domain(s.capacity, D, s.num_items);
+  if (d.entries > XH_VTAB_MAX_ENTRIES)
+    return fail(XH_ERR_INVALID, "venv table: the set's domain has E = %ld "
+                "entries (%d items x %d bin states), the limit is %d "
+                "(XH_VTAB_MAX_ENTRIES); such a venv keeps the per-row calls",
+                d.entries, d.K, d.states, XH_VTAB_MAX_ENTRIES);
+  *m = xh::VenvTabDomain{};
+  m->D = D;
+  m->K = d.K;
+  for (int i = 0; i < 4; ++i) m->side[i] = d.side[i];
+  m->states = d.states;
+  m->entries = d.entries;
+  return XH_OK;
+}
+
+void table_info(const xh::VenvTabDomain &m, int B,
+                struct xh_venv_table_info *out) {
+  out->entries = (int)m.entries;
+  out->states = m.states;
+  out->items = m.K;
+  out->rows = (int)xh::vt::rows(m.entries, B);
+  for (int d = 0; d < 4; ++d) out->side[d] = m.side[d];
+}
+
+// what xh_venv_table_gather and xh_venv_table_grad share: the domain and
+// xh_venv_record_obs's checks and addressing of the STATE view's rows
+int table_rows(const xh_venv *v, const char *what, const int32_t *rows_dev,
+               long first, long count, xh::VenvTabRowArgs *a) {
+  CHK(table_domain(v->items, v->env.D, &a->m));
+  if (!v->rec[XH_VREC_BINS].ptr)
+    return fail(XH_ERR_STATE, "%s: %s", what,
+                v->rec_steps > 0 ? "the record was made without states "
+                                   "(xh_venv_set_record's with_states)"
+                                 : "no record (xh_venv_set_record)");
+  if (first < 0 || count < 0)
+    return fail(XH_ERR_INVALID, "%s: first %ld, count %ld", what, first, count);
+  const long P = v->rec_pos;
+  const long total = (P + 1) * (long)v->N;
+  if (count > 0 && !rows_dev && first + count > total)
+    return fail(XH_ERR_INVALID, "%s: rows %ld .. %ld of %ld (cursor %ld, %d "
+                "envs)", what, first, first + count - 1, total, P, v->N);
+  a->B = v->env.B;
+  a->D = v->env.D;
+  a->N = v->N;
+  a->P = (int)P;
+  a->rec_bins = v->rec_as<const int8_t>(XH_VREC_BINS);
+  a->rec_items = v->rec_as<const int8_t>(XH_VREC_ITEMS);
+  a->cur_bins = (const int8_t *)v->buf[XH_VENV_BINS];
+  a->cur_items = (const int8_t *)v->buf[XH_VENV_ITEMS];
+  a->rows = rows_dev;
+  a->first = first;
+  a->count = count;
+  a->err = v->err;
+  return XH_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -732,6 +805,8 @@ int xh_venv_create_ex(xh_ctx *ctx, int num_envs, int bins, int dims,
       v->table = item_set_table(v->items, dims);
     } else {
       xh_item_set_default(&v->items, dims);
+      // the table calls run the general kernels on the default set
+      v->table = item_set_table(v->items, dims);
     }
     v->N = num_envs;
     v->Ng = num_envs_global;
@@ -811,6 +886,7 @@ int xh_venv_destroy(xh_venv *v) {
     if (v->loss_part) (void)hipFree(v->loss_part);
     if (v->kl_part) (void)hipFree(v->kl_part);
     if (v->ext_part) (void)hipFree(v->ext_part);
+    if (v->tab_scratch) (void)hipFree(v->tab_scratch);
     if (v->legal_buf) (void)hipFree(v->legal_buf);
     venv_free_episode_stats(v);
     venv_free_record(v);
@@ -1259,6 +1335,130 @@ int xh_venv_kl_beta(xh_venv *v, const double *kl_stats_dev, float d_targ,
     if (e != hipSuccess)
       return fail(XH_ERR_HIP, "venv kl beta: %s", hipGetErrorString(e));
     return XH_OK;
+  });
+}
+
+// ---- logit tables (venv_table_kernels.hip, xh_venv_table.h) ----
+int xh_item_set_table_info(const xh_item_set *s, int dims, int bins,
+                           struct xh_venv_table_info *out) {
+  return guard([&]() -> int {
+    if (!out) return fail(XH_ERR_INVALID, "venv table: null out");
+    CHK(item_set_check(s, dims));
+    if (!xh::venv_shape_supported(bins, dims))
+      return fail(XH_ERR_INVALID, "venv table: bins %d (8/16/32/64/128), dims "
+                  "%d (1..3)", bins, dims);
+    xh::VenvTabDomain m;
+    CHK(table_domain(*s, dims, &m));
+    table_info(m, bins, out);
+    return XH_OK;
+  });
+}
+
+int xh_venv_table_info(const xh_venv *v, struct xh_venv_table_info *out) {
+  return guard([&]() -> int {
+    if (!v || !out) return fail(XH_ERR_INVALID, "null arg");
+    xh::VenvTabDomain m;
+    CHK(table_domain(v->items, v->env.D, &m));
+    table_info(m, v->env.B, out);
+    return XH_OK;
+  });
+}
+
+int xh_venv_table_obs(xh_venv *v, float *obs_dev) {
+  return venv_call(v, [&]() -> int {
+    xh::VenvTabDomain m;
+    CHK(table_domain(v->items, v->env.D, &m));
+    if (!obs_dev || (reinterpret_cast<uintptr_t>(obs_dev) & 15))
+      return fail(XH_ERR_INVALID, "venv table obs: obs_dev must be 16-byte "
+                  "aligned");
+    HIPCHK(hipSetDevice(v->ctx->device));
+    const long total = xh::vt::rows(m.entries, v->env.B) * v->env.B;
+    return venv_timed(v, [&] {
+      return xh::launch_venv_table_obs(m, v->table, total, obs_dev,
+                                       v->ctx->stream);
+    });
+  });
+}
+
+int xh_venv_act_table(xh_venv *v, const float *table_dev, int mode,
+                      int write_obs) {
+  return venv_call(v, [&]() -> int {
+    xh::VenvTabActArgs h{};
+    CHK(table_domain(v->items, v->env.D, &h.m));
+    if (mode != XH_ACT_SAMPLE && mode != XH_ACT_ARGMAX)
+      return fail(XH_ERR_INVALID, "venv act table: mode %d (XH_ACT_SAMPLE / "
+                  "ARGMAX)", mode);
+    if (mode == XH_ACT_SAMPLE && v->policy_draws != 2)
+      return fail(XH_ERR_INVALID, "venv act table: sampling takes two draws "
+                  "per env and step, the venv was created with policy_draws %d",
+                  v->policy_draws);
+    if (!table_dev || (reinterpret_cast<uintptr_t>(table_dev) & 3))
+      return fail(XH_ERR_INVALID, "venv act table: table_dev must be a 4-byte "
+                  "aligned device pointer to %ld floats", h.m.entries);
+    CHK(venv_act_ready(v, "venv act table"));
+    h.a = venv_act_args(v, write_obs != 0);
+    h.a.logits = 1;
+    h.a.argmax = mode == XH_ACT_ARGMAX;
+    h.a.rec_distrib = v->rec_as<float>(kRecDistrib);
+    h.table = table_dev;
+    return venv_act_done(v, venv_timed(v, [&] {
+      return xh::launch_venv_act_table(h, v->ctx->stream, v->table);
+    }));
+  });
+}
+
+int xh_venv_table_gather(xh_venv *v, const float *table_dev,
+                         const int32_t *rows_dev, long first, long count,
+                         float *out_dev) {
+  return venv_call(v, [&]() -> int {
+    xh::VenvTabRowArgs a{};
+    CHK(table_rows(v, "venv table gather", rows_dev, first, count, &a));
+    if (!table_dev || (reinterpret_cast<uintptr_t>(table_dev) & 3))
+      return fail(XH_ERR_INVALID, "venv table gather: table_dev must be a "
+                  "4-byte aligned device pointer to %ld floats", a.m.entries);
+    if (count == 0) return XH_OK;
+    if (!out_dev || (reinterpret_cast<uintptr_t>(out_dev) & 15))
+      return fail(XH_ERR_INVALID, "venv table gather: out_dev must be 16-byte "
+                  "aligned (the kernel writes 16-byte stores)");
+    HIPCHK(hipSetDevice(v->ctx->device));
+    a.table = table_dev;
+    a.out = out_dev;
+    return venv_timed(v, [&] {
+      return xh::launch_venv_table_gather(a, v->ctx->stream, v->table);
+    });
+  });
+}
+
+int xh_venv_table_grad(xh_venv *v, const int32_t *rows_dev, long first,
+                       long count, const float *dout_dev, float *g_dev,
+                       int accumulate) {
+  return venv_call(v, [&]() -> int {
+    xh::VenvTabRowArgs a{};
+    CHK(table_rows(v, "venv table grad", rows_dev, first, count, &a));
+    if (!g_dev || (reinterpret_cast<uintptr_t>(g_dev) & 15))
+      return fail(XH_ERR_INVALID, "venv table grad: g_dev must be 16-byte "
+                  "aligned");
+    HIPCHK(hipSetDevice(v->ctx->device));
+    hipStream_t s = v->ctx->stream;
+    const long total = xh::vt::rows(a.m.entries, v->env.B) * v->env.B;
+    if (count == 0) {  // no addends: G = 0
+      if (!accumulate) HIPCHK(hipMemsetAsync(g_dev, 0, (size_t)total * 4, s));
+      return XH_OK;
+    }
+    if (!dout_dev || (reinterpret_cast<uintptr_t>(dout_dev) & 15))
+      return fail(XH_ERR_INVALID, "venv table grad: dout_dev must be 16-byte "
+                  "aligned (the kernel reads 16-byte pieces)");
+    if (!v->tab_scratch)
+      HIPCHK(hipMalloc(&v->tab_scratch, 16 + (size_t)XH_VTAB_MAX_ENTRIES * 8));
+    HIPCHK(hipMemsetAsync(v->tab_scratch, 0, 16 + (size_t)a.m.entries * 8, s));
+    a.dout = dout_dev;
+    a.maxbits = static_cast<uint32_t *>(v->tab_scratch);
+    a.acc = reinterpret_cast<unsigned long long *>(
+        static_cast<char *>(v->tab_scratch) + 16);
+    return venv_timed(v, [&] {
+      return xh::launch_venv_table_grad(a, total, accumulate != 0, g_dev, s,
+                                        v->table);
+    });
   });
 }
 

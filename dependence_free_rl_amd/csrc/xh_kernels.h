@@ -439,6 +439,56 @@ hipError_t launch_venv_heur(const VenvHeurArgs &h, hipStream_t s,
                             const VenvItemTable *items = nullptr);
 hipError_t launch_venv_heur_gen(const VenvHeurArgs &h, hipStream_t s,
                                 const VenvItemTable &items);
+// Logit tables (xh_venv_table_*, venv_table_kernels.hip; the domain:
+// xh_venv_table.h).  Every launch takes the item table by reference: a venv
+// without a set passes the default set's.
+struct VenvTabDomain {
+  int D, K;       // dims, the set's items
+  int side[4];    // capacity[d] + 1, 1 past D
+  int states;     // S = prod side[d]
+  long entries;   // E = K S, 1 .. XH_VTAB_MAX_ENTRIES
+};
+// observations of the table's `total` = R B per-bin rows, [R][B][2D]
+hipError_t launch_venv_table_obs(const VenvTabDomain &m,
+                                 const VenvItemTable &t, long total,
+                                 float *obs, hipStream_t s);
+// xh_venv_act_table (venv_act_table_kernel): the act launch with the row
+// gathered from `table` ([>= E] floats) inside it.  a.policy and a.logits are
+// not read (the rows are logits); a.argmax and a.rec_distrib as in the act.
+struct VenvTabActArgs {
+  VenvActArgs a;
+  VenvTabDomain m;
+  const float *table;
+};
+hipError_t launch_venv_act_table(const VenvTabActArgs &h, hipStream_t s,
+                                 const VenvItemTable &t);
+// `count` rows of the record's STATE view (VenvObsArgs' addressing): the
+// gather reads table and writes out; the gradient sum reads dout and adds
+// into acc through maxbits.
+struct VenvTabRowArgs {
+  int B, D, N;
+  int P;                      // the record's cursor
+  VenvTabDomain m;
+  const int8_t *rec_bins;     // [P][N][B][D]
+  const int8_t *rec_items;    // [P][N][4]
+  const int8_t *cur_bins;     // [N][B][D]
+  const int8_t *cur_items;    // [N][4]
+  const int32_t *rows;        // index list or nullptr (rows first ..)
+  long first, count;
+  const float *table;         // [>= E] (gather)
+  float *out;                 // [count][B], 16-byte aligned (gather)
+  const float *dout;          // [count][B], 16-byte aligned (grad)
+  uint32_t *maxbits;          // one word, zeroed before the launch (grad)
+  unsigned long long *acc;    // [E] int64 sums, zeroed before the launch (grad)
+  int *err;                   // bit 4: an index outside the view's rows; bit
+                              // 8: a state outside the domain, a NaN / inf dout
+};
+hipError_t launch_venv_table_gather(const VenvTabRowArgs &a, hipStream_t s,
+                                    const VenvItemTable &t);
+// G into g [total = R B floats] (added where accumulate): three launches
+hipError_t launch_venv_table_grad(const VenvTabRowArgs &a, long total,
+                                  int accumulate, float *g, hipStream_t s,
+                                  const VenvItemTable &t);
 // xh_venv_legal: out [N][W], the legal set (all bins where it is empty) of
 // every env's current state; reads a.bins / a.items only
 hipError_t launch_venv_legal(const VenvArgs &a, uint32_t *out, hipStream_t s);

@@ -153,6 +153,27 @@ def item_set_thresholds(items, weights=None, capacity=None):
                           dims)["thresholds"]
 
 
+def _table_info_dict(ti, dims):
+    return {"entries": ti.entries, "states": ti.states, "items": ti.items,
+            "rows": ti.rows,
+            "side": np.array(ti.side[:dims], np.int32)}
+
+
+def item_set_table_info(items, weights=None, capacity=None, bins=64):
+    """The logit-table domain of an item set on `bins` bins
+    (xh_item_set_table_info; host only): a dict of entries E = K *
+    prod(capacity[d] + 1), states, items K, rows R = ceil(E / bins) and side
+    int32 [D].  XhError for an invalid set and for E above
+    VTAB_MAX_ENTRIES."""
+    it = np.asarray(items)
+    dims = 1 if it.ndim == 1 else it.shape[1]
+    s = _item_set(items, weights, capacity, dims)
+    ti = _lib.VenvTableInfo()
+    check(_lib.lib.xh_item_set_table_info(C.byref(s), dims, bins,
+                                          C.byref(ti)))
+    return _table_info_dict(ti, dims)
+
+
 class VecEnv:
     """xh_venv: N envs of B bins x D dims stepped by one kernel per call."""
 
@@ -439,6 +460,122 @@ class VecEnv:
         if out is not None:
             return None
         return self._download(dst, np.float32, (count, B, 2 * D))
+
+    # ---- logit tables: act and train on (bin state, item) ------------------
+    def table_info(self):
+        """The domain of the venv's present item set (xh_venv_table_info): a
+        dict of entries E = K * prod(capacity[d] + 1), states S, items K, rows
+        R = ceil(E / B) and side int32 [D].  XhError where E is past
+        VTAB_MAX_ENTRIES: such a venv keeps the per-row calls."""
+        ti = _lib.VenvTableInfo()
+        check(_lib.lib.xh_venv_table_info(self.h, C.byref(ti)))
+        return _table_info_dict(ti, self.D)
+
+    def table_obs(self, out=None):
+        """The table's observations (xh_venv_table_obs): [R][B][2D] float32,
+        flat per-bin row e the observation of entry e, zeros from E on.  A
+        per-bin network's forward on them, R rows, is the table: [R * B]
+        logits.  out: an integer device pointer (16-byte aligned; nothing is
+        returned), or None for a host array."""
+        R = self.table_info()["rows"]
+        dst = out if out is not None else self._scratch(
+            "tab_obs", R * self.B * 2 * self.D * 4)
+        check(_lib.lib.xh_venv_table_obs(self.h, int(dst)))
+        if out is not None:
+            return None
+        return self._download(dst, np.float32, (R, self.B, 2 * self.D))
+
+    def _table_ptr(self, table):
+        if isinstance(table, (int, np.integer)):
+            return int(table)
+        E = self.table_info()["entries"]
+        t = np.ascontiguousarray(table, np.float32).reshape(-1)
+        if t.size < E:
+            raise ValueError("table: %d floats, the domain has %d entries"
+                             % (t.size, E))
+        ptr = self._scratch("tab_table", t.nbytes)
+        self._upload(ptr, t)
+        return ptr
+
+    def _table_rows(self, what, rows, first, count):
+        """(rows_ptr, first, count) of the STATE view's rows, as
+        record_obs()."""
+        if rows is None:
+            if count is None:
+                count = (self.record_pos() + 1) * self.N - first
+            return None, first, count
+        if isinstance(rows, (int, np.integer)):
+            if count is None:
+                raise ValueError("%s: count is needed with a device pointer "
+                                 "to the rows" % what)
+            return int(rows), first, count
+        r = np.ascontiguousarray(rows, np.int32).reshape(-1)
+        if count is None:
+            count = r.size - first
+        if first < 0 or count < 0 or first + count > r.size:
+            raise ValueError("%s: rows %d .. %d of a list of %d"
+                             % (what, first, first + count - 1, r.size))
+        ptr = self._scratch("tab_rows", r.nbytes)
+        self._upload(ptr, r)
+        return ptr, first, count
+
+    def act_table(self, table, mode="sample", write_obs=False, fetch=False):
+        """act(kind="logits") on the rows z[b] = table[entry(bins[b], item)],
+        gathered inside the launch (xh_venv_act_table): no policy row is
+        formed or read.  table: a host array of at least E floats (uploaded)
+        or an integer device pointer, e.g. where pol.forward(table_obs, R,
+        out=ptr) wrote.  Everything after the row is act()'s.  Returns
+        (actions, pchoice, reward, done) if fetch."""
+        check(_lib.lib.xh_venv_act_table(self.h, self._table_ptr(table),
+                                         _MODES[mode], 1 if write_obs else 0))
+        if fetch:
+            return (self.get(VENV_ACTIONS), self.get(VENV_PCHOICE),
+                    self.get(VENV_REWARD), self.get(VENV_DONE))
+        return None
+
+    def table_logits(self, table, rows=None, first=0, count=None, out=None):
+        """The logits of recorded rows from the table (xh_venv_table_gather):
+        [count][B] float32, what policy_loss(kind="logits") takes.  rows /
+        first / count as record_obs(view="state"); table as act_table().  out:
+        an integer device pointer (16-byte aligned; nothing is returned), or
+        None for a host array."""
+        tptr = self._table_ptr(table)
+        rows_ptr, first, count = self._table_rows("table_logits", rows, first,
+                                                  count)
+        dst = out if out is not None else self._scratch(
+            "tab_logits", count * self.B * 4)
+        check(_lib.lib.xh_venv_table_gather(self.h, tptr, rows_ptr, first,
+                                            count, int(dst)))
+        if out is not None:
+            return None
+        return self._download(dst, np.float32, (count, self.B))
+
+    def table_grad(self, dout, rows=None, first=0, count=None,
+                   accumulate=False, out=None):
+        """G[e] = the sum of dout[j][b] over the minibatch's (row, bin) pairs
+        whose entry is e (xh_venv_table_grad): float32 [R * B], 0 where no row
+        touches and from E on; an exact integer sum, the same bits from run to
+        run.  dout [count][B]: a host array or an integer device pointer, e.g.
+        policy_loss()'s grad.  accumulate adds to what `out` (or, with out
+        None, the previous call's block) holds.  net.backward(table_obs, G,
+        rows=R) is then the parameter gradient of the whole minibatch.  out:
+        an integer device pointer (16-byte aligned; nothing is returned), or
+        None for a host array."""
+        if not isinstance(dout, (int, np.integer)):
+            dout = np.ascontiguousarray(dout, np.float32).reshape(-1, self.B)
+            if count is None and rows is None:
+                count = dout.shape[0]
+        rows_ptr, first, count = self._table_rows("table_grad", rows, first,
+                                                  count)
+        dptr = self._staged("tab_dout", dout, np.float32, (count, self.B))
+        total = self.table_info()["rows"] * self.B
+        dst = out if out is not None else self._scratch("tab_g", total * 4)
+        check(_lib.lib.xh_venv_table_grad(self.h, rows_ptr, first, count,
+                                          dptr, int(dst),
+                                          1 if accumulate else 0))
+        if out is not None:
+            return None
+        return self._download(dst, np.float32, (total,))
 
     def record_ends(self):
         """The ended transitions of the recorded slots (xh_venv_record_ends):

@@ -5,6 +5,7 @@ and every stage between them is a launch of the venv chain.
 
     python examples/venv_ppo.py
     python examples/venv_ppo.py --bins 16 --envs 2048 --iterations 60
+    python examples/venv_ppo.py --table
 
 Per iteration: T masked act() steps from PolicyNet.forward(venv) with the
 record on; record_obs of the window; ValueNet.forward; advantages (GAE and TD
@@ -14,7 +15,16 @@ forward -> policy_loss(clipped, legal, ent_coef, value head) -> backward
 episode_row().  Every `--eval-every` iterations the current policy plays a
 fresh VecEnv greedily until every env has finished its first episode (one
 episode per env: the unbiased sample), and that first-episode return is
-printed beside heuristic_baseline(...) of the same item set."""
+printed beside heuristic_baseline(...) of the same item set.
+
+--table (opt-in) runs the policy on its logit table instead of on per-bin
+rows: a per-bin logit depends on (bin state, item) alone, E = K * prod(capacity
++ 1) = 308 points for this set, so PolicyNet.forward(table_obs) once per
+iteration and once per epoch replaces every per-row forward; the rollout is
+act_table(), the minibatches are table_logits -> policy_loss -> table_grad
+(accumulating), and one PolicyNet.backward(table_obs, G) per step gives the
+epoch's parameter gradient.  The value net sees whole observations and keeps
+its path."""
 import argparse
 import os
 import sys
@@ -72,6 +82,8 @@ def main():
     ap.add_argument("--eval-envs", type=int, default=512)
     ap.add_argument("--eval-max-steps", type=int, default=4096)
     ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--table", action="store_true",
+                    help="act and train the policy on its logit table")
     a = ap.parse_args()
 
     from dependence_free_rl_amd import (VENV_POLICY, VLOSS_CLIPPED,
@@ -99,9 +111,18 @@ def main():
     venv.observe()
     rng = np.random.default_rng(a.seed)
     total = T * N
+    if a.table:
+        info = venv.table_info()
+        tobs = venv.table_obs()  # [R][B][2D], fixed while the set is
+        print("logit table: %d entries, %d rows of %d bins"
+              % (info["entries"], info["rows"], B), flush=True)
     for it in range(a.iterations):
         venv.rewind()
-        for _ in range(T):
+        if a.table:
+            table = pol.forward(tobs)  # once per iteration
+            for _ in range(T):  # the value net reads the record: no OBS
+                venv.act_table(table)
+        for _ in range(0 if a.table else T):
             pol.forward(venv, out=venv.device_ptr(VENV_POLICY))
             venv.act(None, kind="logits", write_obs=True, fetch=False)
         states = venv.record_obs("state")  # [(T + 1) N][B][2D]
@@ -110,19 +131,30 @@ def main():
                               returns=("adv", "td_target"))
         for epoch in range(a.epochs):
             perm = rng.permutation(total).astype(np.int32)
+            if a.table:
+                table = pol.forward(tobs)  # once per epoch
             for first in range(0, total, a.minibatch):
                 count = min(a.minibatch, total - first)
                 obs = venv.record_obs("state", rows=perm, first=first,
                                       count=count)
+                logits = venv.table_logits(
+                    table, rows=perm, first=first,
+                    count=count) if a.table else pol.forward(obs)
                 res = venv.policy_loss(
-                    pol.forward(obs), adv["adv"], kind="logits",
+                    logits, adv["adv"], kind="logits",
                     loss="clipped", rows=perm, first=first, count=count,
                     scale=1.0 / total, legal=True, ent_coef=a.ent_coef,
                     values=val.forward(obs), target=adv["td_target"],
                     value_scale=1.0 / total, want_stats=True,
                     accumulate=first > 0)
-                pol.backward(obs, res["grad"], accumulate=first > 0)
+                if a.table:
+                    G = venv.table_grad(res["grad"], rows=perm, first=first,
+                                        count=count, accumulate=first > 0)
+                else:
+                    pol.backward(obs, res["grad"], accumulate=first > 0)
                 val.backward(obs, res["dvalue"], accumulate=first > 0)
+            if a.table:  # the epoch's gradient: one backward on the table
+                pol.backward(tobs, G.reshape(info["rows"], B))
             pol.step(max_norm=a.max_norm)
             val.step(max_norm=a.max_norm)
         venv.episode_row()

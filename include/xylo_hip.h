@@ -1199,6 +1199,97 @@ int xh_venv_policy_loss_ex(xh_venv *v, const xh_venv_loss *a,
  * finite or not positive. */
 int xh_venv_kl_beta(xh_venv *v, const double *kl_stats_dev, float d_targ,
                     float *beta_dev, float *log_dev);
+/* Logit tables: act and train on (bin state, item) instead of per-bin rows.
+ *
+ * A per-bin logit (xh_net's policy, or any network of the caller's that
+ * shares its weights over the bins) depends on (bins[b][0..D), item[0..D))
+ * alone.  Every bin value a venv stores lies in [0, capacity[d]] -- the launch
+ * that takes a bin below zero resets the env -- and the item is one of the
+ * set's K shapes, so the policy is a function on
+ *   E = K * prod_d (capacity[d] + 1)
+ * points: 162 for the reference's instance at D = 2, against N * B per-bin
+ * rows per env step.  The domain (csrc/xh_venv_table.h):
+ *   side[d] = capacity[d] + 1, S = prod_d side[d],
+ *   s = (b0 * side[1] + b1) * side[2] + b2 with the unused dims dropped,
+ *   e = k * S + s, k the first shape of the set equal to the item,
+ * laid out as R = ceil(E / B) observation rows of B per-bin rows each, so the
+ * network's own forward and backward run on it: flat per-bin row e of [R][B]
+ * is entry e, the tail from E on is padding.  A venv created without a set
+ * has xh_item_set_default's domain.  E is at most XH_VTAB_MAX_ENTRIES (a 3-D
+ * venv at capacity 8 with 16 items has 11664): a set past it is
+ * XH_ERR_INVALID, with a message that names E, from every call below, and such
+ * a venv keeps the per-row chain.
+ *
+ * xh_item_set_table_info: host only, no device (as xh_item_set_thresholds):
+ *   the domain of a valid set at dims / bins.  xh_venv_table_info: the same
+ *   for the venv's present set.
+ * xh_venv_table_obs: obs_dev [R][B][2 dims] f32, 16-byte aligned: row e is
+ *   entry e's observation, float(b[d]) / float(capacity[d]) and float(item[d])
+ *   / float(capacity[d]) as IEEE f32 divisions (OBS's expressions and bits);
+ *   the rows from E on are zero.  xh_net_forward(n, obs_dev, R, table_dev)
+ *   then leaves the table in table_dev's [R * B] floats.
+ * xh_venv_act_table: xh_venv_act(XH_ACT_LOGITS, mode) on the row z[b] =
+ *   table_dev[e(bins[b], item)], gathered inside the launch from the int8 bins
+ *   the kernel holds anyway; no policy row is read.  Everything after the row
+ *   is xh_venv_act's, bit for bit: the mask, the softmax, the sampler or the
+ *   first maximum, apply, REWARD / DONE, the reset, the record's slot, the
+ *   distribution record, the legal words, the episode counters and OBS; and so
+ *   are its argument rules (policy_draws == 2 for XH_ACT_SAMPLE, XH_ERR_STATE
+ *   on a full record).  table_dev: at least E floats, 4-byte aligned.
+ * xh_venv_table_gather: out_dev [count][B] (16-byte aligned) = the logits of
+ *   `count` rows of the record's XH_VOBS_STATE view, what xh_venv_policy_loss
+ *   takes as XH_ACT_LOGITS.  rows_dev / first / count, the alignment rule and
+ *   a bad index (its output row left untouched, XH_ERR_INVALID at the next
+ *   xh_venv_synchronize) are xh_venv_record_obs's.
+ * xh_venv_table_grad: g_dev [R * B] f32 (16-byte aligned) receives G[e] = the
+ *   sum of dout_dev[j][b] ([count][B], 16-byte aligned, e.g. the loss head's
+ *   grad) over the minibatch's (row, bin) pairs whose entry is e; entries no
+ *   row touches and the tail from E on are 0.  accumulate != 0: g[e] += G[e],
+ *   one f32 add per entry.  xh_net_backward(n, table_obs, R, g_dev, 0) then
+ *   gives the parameter gradient of the whole minibatch -- or of an epoch
+ *   accumulated into g_dev.  count >= 1.
+ *   The sum is exact integer arithmetic (no floating-point atomics; the same
+ *   bits from any grid and any order): with n = count * B, L the least integer
+ *   with 2^L >= n, m = max |dout| over the count * B floats and ex the integer
+ *   with 2^(ex-1) <= m < 2^ex: s = 62 - L - ex, q = llrint((double)dout * 2^s)
+ *   (the product exact, the rounding to nearest even), the q of an entry added
+ *   as 64-bit integers, G[e] = (float)((double)sum * 2^-s), both conversions to
+ *   nearest even; m = 0 gives G = 0.  The error of an entry with n_e addends is
+ *   at most n_e * 2^(-s-1) plus the two final roundings.
+ *
+ * Out-of-domain input never reads outside the table: an entry is formed only
+ * from values that passed the checks.  A bin outside [0, capacity[d]]
+ * (possible after xh_venv_apply without a reset, or xh_venv_set) or an item
+ * that is none of the present set's shapes (possible after
+ * xh_venv_set_item_set): xh_venv_act_table refuses the env as a bad policy row
+ * is refused (untouched, DONE[e] = 0, the record's entries of a refused row),
+ * gather and grad skip the row as a bad index is skipped, and a NaN or an
+ * infinity in dout_dev leaves g_dev untouched; each is XH_ERR_INVALID at the
+ * next xh_venv_synchronize / get.
+ * A table stays valid while the set's shapes and capacities do: a curriculum
+ * that only changes weights (zero weights included: a zero-weight item is a
+ * legal shape that is never drawn) needs no new table; new weights of the
+ * network need a new forward. */
+#define XH_VTAB_MAX_ENTRIES 16384
+struct xh_venv_table_info {      /* xh_struct_size("xh_venv_table_info")    */
+  int entries;                   /* E                                       */
+  int states;                    /* S                                       */
+  int items;                     /* K                                       */
+  int rows;                      /* R = ceil(E / bins)                      */
+  int side[4];                   /* capacity[d] + 1; 1 past dims            */
+};
+int xh_item_set_table_info(const xh_item_set *s, int dims, int bins,
+                           struct xh_venv_table_info *out);
+int xh_venv_table_info(const xh_venv *v, struct xh_venv_table_info *out);
+int xh_venv_table_obs(xh_venv *v, float *obs_dev);
+int xh_venv_act_table(xh_venv *v, const float *table_dev, int mode,
+                      int write_obs);
+int xh_venv_table_gather(xh_venv *v, const float *table_dev,
+                         const int32_t *rows_dev, long first, long count,
+                         float *out_dev);
+int xh_venv_table_grad(xh_venv *v, const int32_t *rows_dev, long first,
+                       long count, const float *dout_dev, float *g_dev,
+                       int accumulate);
 /* environment::apply(ACTIONS[e], e) for the envs selected by MASK (all if
  * use_mask == 0), no reset; DONE[e] = game_over after the apply, 0 for the
  * envs this call did not apply (masked out, or an out-of-range action). */

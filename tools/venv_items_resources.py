@@ -2,7 +2,7 @@
 """Register, scratch and code-size figures of the venv step / act kernels,
 from the code object's metadata (cross-compiled; no device needed).
 
-    tools/venv_items_resources.py [--general] [--heur] [TREE ...]
+    tools/venv_items_resources.py [--general] [--heur] [--table] [TREE ...]
 
 For every TREE (default: this one) compiles TREE/dependence_free_rl_amd/csrc/
 venv_kernels.hip for the device only, reads each kernel's .vgpr_count,
@@ -17,7 +17,9 @@ venv_heur_kernels.hip (venv_heur_kernel, xh_venv_act_heuristic) instead of
 venv_kernels.hip and, beside each kernel, prints the act kernel of the same
 shape, mask and episode switches (no distribution record) from
 venv_kernels.hip: the heuristic kernel is to need no scratch and no more
-VGPRs than it.
+VGPRs than it.  --table reads venv_table_kernels.hip (xh_venv_table_*) and
+prints venv_act_table_kernel beside the general act kernel of the same shape
+and switches, then the other table kernels; none is to need scratch.
 """
 import json
 import os
@@ -92,12 +94,37 @@ def heur(tree, defines):
     return 1 if bad else 0
 
 
+def table(tree):
+    """The table kernels' figures; the act beside the general act kernel."""
+    tab = kernels(tree, (), "venv_table_kernels.hip")
+    act = kernels(tree, ("-DXH_VENV_GEN_TU=1",))
+    act = {demangle([n])[n]: v for n, v in act.items()}
+    pretty = demangle(sorted(tab))
+    scratch = []
+    for n in sorted(tab, key=pretty.get):
+        name, row = pretty[n], dict(tab[n])
+        m = re.match(r"void xh::venv_act_table_kernel<(\d+), (\d+), (\w+), "
+                     r"(\w+), (\w+)>", name)
+        if m:
+            a = act["void xh::venv_act_kernel<%s, %s, %s, %s, %s, "
+                    "xh::VenvItemTable>(xh::VenvActArgs, xh::VenvItemTable)"
+                    % m.groups()]
+            row.update(act_vgpr=a["vgpr"], act_code_bytes=a["code_bytes"])
+        print(json.dumps({"kernel": name, **row}))
+        if tab[n]["scratch"]:
+            scratch.append(name)
+    print(json.dumps({"table_kernels": len(tab), "scratch": scratch}))
+    return 1 if scratch else 0
+
+
 def main():
     general = "--general" in sys.argv[1:]
     defines = ("-DXH_VENV_GEN_TU=1",) if general else ()
     here = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    trees = [t for t in sys.argv[1:] if t not in ("--general", "--heur")] \
-        or [here]
+    trees = [t for t in sys.argv[1:]
+             if t not in ("--general", "--heur", "--table")] or [here]
+    if "--table" in sys.argv[1:]:
+        return table(trees[0])
     if "--heur" in sys.argv[1:]:
         return heur(trees[0], defines)
     tables = []

@@ -158,7 +158,8 @@ class VenvTableInfo(C.Structure):
 
 # calls an A/B library from before them (XH_LIB_PATH) may lack; the wrappers
 # that need one raise
-_AB_OPTIONAL = ("xh_trainer_table_stats", "xh_item_set_default",
+_AB_OPTIONAL = ("xh_trainer_table_stats", "xh_trainer_pack_read",
+                "xh_item_set_default",
                 "xh_item_set_thresholds", "xh_venv_create_ex",
                 "xh_venv_set_item_set", "xh_venv_get_item_set",
                 "xh_net_create", "xh_net_destroy", "xh_net_num_params",
@@ -217,6 +218,7 @@ def _load():
                                       C.POINTER(C.c_long)]),
         "xh_trainer_table_stats": (i, [vp, C.POINTER(C.c_int), C.POINTER(C.c_long),
                                        C.POINTER(C.c_long)]),
+        "xh_trainer_pack_read": (i, [vp, C.POINTER(C.c_int), vp, sz]),
         "xh_ctx_inject_fault": (i, [vp, i]),
         "xh_trainer_get_env_state": (i, [vp, i, i, vp, vp]),
         "xh_trainer_set_env_state": (i, [vp, i, i, vp, vp]),

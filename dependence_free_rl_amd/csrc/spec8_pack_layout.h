@@ -30,6 +30,12 @@
 #include <cstddef>
 #include <cstdint>
 
+#if defined(__HIPCC__)
+#define XH_PK_HD __host__ __device__
+#else
+#define XH_PK_HD
+#endif
+
 namespace xh {
 namespace sp8 {
 
@@ -59,6 +65,44 @@ enum {
 };
 // env-step classes, in group order
 enum { kPkClsA = 0, kPkClsB, kPkClsWideA, kPkClsWideB, kPkClasses };
+
+// The duplicate search of the compaction pass on lane masks (DESIGN.md §3.0e,
+// "the duplicate search"; spec8_pack_kernels.hip, tests/pack_dedup_check.cc).
+// Every bin state the environment produces lies in [-kPkCap, kPkCap]^2:
+// kPkMaskWords states, one 64-bit word each in a wave's own LDS table.  Each
+// lane ORs its lane bit into its state's word; the word read back, m, is the
+// set of lanes that hold the lane's state.
+constexpr int kPkCap = 8, kPkSide = 2 * kPkCap + 1;
+constexpr int kPkMaskWords = kPkSide * kPkSide;
+// a bin value the table has a word for
+XH_PK_HD inline bool pk_in_domain(int b0, int b1) {
+  return (unsigned)(b0 + kPkCap) <= 2u * kPkCap && (unsigned)(b1 + kPkCap) <= 2u * kPkCap;
+}
+// the word of state (b0, b1), both in [-kPkCap, kPkCap] (xh_logit_table.h's
+// state_index)
+XH_PK_HD inline int pk_mask_index(int b0, int b1) {
+  return (b0 + kPkCap) * kPkSide + (b1 + kPkCap);
+}
+// the lane is its state's first occurrence
+XH_PK_HD inline bool pk_dedup_first(unsigned long long m, int lane) {
+  return lane == __builtin_ctzll(m);
+}
+// From m and F = the set of lanes that are a first occurrence (one ballot):
+// the state's index in first-occurrence order, its multiplicity, and the
+// number of distinct states (not capped: a wide env-step is d > kPkSegRows).
+struct PkDedup {
+  int slot, count, d;
+  bool first;
+};
+XH_PK_HD inline PkDedup pk_dedup(unsigned long long m, unsigned long long F, int lane) {
+  const int lead = __builtin_ctzll(m);
+  PkDedup r;
+  r.slot = __builtin_popcountll(F & ((1ull << lead) - 1ull));
+  r.count = __builtin_popcountll(m);
+  r.d = __builtin_popcountll(F);
+  r.first = lane == lead;
+  return r;
+}
 
 // groups a batch of nt env-steps can need: all wide, or packed with both
 // classes' last groups partly filled

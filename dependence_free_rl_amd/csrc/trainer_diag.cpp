@@ -503,6 +503,27 @@ int xh_trainer_pack_stats(xh_trainer *t, long *packed, long *unpacked, long *gro
   });
 }
 
+int xh_trainer_pack_read(xh_trainer *t, int *hdr, void *records, size_t cap) {
+  return guard([&]() -> int {
+    if (!t || !hdr) return fail(XH_ERR_INVALID, "null arg");
+    if (!t->pk || !t->pk_hdr || !t->pk_learned)
+      return fail(XH_ERR_STATE, "pack_read: the last learn() did not run packed");
+    HIPCHK(hipMemcpyAsync(hdr, t->pk_hdr, xh::sp8::kPkHdrInts * sizeof(int),
+                          hipMemcpyDeviceToHost, t->ctx->stream));
+    HIPCHK(hipStreamSynchronize(t->ctx->stream));
+    if (!records) return XH_OK;
+    const size_t groups = (size_t)hdr[xh::sp8::kPkGroups];
+    const size_t bytes = groups * xh::sp8::kPkGroupBytes;
+    if (hdr[xh::sp8::kPkGroups] < 0 ||
+        groups > xh::sp8::pk_max_groups((size_t)(t->T() * t->N())))
+      return fail(XH_ERR_STATE, "pack_read: a header of %d groups", hdr[xh::sp8::kPkGroups]);
+    if (bytes > cap) return fail(XH_ERR_INVALID, "pack_read: %zu bytes needed", bytes);
+    HIPCHK(hipMemcpyAsync(records, t->pk, bytes, hipMemcpyDeviceToHost, t->ctx->stream));
+    HIPCHK(hipStreamSynchronize(t->ctx->stream));
+    return XH_OK;
+  });
+}
+
 int xh_trainer_table_stats(xh_trainer *t, int *ran, long *out_of_domain, long *groups) {
   return guard([&]() -> int {
     if (!t || !ran || !out_of_domain || !groups) return fail(XH_ERR_INVALID, "null arg");

@@ -284,11 +284,15 @@ hipError_t table_epoch(xh_trainer *t, const xh::PolicyTrainArgs &pa, int grid, b
                                            grid, s);
 }
 
-// the compaction pass: once per learn(), behind the final advantages
+// the compaction pass: once per learn(), behind the final advantages.
+// XH_SP8_PACK_DEDUP=loop (read per learn(); A/B runs and tests): the former
+// classify and write kernels, the same bytes.
 int pack_batch(xh_trainer *t, xh::PolicyTrainArgs *pa) {
   hipStream_t s = t->ctx->stream;
   const xh::PackArgs ka{t->env, t->batch(), t->adv, t->pk, t->pk_hdr, t->pk_cls, t->pk_blk};
-  CHK(timed(t, "pack", [&]() { return xh::launch_spec8_pack(ka, s); }));
+  const char *dd = std::getenv("XH_SP8_PACK_DEDUP");
+  const bool loop = dd && std::strcmp(dd, "loop") == 0;
+  CHK(timed(t, "pack", [&]() { return xh::launch_spec8_pack(ka, loop, s); }));
   pa->pk = t->pk;
   pa->pk_hdr = t->pk_hdr;
   t->pk_learned = true;

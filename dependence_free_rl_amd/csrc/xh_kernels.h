@@ -730,7 +730,10 @@ struct PackArgs {
   int *blk;          // [pk_scratch_ints(T N)] scratch: per chunk of 64 env-steps
                      // the classes' counts, then their offsets
 };
-hipError_t launch_spec8_pack(const PackArgs &a, hipStream_t s);
+// loop: classify and write find an env-step's duplicate states with the former
+// wave-uniform loop (XH_SP8_PACK_DEDUP=loop) instead of the LDS lane masks;
+// the same bytes either way
+hipError_t launch_spec8_pack(const PackArgs &a, bool loop, hipStream_t s);
 // The epoch on the table (spec8_table_layout.h): the per-bin
 // net's activations depend on the table entry (bin state, item) alone and
 // every parameter gradient is linear in the rows' loss gradient g, so an epoch

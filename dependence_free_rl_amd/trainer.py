@@ -815,6 +815,24 @@ class Trainer:
                                              C.byref(g)))
         return {"packed": p.value, "unpacked": u.value, "groups": g.value}
 
+    def pack_buffer(self):
+        """The packed batch of the last learn() as the compaction pass wrote
+        it (xh_trainer_pack_read; synchronises -- tests only): (header, the 8
+        int32 of spec8_pack_layout.h; records, uint8 [groups, 256]).  Raises
+        when the last learn() did not run packed, or on an A/B library from
+        before the call."""
+        import numpy as np
+        read = getattr(_lib.lib, "xh_trainer_pack_read", None)
+        if read is None:
+            raise RuntimeError("pack_buffer: %s has no xh_trainer_pack_read"
+                               % _lib.lib._name)
+        hdr = np.zeros(8, np.int32)
+        hp = hdr.ctypes.data_as(C.POINTER(C.c_int))
+        check(read(self.h, hp, None, 0))
+        rec = np.zeros((int(hdr[6]), 256), np.uint8)
+        check(read(self.h, hp, rec.ctypes.data_as(C.c_void_p), rec.nbytes))
+        return hdr, rec
+
     def table_stats(self):
         """Whether the last learn() ran its packed epochs on the table of
         (bin state, item) points (xh_trainer_table_stats; synchronises -- tests

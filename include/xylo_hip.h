@@ -1680,6 +1680,14 @@ int xh_trainer_kernel_info(xh_trainer *t, char *buf, size_t cap);
  * override, a wide slot) or none has run yet. */
 int xh_trainer_pack_stats(xh_trainer *t, long *packed, long *unpacked, long *groups);
 
+/* Tests only (synchronises the stream): the packed batch of the last learn()
+ * as the compaction pass wrote it.  hdr: its 8 header ints (env-steps per
+ * class NA, NB, UA, UB, packed groups GA, GB, all groups, 0); records, when
+ * not NULL: the hdr[6] group records of 256 bytes each, in group order
+ * (XH_ERR_INVALID when cap is smaller).  XH_ERR_STATE when the last learn()
+ * did not run packed or none has run yet. */
+int xh_trainer_pack_read(xh_trainer *t, int *hdr, void *records, size_t cap);
+
 /* Tests and diagnostics only (synchronises the stream): whether the last
  * learn() ran its packed epochs ON THE TABLE -- a forward over the 578 (bin
  * state, item) points, one streaming pass over the packed batch that sums the

@@ -22,6 +22,7 @@ OBJS     := $(SRC)/policy_kernels.o $(SRC)/value_kernels.o \
             $(SRC)/policy_spec8_pack_kernels.o $(SRC)/spec8_pack_kernels.o \
             $(SRC)/policy_spec8_tab_kernels.o $(SRC)/spec8_table_kernels.o \
             $(SRC)/table_mm_kernels.o $(SRC)/net_kernels.o $(SRC)/net_api.o \
+            $(SRC)/net_value_kernels.o \
             $(SRC)/policy_spec4_kernels.o \
             $(SRC)/policy_split8wh_kernels.o $(SRC)/policy_split8wh_kl_kernels.o \
             $(SRC)/policy_split8x_kernels.o $(SRC)/policy_split8x_kl_kernels.o \

@@ -167,6 +167,7 @@ _AB_OPTIONAL = ("xh_trainer_table_stats", "xh_trainer_pack_read",
                 "xh_net_get_step", "xh_net_set_step", "xh_net_forward",
                 "xh_net_backward", "xh_net_set_optimizer", "xh_net_step",
                 "xh_net_set_grid_cap", "xh_net_info",
+                "xh_net_forward_record", "xh_net_backward_record",
                 "xh_item_set_table_info", "xh_venv_table_info",
                 "xh_venv_table_obs", "xh_venv_act_table",
                 "xh_venv_table_gather", "xh_venv_table_grad")
@@ -319,6 +320,9 @@ def _load():
         "xh_net_step": (i, [vp, C.c_float, vp]),
         "xh_net_set_grid_cap": (i, [vp, i]),
         "xh_net_info": (i, [vp, C.c_char_p, sz]),
+        "xh_net_forward_record": (i, [vp, vp, i, vp, C.c_long, C.c_long, vp]),
+        "xh_net_backward_record": (i, [vp, vp, i, vp, C.c_long, C.c_long, vp,
+                                       i]),
         "xh_trainer_set_record_last_step": (i, [vp, i]),
         "xh_trainer_set_stats": (i, [vp, i]),
         "xh_trainer_stats_count": (i, [vp, C.POINTER(C.c_long)]),

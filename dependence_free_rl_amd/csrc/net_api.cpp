@@ -4,7 +4,10 @@
 // on the context's stream with no host synchronisation.  The policy runs the
 // fused kernels of net_kernels.hip; the value net composes the layer launches
 // of dense_kernels.hip (the ones xh_model_forward / xh_model_gradient run) on
-// device buffers; step is the trainer's clip and optimizer launches.
+// device buffers -- or, for widths (64, 32), the fused kernels of
+// net_value_kernels.hip straight on a venv's recorded window
+// (xh_net_forward_record / xh_net_backward_record); step is the trainer's clip
+// and optimizer launches.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -27,7 +30,8 @@ struct xh_net {
   float lr = 0.0f, wd = 0.0f, beta1 = 0.9f, beta2 = 0.999f;
   long t = 0;                     // steps taken
   int grid_cap = 0, cus = 1;
-  // policy: one slab per workgroup of the backward
+  // policy, and the value net on the record (allocated at its first
+  // backward): one slab per workgroup of the backward
   float *slab = nullptr;
   int slab_stride = 0, slab_cap = 0;
   // value: activations, backprop ping-pong and split-K slabs for rows_cap rows
@@ -36,6 +40,7 @@ struct xh_net {
   int vstride = 0;
   // what the last forward / backward launched (xh_net_info)
   int grid_fwd = 0, grid_bwd = 0, slabs = 0;
+  bool on_record = false;  // the last one was a *_record call
 };
 
 namespace {
@@ -309,6 +314,7 @@ int xh_net_forward(xh_net *n, const float *obs_dev, long rows, float *out_dev) {
     if (n->kind != XH_NET_POLICY) {
       const long m = rows * net_points(n);
       CHK(value_reserve(n, m));
+      n->on_record = false;
       return value_forward(n, obs_dev, (int)m, out_dev);
     }
     xh::NetPolicyArgs a{};
@@ -333,6 +339,7 @@ int xh_net_backward(xh_net *n, const float *obs_dev, long rows, const float *dou
     if (n->kind != XH_NET_POLICY) {
       const long m = rows * net_points(n);
       CHK(value_reserve(n, m));
+      n->on_record = false;
       CHK(value_backward(n, obs_dev, (int)m, dout_dev, dst));
     } else {
       xh::NetPolicyArgs a{};
@@ -353,6 +360,96 @@ int xh_net_backward(xh_net *n, const float *obs_dev, long rows, const float *dou
       CHK(launched(xh::launch_tensor_map(xh::kTensorAdd, n->buf[XH_NET_GRAD], n->tmp, 0.0f,
                                          n->buf[XH_NET_GRAD], n->np, s),
                    "net_backward"));
+    return XH_OK;
+  });
+}
+
+// ---- the value net on a venv's recorded window (net_value_kernels.hip) ----
+namespace {
+
+// the refusals of both calls and the launch's arguments; a->rec.count == 0:
+// nothing to launch
+int record_args(xh_net *n, xh_venv *v, const char *who, int view, const int32_t *rows_dev,
+                long first, long count, xh::NetValueArgs *a) {
+  if (!n) return fail(XH_ERR_INVALID, "%s: null net", who);
+  if (n->kind != XH_NET_VALUE)
+    return fail(XH_ERR_INVALID, "%s: the net is not a value net (XH_NET_VALUE); the policy "
+                "reads observations or runs on the venv's logit table", who);
+  if (n->h1 != xh::kNetValueV1 || n->h2 != xh::kNetValueV2)
+    return fail(XH_ERR_INVALID, "%s: value widths [%d, %d], the fused kernels are built for "
+                "[%d, %d] (other widths: xh_venv_record_obs and xh_net_forward / backward)",
+                who, n->h1, n->h2, xh::kNetValueV1, xh::kNetValueV2);
+  const int32_t *cap = nullptr;
+  xh_ctx *vctx = nullptr;
+  CHK(venv_record_rows(v, who, view, rows_dev, first, count, &a->rec, &cap, &vctx));
+  if (a->rec.B != n->B || a->rec.D != n->D)
+    return fail(XH_ERR_INVALID, "%s: the venv is %d bins x %d dims, the net %d x %d", who,
+                a->rec.B, a->rec.D, n->B, n->D);
+  if (vctx != n->ctx)
+    return fail(XH_ERR_INVALID, "%s: the net and the venv live on different contexts", who);
+  for (int d = 0; d < 4; ++d) a->cap[d] = d < n->D ? cap[d] : 1;
+  a->params = n->buf[XH_NET_PARAMS];
+  return XH_OK;
+}
+
+// tiles and CUs decide the grid, capped by xh_net_set_grid_cap
+int record_grid(const xh_net *n, long count, int per_cu) {
+  long g = (long)n->cus * per_cu;
+  if (n->grid_cap > 0) g = std::min<long>(g, n->grid_cap);
+  return (int)std::max<long>(1, std::min(g, xh::net_value_tiles(count)));
+}
+
+}  // namespace
+
+int xh_net_forward_record(xh_net *n, xh_venv *v, int view, const int32_t *rows_dev, long first,
+                          long count, float *out_dev) {
+  return guard([&]() -> int {
+    xh::NetValueArgs a{};
+    CHK(record_args(n, v, "net_forward_record", view, rows_dev, first, count, &a));
+    if (!out_dev) return fail(XH_ERR_INVALID, "net_forward_record: null out_dev");
+    if (a.rec.count == 0) return XH_OK;
+    HIPCHK(hipSetDevice(n->ctx->device));
+    a.out = out_dev;
+    n->grid_fwd = record_grid(n, count, 2);
+    n->on_record = true;
+    return launched(xh::launch_net_value_fwd(a, n->grid_fwd, n->ctx->stream),
+                    "net_forward_record");
+  });
+}
+
+int xh_net_backward_record(xh_net *n, xh_venv *v, int view, const int32_t *rows_dev, long first,
+                           long count, const float *dout_dev, int accumulate) {
+  return guard([&]() -> int {
+    xh::NetValueArgs a{};
+    CHK(record_args(n, v, "net_backward_record", view, rows_dev, first, count, &a));
+    if (!dout_dev) return fail(XH_ERR_INVALID, "net_backward_record: null dout_dev");
+    HIPCHK(hipSetDevice(n->ctx->device));
+    hipStream_t s = n->ctx->stream;
+    if (a.rec.count == 0) {  // an empty sum
+      if (!accumulate) HIPCHK(hipMemsetAsync(n->buf[XH_NET_GRAD], 0, (size_t)n->np * 4, s));
+      return XH_OK;
+    }
+    if (!n->slab) {  // at the first backward on the record, as value_reserve
+      n->slab_stride = (n->np + 63) & ~63;
+      HIPCHK(hipStreamSynchronize(s));
+      CHK(dev_zalloc(s, (void **)&n->slab, (size_t)n->cus * n->slab_stride * 4,
+                     "net_backward_record"));
+      n->slab_cap = n->cus;
+    }
+    a.dout = dout_dev;
+    a.slab = n->slab;
+    a.slab_stride = n->slab_stride;
+    n->grid_bwd = std::min(record_grid(n, count, 1), n->slab_cap);
+    n->slabs = n->grid_bwd;
+    n->on_record = true;
+    float *dst = accumulate ? n->tmp : n->buf[XH_NET_GRAD];
+    CHK(launched(xh::launch_net_value_bwd(a, n->grid_bwd, s), "net_backward_record"));
+    CHK(launched(xh::launch_slab_reduce(n->slab, n->grid_bwd, n->slab_stride, n->np, dst, s),
+                 "net_backward_record"));
+    if (accumulate)  // grad[i] += this call's sum: one f32 add per entry
+      CHK(launched(xh::launch_tensor_map(xh::kTensorAdd, n->buf[XH_NET_GRAD], n->tmp, 0.0f,
+                                         n->buf[XH_NET_GRAD], n->np, s),
+                   "net_backward_record"));
     return XH_OK;
   });
 }
@@ -433,6 +530,15 @@ int xh_net_info(xh_net *n, char *buf, size_t cap) {
           n->grid_fwd, n->grid_bwd, n->grid_cap,
           xh::net_policy_lds_bytes(2 * n->D, n->h1, n->h2, 0),
           xh::net_policy_lds_bytes(2 * n->D, n->h1, n->h2, 1), n->slabs);
+    else if (n->on_record)
+      len = std::snprintf(
+          buf, cap,
+          "{\"kind\": \"value\", \"kernels\": [\"net_value_fwd_kernel\", "
+          "\"net_value_bwd_kernel\", \"slab_reduce\"], \"math\": \"f32_mfma_16x16x4\", "
+          "\"grid\": {\"forward\": %d, \"backward\": %d}, \"grid_cap\": %d, "
+          "\"lds\": {\"forward\": %d, \"backward\": %d}, \"slabs\": %d}",
+          n->grid_fwd, n->grid_bwd, n->grid_cap, xh::net_value_lds_bytes(0),
+          xh::net_value_lds_bytes(1), n->slabs);
     else
       len = std::snprintf(
           buf, cap,

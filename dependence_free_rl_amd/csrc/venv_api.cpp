@@ -746,6 +746,49 @@ int table_rows(const xh_venv *v, const char *what, const int32_t *rows_dev,
 
 }  // namespace
 
+// xh_host.h: xh_venv_record_obs's checks and row addressing, for it and for the
+// nets that read the record themselves (net_api.cpp)
+int xh::host::venv_record_rows(xh_venv *v, const char *who, int view,
+                               const int32_t *rows_dev, long first, long count,
+                               xh::VenvObsArgs *a, const int32_t **cap,
+                               xh_ctx **ctx) {
+  if (!v) return fail(XH_ERR_INVALID, "%s: null venv", who);
+  if (view != XH_VOBS_STATE && view != XH_VOBS_NEXT)
+    return fail(XH_ERR_INVALID, "%s: view %d (XH_VOBS_STATE / NEXT)", who, view);
+  if (!v->rec[XH_VREC_BINS].ptr)
+    return fail(XH_ERR_STATE, "%s: %s", who,
+                v->rec_steps > 0 ? "the record was made without states "
+                                   "(xh_venv_set_record's with_states)"
+                                 : "no record (xh_venv_set_record)");
+  if (first < 0 || count < 0)
+    return fail(XH_ERR_INVALID, "%s: first %ld, count %ld", who, first, count);
+  if (cap) *cap = v->table.cap;
+  if (ctx) *ctx = v->ctx;
+  a->B = v->env.B;
+  a->D = v->env.D;
+  a->N = v->N;
+  a->count = 0;
+  if (count == 0) return XH_OK;
+  const long P = v->rec_pos;
+  const long total = (view == XH_VOBS_NEXT ? P : P + 1) * (long)v->N;
+  if (total == 0 || (!rows_dev && first + count > total))
+    return fail(XH_ERR_INVALID, "%s: rows %ld .. %ld of %ld (cursor %ld, %d "
+                "envs)", who, first, first + count - 1, total, P, v->N);
+  a->P = (int)P;
+  a->next = view == XH_VOBS_NEXT;
+  a->rec_bins = v->rec_as<const int8_t>(XH_VREC_BINS);
+  a->rec_items = v->rec_as<const int8_t>(XH_VREC_ITEMS);
+  a->cur_bins = (const int8_t *)v->buf[XH_VENV_BINS];
+  a->cur_items = (const int8_t *)v->buf[XH_VENV_ITEMS];
+  a->rec_action = v->rec_as<const int32_t>(XH_VREC_ACTION);
+  a->rec_done = v->rec_as<const uint8_t>(XH_VREC_DONE);
+  a->rows = rows_dev;
+  a->first = first;
+  a->count = count;
+  a->err = v->err;
+  return XH_OK;
+}
+
 extern "C" {
 
 void xh_item_set_default(xh_item_set *s, int dims) {
@@ -1170,45 +1213,15 @@ int xh_venv_get_record_legal(xh_venv *v, uint32_t *host, size_t bytes) {
 int xh_venv_record_obs(xh_venv *v, int view, const int32_t *rows_dev,
                        long first, long count, float *obs_dev) {
   return venv_call(v, [&]() -> int {
-    if (view != XH_VOBS_STATE && view != XH_VOBS_NEXT)
-      return fail(XH_ERR_INVALID, "venv record obs: view %d (XH_VOBS_STATE / "
-                  "NEXT)", view);
-    if (!v->rec[XH_VREC_BINS].ptr)
-      return fail(XH_ERR_STATE, "venv record obs: %s",
-                  v->rec_steps > 0 ? "the record was made without states "
-                                     "(xh_venv_set_record's with_states)"
-                                   : "no record (xh_venv_set_record)");
-    if (first < 0 || count < 0)
-      return fail(XH_ERR_INVALID, "venv record obs: first %ld, count %ld",
-                  first, count);
+    xh::VenvObsArgs a{};
+    CHK(venv_record_rows(v, "venv record obs", view, rows_dev, first, count, &a,
+                         nullptr, nullptr));
     if (count == 0) return XH_OK;
     if (!obs_dev || (reinterpret_cast<uintptr_t>(obs_dev) & 15))
       return fail(XH_ERR_INVALID, "venv record obs: obs_dev must be 16-byte "
                   "aligned (the kernel writes 16-byte stores)");
-    const long P = v->rec_pos;
-    const long total = (view == XH_VOBS_NEXT ? P : P + 1) * (long)v->N;
-    if (total == 0 || (!rows_dev && first + count > total))
-      return fail(XH_ERR_INVALID, "venv record obs: rows %ld .. %ld of %ld "
-                  "(cursor %ld, %d envs)", first, first + count - 1, total, P,
-                  v->N);
     HIPCHK(hipSetDevice(v->ctx->device));
-    xh::VenvObsArgs a{};
-    a.B = v->env.B;
-    a.D = v->env.D;
-    a.N = v->N;
-    a.P = (int)P;
-    a.next = view == XH_VOBS_NEXT;
-    a.rec_bins = v->rec_as<const int8_t>(XH_VREC_BINS);
-    a.rec_items = v->rec_as<const int8_t>(XH_VREC_ITEMS);
-    a.cur_bins = (const int8_t *)v->buf[XH_VENV_BINS];
-    a.cur_items = (const int8_t *)v->buf[XH_VENV_ITEMS];
-    a.rec_action = v->rec_as<const int32_t>(XH_VREC_ACTION);
-    a.rec_done = v->rec_as<const uint8_t>(XH_VREC_DONE);
-    a.rows = rows_dev;
-    a.first = first;
-    a.count = count;
     a.obs = obs_dev;
-    a.err = v->err;
     return venv_timed(v, [&] {
       return xh::launch_venv_record_obs(a, v->ctx->stream,
                                         v->general ? v->table.cap : nullptr);

@@ -223,6 +223,15 @@ inline xh::EnvDesc make_env(int bins, int dims) {
   return env;
 }
 
+// venv_api.cpp: xh_venv_record_obs's checks and row addressing, for a launch
+// that reads `count` rows of v's recorded window (a->obs is left null;
+// a->count == 0: nothing to launch).  *cap: the venv's per-dim capacities
+// (1 past its dims), *ctx: its context; either may be null.  `who` prefixes
+// the messages.
+int venv_record_rows(xh_venv *v, const char *who, int view,
+                     const int32_t *rows_dev, long first, long count,
+                     xh::VenvObsArgs *a, const int32_t **cap, xh_ctx **ctx);
+
 }  // namespace host
 }  // namespace xh
 

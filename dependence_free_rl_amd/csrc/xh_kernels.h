@@ -635,6 +635,27 @@ int net_policy_lds_bytes(int F0, int H1, int H2, int backward);
 hipError_t launch_net_policy_fwd(const NetPolicyArgs &a, int grid, hipStream_t s);
 hipError_t launch_net_policy_bwd(const NetPolicyArgs &a, int grid, hipStream_t s);
 
+// The value net 2BD -> 64 -> relu -> 32 -> relu -> 1 read straight from a
+// venv's recorded window (xh_net_forward_record / xh_net_backward_record,
+// net_value_kernels.hip): `rec` addresses the rows as xh_venv_record_obs does
+// (rec.obs is not used), the observation is formed in registers from the int8
+// state with IEEE f32 divisions by float(cap[d]); tiles of 64 rows, `grid`
+// persistent workgroups (1 <= grid <= net_value_tiles(rec.count)).
+struct NetValueArgs {
+  VenvObsArgs rec;
+  int32_t cap[4];       // the venv's per-dim capacities
+  const float *params;  // ValueLayout{2BD, 64, 32}
+  float *out;           // forward: [count] (out); rows outside the view untouched
+  const float *dout;    // backward: [count] dL/dvalue
+  float *slab;          // backward: [grid][slab_stride] (out), ValueLayout
+  int slab_stride;
+};
+constexpr int kNetValueV1 = 64, kNetValueV2 = 32;
+long net_value_tiles(long count);
+int net_value_lds_bytes(int backward);
+hipError_t launch_net_value_fwd(const NetValueArgs &a, int grid, hipStream_t s);
+hipError_t launch_net_value_bwd(const NetValueArgs &a, int grid, hipStream_t s);
+
 // 1 when the kernels were built with the phase-ablation switches
 // (make diag, -DXH_DIAG_ABLATE=1), 0 in the product library.
 int diag_build();

@@ -249,3 +249,45 @@ class ValueNet(_Net):
         (trainer.init_value; drawn with numpy on the host)."""
         self.params = init_value(self.B, self.D, self.widths[0],
                                  self.widths[1], seed=seed)
+
+    # ---- straight from a venv's recorded window (widths (64, 32)) ------------
+    def forward_record(self, venv, view="state", rows=None, first=0,
+                       count=None, out=None):
+        """forward(venv.record_obs(view, rows, first, count)) without the
+        observations (xh_net_forward_record): the fused kernel reads the int8
+        record.  view, rows, first and count as VecEnv.record_obs.  out: an
+        integer device pointer that receives the [count] values (nothing is
+        returned), or None for a host array.  With out=None an index outside
+        the view gives NaN in its entry."""
+        view_id, rows_ptr, count = venv._record_rows("forward_record", view,
+                                                     rows, first, count)
+        dst = out
+        if out is None:
+            dst = self._scratch("out", count * 4)
+            if count:
+                self._upload(dst, np.full(count, np.nan, np.float32))
+        check(_lib.lib.xh_net_forward_record(self.h, venv.h, view_id, rows_ptr,
+                                             first, count, int(dst)))
+        if out is not None:
+            return None
+        return self._download(dst, (count,))
+
+    def backward_record(self, venv, dout, view="state", rows=None, first=0,
+                        count=None, accumulate=False):
+        """backward(venv.record_obs(view, rows, first, count), dout) without
+        the observations (xh_net_backward_record).  dout: a host array [count]
+        or an integer device pointer."""
+        view_id, rows_ptr, count = venv._record_rows("backward_record", view,
+                                                     rows, first, count)
+        if isinstance(dout, (int, np.integer)):
+            dptr = int(dout)
+        else:
+            d = np.ascontiguousarray(dout, np.float32)
+            if d.shape != (count,):
+                raise ValueError("dout: shape %s, expected %s"
+                                 % (d.shape, (count,)))
+            dptr = self._scratch("dout", d.nbytes)
+            self._upload(dptr, d)
+        check(_lib.lib.xh_net_backward_record(self.h, venv.h, view_id, rows_ptr,
+                                              first, count, dptr,
+                                              1 if accumulate else 0))

@@ -422,6 +422,31 @@ class VecEnv:
         self._upload(ptr, a)
         return ptr
 
+    def _record_rows(self, who, view, rows, first, count):
+        """(view id, device address of the index list or None, count) of the
+        view / rows / first / count arguments record_obs documents."""
+        view_id = {"state": VOBS_STATE, "next": VOBS_NEXT}[view]
+        rows_ptr = None
+        if rows is None:
+            if count is None:
+                P = self.record_pos()
+                count = (P + 1 if view_id == VOBS_STATE else P) * self.N - first
+        elif isinstance(rows, (int, np.integer)):
+            if count is None:
+                raise ValueError("%s: count is needed with a device "
+                                 "pointer to the rows" % who)
+            rows_ptr = int(rows)
+        else:
+            r = np.ascontiguousarray(rows, np.int32).reshape(-1)
+            if count is None:
+                count = r.size - first
+            if first < 0 or count < 0 or first + count > r.size:
+                raise ValueError("%s: rows %d .. %d of a list of %d"
+                                 % (who, first, first + count - 1, r.size))
+            rows_ptr = self._scratch("rows", r.nbytes)
+            self._upload(rows_ptr, r)
+        return view_id, rows_ptr, count
+
     def record_obs(self, view="state", rows=None, first=0, count=None,
                    out=None):
         """observation::to_vector of recorded rows (xh_venv_record_obs), row
@@ -432,27 +457,9 @@ class VecEnv:
         device pointer to int32 indices, of which first .. first + count - 1
         are taken.  out: an integer device pointer (16-byte aligned; nothing
         is returned), or None for a host array [count][B][2D] float32."""
-        view_id = {"state": VOBS_STATE, "next": VOBS_NEXT}[view]
-        N, B, D = self.N, self.B, self.D
-        rows_ptr = None
-        if rows is None:
-            if count is None:
-                P = self.record_pos()
-                count = (P + 1 if view_id == VOBS_STATE else P) * N - first
-        elif isinstance(rows, (int, np.integer)):
-            if count is None:
-                raise ValueError("record_obs: count is needed with a device "
-                                 "pointer to the rows")
-            rows_ptr = int(rows)
-        else:
-            r = np.ascontiguousarray(rows, np.int32).reshape(-1)
-            if count is None:
-                count = r.size - first
-            if first < 0 or count < 0 or first + count > r.size:
-                raise ValueError("record_obs: rows %d .. %d of a list of %d"
-                                 % (first, first + count - 1, r.size))
-            rows_ptr = self._scratch("rows", r.nbytes)
-            self._upload(rows_ptr, r)
+        B, D = self.B, self.D
+        view_id, rows_ptr, count = self._record_rows("record_obs", view, rows,
+                                                     first, count)
         dst = out if out is not None else self._scratch(
             "obs", count * B * 2 * D * 4)
         check(_lib.lib.xh_venv_record_obs(self.h, view_id, rows_ptr, first,

@@ -6,6 +6,7 @@ and every stage between them is a launch of the venv chain.
     python examples/venv_ppo.py
     python examples/venv_ppo.py --bins 16 --envs 2048 --iterations 60
     python examples/venv_ppo.py --table
+    python examples/venv_ppo.py --table --value-record
 
 Per iteration: T masked act() steps from PolicyNet.forward(venv) with the
 record on; record_obs of the window; ValueNet.forward; advantages (GAE and TD
@@ -24,7 +25,13 @@ iteration and once per epoch replaces every per-row forward; the rollout is
 act_table(), the minibatches are table_logits -> policy_loss -> table_grad
 (accumulating), and one PolicyNet.backward(table_obs, G) per step gives the
 epoch's parameter gradient.  The value net sees whole observations and keeps
-its path."""
+its path.
+
+--value-record (opt-in) runs the value net straight on the record:
+ValueNet.forward_record / backward_record read the int8 states of the window's
+rows themselves, so the window's values and every minibatch's value forward and
+backward need no record_obs.  Without --table the policy's minibatches still
+form their observations; with --table no f32 observation is formed at all."""
 import argparse
 import os
 import sys
@@ -84,6 +91,8 @@ def main():
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--table", action="store_true",
                     help="act and train the policy on its logit table")
+    ap.add_argument("--value-record", action="store_true",
+                    help="run the value net straight on the recorded window")
     a = ap.parse_args()
 
     from dependence_free_rl_amd import (VENV_POLICY, VLOSS_CLIPPED,
@@ -125,8 +134,11 @@ def main():
         for _ in range(0 if a.table else T):
             pol.forward(venv, out=venv.device_ptr(VENV_POLICY))
             venv.act(None, kind="logits", write_obs=True, fetch=False)
-        states = venv.record_obs("state")  # [(T + 1) N][B][2D]
-        values = val.forward(states).reshape(T + 1, N)
+        if a.value_record:
+            values = val.forward_record(venv, "state").reshape(T + 1, N)
+        else:
+            states = venv.record_obs("state")  # [(T + 1) N][B][2D]
+            values = val.forward(states).reshape(T + 1, N)
         adv = venv.advantages(values, normalize=True,
                               returns=("adv", "td_target"))
         for epoch in range(a.epochs):
@@ -135,16 +147,18 @@ def main():
                 table = pol.forward(tobs)  # once per epoch
             for first in range(0, total, a.minibatch):
                 count = min(a.minibatch, total - first)
-                obs = venv.record_obs("state", rows=perm, first=first,
-                                      count=count)
+                at = dict(rows=perm, first=first, count=count)
+                if not (a.table and a.value_record):  # somebody reads them
+                    obs = venv.record_obs("state", **at)
                 logits = venv.table_logits(
-                    table, rows=perm, first=first,
-                    count=count) if a.table else pol.forward(obs)
+                    table, **at) if a.table else pol.forward(obs)
+                v_mb = val.forward_record(venv, "state", **at) \
+                    if a.value_record else val.forward(obs)
                 res = venv.policy_loss(
                     logits, adv["adv"], kind="logits",
                     loss="clipped", rows=perm, first=first, count=count,
                     scale=1.0 / total, legal=True, ent_coef=a.ent_coef,
-                    values=val.forward(obs), target=adv["td_target"],
+                    values=v_mb, target=adv["td_target"],
                     value_scale=1.0 / total, want_stats=True,
                     accumulate=first > 0)
                 if a.table:
@@ -152,7 +166,11 @@ def main():
                                         count=count, accumulate=first > 0)
                 else:
                     pol.backward(obs, res["grad"], accumulate=first > 0)
-                val.backward(obs, res["dvalue"], accumulate=first > 0)
+                if a.value_record:
+                    val.backward_record(venv, res["dvalue"], "state",
+                                        accumulate=first > 0, **at)
+                else:
+                    val.backward(obs, res["dvalue"], accumulate=first > 0)
             if a.table:  # the epoch's gradient: one backward on the table
                 pol.backward(tobs, G.reshape(info["rows"], B))
             pol.step(max_norm=a.max_norm)

@@ -1550,6 +1550,40 @@ int xh_net_step(xh_net *n, float max_norm, double *clip_log_dev);
 int xh_net_set_grid_cap(xh_net *n, int cap);
 int xh_net_info(xh_net *n, char *buf, size_t cap);
 
+/* The value net read straight from a venv's recorded window (opt-in; fused:
+ * net_value_fwd_kernel / net_value_bwd_kernel, exact f32 MFMA).
+ * xh_net_forward_record(n, v, view, rows_dev, first, count, out_dev) replaces
+ * xh_net_forward on the block xh_venv_record_obs(v, view, rows_dev, first,
+ * count, obs) writes, call for call: view, rows_dev, first and count mean what
+ * they mean there (XH_VOBS_STATE over (P + 1) N rows with slot P the present
+ * state, XH_VOBS_NEXT over P N rows: the successor, or the terminal view where
+ * the transition ended), output row j is the row record_obs writes as row j,
+ * and each observation has record_obs's bits ((float)v / (float)capacity[d] of
+ * the venv's item set, the default one without a set) -- formed in registers
+ * from the int8 record: no f32 observation and no activation is written.
+ * xh_net_backward_record is xh_net_backward on the same rows: the parameter
+ * gradient of sum(dout * out) into XH_NET_GRAD, accumulate as there;
+ * per-workgroup slabs summed in a fixed order, no floating-point atomics, the
+ * same bits from run to run.  An index outside the view leaves out_dev[j]
+ * untouched / adds nothing to the gradient and raises the venv's error bit
+ * that xh_venv_record_obs raises (XH_ERR_INVALID at the next
+ * xh_venv_synchronize).  Both are asynchronous on the context's stream; the
+ * first backward allocates the slabs (one synchronisation then).
+ * xh_net_set_grid_cap caps these launches too and xh_net_info describes them
+ * ("kernels" names them once one has run).
+ * XH_ERR_INVALID: n is not XH_NET_VALUE, its widths are not (64, 32), its bins
+ * or dims are not the venv's, net and venv live on different contexts, count <
+ * 0, out_dev / dout_dev NULL, or what xh_venv_record_obs refuses; XH_ERR_STATE:
+ * the venv has no record.  count = 0 does nothing (a backward without
+ * accumulate then zeroes XH_NET_GRAD).  Other widths keep the layer path
+ * through xh_venv_record_obs. */
+int xh_net_forward_record(xh_net *n, xh_venv *v, int view,
+                          const int32_t *rows_dev, long first, long count,
+                          float *out_dev);
+int xh_net_backward_record(xh_net *n, xh_venv *v, int view,
+                           const int32_t *rows_dev, long first, long count,
+                           const float *dout_dev, int accumulate);
+
 /* ---------------------------------------------------------- tensor ---- */
 /* xylo/tensor.{h,cc} on the device, for the drop-in tensor type
  * (include/xylo_compat/xylo/tensor.h): tensors created with on_device = true

@@ -9,7 +9,8 @@ SRC      := $(PKG)/csrc
 LIB      := $(PKG)/libxylo_hip.so
 HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -Wall \
             -Wno-unused-result -Iinclude -I$(SRC)
-OBJS     := $(SRC)/policy_kernels.o $(SRC)/value_kernels.o \
+OBJS     := $(SRC)/policy_kernels.o $(SRC)/rollout_pack_kernels.o \
+            $(SRC)/value_kernels.o \
             $(SRC)/env_kernels.o $(SRC)/kl_kernels.o \
             $(SRC)/heuristic_kernels.o $(SRC)/dense_kernels.o \
             $(SRC)/pg_kernels.o $(SRC)/venv_kernels.o $(SRC)/venv_gen_kernels.o \
@@ -49,6 +50,7 @@ HDRS     := $(SRC)/xh_device.h $(SRC)/xh_kernels.h $(SRC)/xh_split.h \
             $(SRC)/xh_diag.h $(SRC)/xh_sums.h $(SRC)/xh_seg.h $(SRC)/xh_vstore.h \
             $(SRC)/xh_digest.h $(SRC)/xh_state_blob.h $(SRC)/xh_trainer.h \
             $(SRC)/xh_host.h $(SRC)/xh_ring.h $(SRC)/xh_logit_table.h \
+            $(SRC)/xh_roll_split.h $(SRC)/rollout_pack_layout.h \
             $(SRC)/xh_venv_device.h $(SRC)/xh_venv_sample.inc \
             $(SRC)/xh_venv_table.h \
             include/xylo_hip.h

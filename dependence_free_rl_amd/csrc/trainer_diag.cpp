@@ -468,7 +468,9 @@ int xh_trainer_kernel_info(xh_trainer *t, char *buf, size_t cap) {
     if (!t || !buf || cap == 0) return fail(XH_ERR_INVALID, "null arg");
     std::string roll = kernel_json(t->last_rollout);
     roll.insert(roll.size() - 1, std::string(", \"logit_table\": ") +
-                                     (t->last_rollout.logit_table ? "true" : "false"));
+                                     (t->last_rollout.logit_table ? "true" : "false") +
+                                     ", \"envs_per_wave\": " +
+                                     std::to_string(t->last_rollout.envs_per_wave));
     const std::string js = "{\"rollout_step\": " + roll +
                            ", \"policy_train\": " + kernel_json(t->last_train) +
                            ", \"value\": \"" +

@@ -697,9 +697,23 @@ struct KernelInfo {
   // launch_rollout_step: the logits came from the launch's logit table
   // (rollout_split_kernel's table build) instead of a forward per row
   bool logit_table = false;
+  // launch_rollout_step: envs a wave of the register-stepping rollout steps
+  // at once (0: another kernel).  1 at 64 bins, lane = bin; more on the packed
+  // table kernel (rollout_pack_kernels.hip)
+  int envs_per_wave = 0;
 };
 hipError_t launch_rollout_step(const RolloutArgs &a, int H1, int H2, int grid,
                                hipStream_t s, KernelInfo *info = nullptr);
+// The 64-bin 2-D table rollout with 64 / lanes envs per wave
+// (rollout_pack_kernels.hip): rollout_split_kernel's table
+// launch in another lane layout, for the same RolloutArgs (no e0_mask, not
+// wide / wide_seen) and with the same bits in everything it writes.  lanes per
+// env: kRollPackLanes, the shipped layout, or kRollPackLanesAlt, built beside
+// it for A/B runs (XH_ROLLOUT_PACK_LANES, read per rollout); cus = workgroups
+// at most.
+constexpr int kRollPackLanes = 8, kRollPackLanesAlt = 16;
+int rollout_pack_lanes(int want);
+hipError_t launch_rollout_pack(const RolloutArgs &a, int lanes, int cus, hipStream_t s);
 hipError_t launch_policy_train(const PolicyTrainArgs &a, int H1, int H2,
                                int grid, hipStream_t s,
                                KernelInfo *info = nullptr);

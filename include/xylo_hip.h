@@ -1691,7 +1691,11 @@ int xh_trainer_reset_timing(xh_trainer *t);
  *   at 64 bins, 2-D, [128,128]; off with XH_ROLLOUT_TABLE=0, for a launch
  *   that writes PPO's epoch-0 records, and for a trainer whose slot 0 has
  *   held a bin below -capacity); the same kernel name and arithmetic either
- *   way, and the same bits.
+ *   way, and the same bits.  "envs_per_wave": the envs a wave of the
+ *   register-stepping rollout steps at once -- 8 where the table launch runs
+ *   (its packed kernel; XH_ROLLOUT_TABLE=1 selects the one-env-per-wave table
+ *   launch, 1), 1 for rollout_split_kernel's other 64-bin launches, 2 at 32
+ *   bins, 0 for any other kernel.
  *   V ="vnet_bf16" (the Fin -> 64 -> 32 -> 1 value net on exact bf16
  *   splits: two forwards and one fused backward per update, B*D % 16 == 0,
  *   B*D + D < 416), "mlp3_fused" (the same net on the f32 fused kernels:
